@@ -55,7 +55,7 @@ def test_committed_kernel_counters_belong_to_the_kernels_in_the_tree():
 
 @pytest.mark.gpu
 def test_bench_line_on_the_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--self-check-steps", "20", "--self-check-seconds", "0", "--quad-launches", "4", "--ref-config-frames", "400000"], capture_output=True, text=True, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--self-check-steps", "20", "--self-check-seconds", "0", "--quad-launches", "4", "--ref-config-frames", "400000"], capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -131,13 +131,36 @@ def test_bench_line_on_the_gpu():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_and_its_outputs(tmp_path):
+    """The plain run (no --full): the headline line alone, and --dump-outputs: the sampled hard decisions of the timed batch are the information bits that went in
+    (4.0 dB: every frame of the batch decodes, test_bench_line_on_the_gpu), rebuilt here from bench.py's seeds."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["roofline"]["launches"] == 3 and d["roofline"]["avg_launch_ms"] <= d["ms_per_step"] * 1.02
+    assert abs(d["ms_per_step"] - 1e3 * 4096 / d["fec_frames_per_s"]) < 1e-9 * d["ms_per_step"]
+    assert d["ber"] is None and d["self_check"] is None and "cpu_baseline" not in d and d["roofline"]["live_pmc"] is None and d["extra"]["configs"] is None
+    bits, idx, cwd = (np.load(tmp_path / n) for n in ("bits.npy", "bits_frames.npy", "cwd.npy"))
+    assert bits.dtype == np.float32 and bits.shape == (256, 57600) and cwd.shape == (4096,)
+    rng = np.random.default_rng(1)                                   # bench.py's draws for rank 0: 16 information words, then the word of every frame
+    info = rng.integers(0, 2, (16, 57600))
+    sel = rng.integers(0, 16, 4096)
+    assert np.array_equal(bits, info[sel[idx.astype(np.int64)]].astype(np.float32))
+    assert cwd.sum() >= 4090
+
+
+@pytest.mark.gpu
 def test_bench_under_torchrun_one_rank():
     """The launch line the driver uses for N > 1, with one rank (this pool has one GPU per box): `python -m torch.distributed.run ... bench.py --gpus 1`
     as a FRESH child process (never a re-exec of one that has touched the GPU): RCCL process group, the counters' all-reduce, the max over ranks
     of the timing, one JSON line from rank 0.  What it cannot show is scaling: N > 1 is unmeasured on this pool."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29517",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--self-check-steps", "0", "--self-check-seconds", "0"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--self-check-steps", "0", "--self-check-seconds", "0"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

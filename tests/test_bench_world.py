@@ -30,7 +30,7 @@ def _rank(rank, world, port, outdir, extras):
     import bench
     import bench_stub
     sys.stdout = open(os.path.join(outdir, "out.%d" % rank), "w")
-    argv = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--frames", str(FRAMES), "--quad-launches", "1", "--self-check-steps", "2", "--self-check-seconds", "0", "--no-cpu-baseline"]
+    argv = ["--gpus", str(world), "--full", "--steps", "2", "--warmup", "1", "--frames", str(FRAMES), "--quad-launches", "1", "--self-check-steps", "2", "--self-check-seconds", "0", "--no-cpu-baseline"]
     bench.main(argv + ([] if extras else ["--no-extras"]), runtime=bench_stub.StubRuntime)
     sys.stdout.flush()
     with open(os.path.join(outdir, "calls.%d" % rank), "w") as fh:
@@ -81,6 +81,66 @@ def test_bench_control_path_one_rank_under_a_process_group(tmp_path):
     outs, _ = _run(1, tmp_path, extras=False)
     d = json.loads([l for l in outs[0].splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["ber"]["FRA"] == FRAMES and "cpu_baseline" not in d and d["extra"]["configs"] is None
+
+
+def _plain(argv, monkeypatch, capsys):
+    """bench.main() in this process, world 1 without a process group, over the stand-in; -> (the line, decode calls, entry-point log)"""
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench
+    import bench_stub
+
+    class CountingRx(bench_stub.StubRx):
+        decodes = 0
+
+        def decode_siho_dev(self, *a):
+            CountingRx.decodes += 1
+            super().decode_siho_dev(*a)
+
+    class Runtime(bench_stub.StubRuntime):
+        def __init__(self, local_rank):
+            super().__init__(local_rank)
+            self.Dvbs2Hip = CountingRx
+
+    bench_stub.StubRx.calls = []
+    capsys.readouterr()
+    bench.main(argv, runtime=Runtime)
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), CountingRx.decodes, bench_stub.StubRx.calls
+
+
+def test_plain_run_times_the_steps_and_nothing_else(monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one handle, W + K decodes of the timed batch, the line -- no BER pass, self-check, extras or CPU baseline."""
+    d, decodes, calls = _plain(["--gpus", "1", "--steps", "3", "--warmup", "2", "--frames", str(FRAMES)], monkeypatch, capsys)
+    assert decodes == 2 + 3 and calls == [("create", "QPSK-N_8/9"), ("close",)]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["roofline"]["launches"] == 3 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] - 1e3 * FRAMES / d["fec_frames_per_s"]) < 1e-9 * d["ms_per_step"] and abs(d["value"] - d["fec_frames_per_s"] * 57472) < 1e-6 * d["value"]
+    assert d["ber"] is None and d["self_check"] is None and "cpu_baseline" not in d and d["roofline"]["live_pmc"] is None and d["extra"]["configs"] is None
+
+
+@pytest.mark.parametrize("frames", [FRAMES, 300])
+def test_dump_outputs_are_the_last_steps_and_repeat(frames, tmp_path, monkeypatch, capsys):
+    """--dump-outputs DIR: float32 .npy files of what the timed path returned (the hard decisions of a seeded sample of at most 256 frames, every frame's code-word flag),
+    under 64 MB in all, the same in two runs with the same arguments (seeded inputs)."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for out in dirs:
+        _plain(["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", str(frames), "--dump-outputs", str(out)], monkeypatch, capsys)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["bits.npy", "bits_frames.npy", "cwd.npy"] and sorted(os.listdir(dirs[1])) == names
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 * 10 ** 6
+    import numpy as np
+    a = {n: np.load(dirs[0] / n) for n in names}
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], np.load(dirs[1] / n)), n
+    idx = a["bits_frames.npy"].astype(np.int64)
+    assert a["bits.npy"].shape == (min(frames, 256), 57600) and a["cwd.npy"].shape == (frames,)
+    assert np.array_equal(idx, np.arange(frames)) if frames <= 256 else (len(np.unique(idx)) == 256 and idx.min() >= 0 and idx.max() < frames)
+    assert set(np.unique(a["bits.npy"])) <= {0.0, 1.0}
 
 
 def test_default_runtime_refuses_to_run_without_a_gpu():

@@ -60,7 +60,7 @@ def render(tag, bench_path=None):
     pq, pn, pe = refs_pooled.pooled(rd, "r06_clip_"), refs_pooled.pooled(rd, "r06_tanhnat_"), refs_pooled.pooled(rd, "r06_exact_")
     big = c4["per_F"][-1]
     L = [BEGIN, "",
-         "One MI355X, `python bench.py` (`profiles/%s_bench.json`); parity rows from `results/%s/spa_rules.md`.  Regenerate: `python tools/make_readme_table.py %s --write`." % (tag, tag, tag), "",
+         "One MI355X, `python bench.py --full` (`profiles/%s_bench.json`); parity rows from `results/%s/spa_rules.md`.  Regenerate: `python tools/make_readme_table.py %s --write`." % (tag, tag, tag), "",
          "| what | figure | against its bound | pinned by |", "|---|---|---|---|",
          "| **BASELINE metric** -- configs[1]: LDPC layered NMS, N = 64800 8/9, 10 ite, 4096 frames in HBM | **%.2f Gb/s = %.0f k frames/s** (%.3f ms per step) | counter bytes / time = %.2f of the 8 TB/s HBM peak (`roofline.frac`; SURVEY 8(d) algorithmic figure %.2f x); vector issue %s | `test_ldpc_baseline_batch_of_exactly_4096_frames_matches_oracle` (bit-exact) |" % (
              d["value"] / 1e9, d["fec_frames_per_s"] / 1e3, d["ms_per_step"], ro["frac"] or 0, ro["algorithmic_frac"], ("%.2f" % ro["resources"]["vector_issue"]["frac"]) if ro["resources"]["vector_issue"]["frac"] else "n/a"),

@@ -6,7 +6,7 @@ for ord in 0 1; do for c in 1 3; do
 done; done 2>&1 | tee $OUT/r06_g6_order.txt
 for ord in 0 1; do echo "order=$ord N: $(DVBS2HIP_LDPC_ORDER=$ord ./host/dvbs2_tx_rx_bb --mod-cod QPSK-N_8/9 -m 3.9 -M 4.11 -s 0.1 --dec-implem SPA --dec-ite 50 -F 4096 --clones 1 -e 100000000 --max-frames 300000 | grep -E '^ +[0-9]' | tr '\n' ' ')"; done 2>&1 | tee -a $OUT/r06_g6_order.txt
 for ord in 0 1; do echo "order=$ord NMS-N es: $(DVBS2HIP_LDPC_ORDER=$ord ./host/dvbs2_tx_rx_bb --mod-cod QPSK-N_8/9 -m 3.9 -M 4.11 -s 0.1 --dec-implem NMS --dec-ite 10 -F 4096 --clones 1 -e 100000000 --max-frames 600000 | grep -E '^ +[0-9]' | tr '\n' ' ')"; done 2>&1 | tee -a $OUT/r06_g6_order.txt
-python bench.py --no-cpu-baseline --no-live-pmc > $OUT/r06_g6_bench.json 2> $OUT/r06_g6_bench.err; tail -2 $OUT/r06_g6_bench.err
+python bench.py --full --no-cpu-baseline --no-live-pmc > $OUT/r06_g6_bench.json 2> $OUT/r06_g6_bench.err; tail -2 $OUT/r06_g6_bench.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r06_g6_bench.json') if l.startswith('{')][-1])
