@@ -3,8 +3,8 @@
 Mirrors /root/reference src/mains/CH/main.cpp:25-104 for `--chn-type AWGN` (its default): a sequence
 receive -> add_noise -> send that runs until the input file ends, sigma from `-m` (Eb/N0 in dB) through
 ebn0_to_esn0 / esn0_to_sigma with the code rate K_bch / N_ldpc (main.cpp:35-42), frames of
-p_rad.N = pl_frame * osf complex samples (DVBS2.cpp:175).  The SYNCHRO channel (fading, Farrow fractional
-delay, frequency shift: main.cpp:56-65) is sample-serial test-bench code and is not provided.
+p_rad.N = pl_frame * osf complex samples (DVBS2.cpp:175).  --chn-max-delay D adds the SYNCHRO channel's three delay
+tasks (main.cpp:60-62) in front of the noise; its fading and frequency shift (main.cpp:59,63) are not provided.
 
   python -m dvbs2_amd.ch --mod-cod QPSK-S_8/9 -m 4.5 --rad-rx-file-path after_TX.bin \
          --rad-tx-file-path before_RX_4.5dB.bin --rad-rx-no-loop
@@ -31,6 +31,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rad-rx-no-loop", action="store_true", help="stop at the end of the input file instead of rewinding")
     ap.add_argument("--rad-type", default="USER_BIN", choices=["USER_BIN"])
     ap.add_argument("--chn-type", default="AWGN", choices=["AWGN"])
+    ap.add_argument("--chn-max-delay", type=float, default=None, dest="max_delay",
+                    help="apply the reference channel's three delay tasks (frame, integer and Farrow fractional delay of DVBS2.cpp:520-544) before the noise; D >= 2")
     ap.add_argument("--sim-seed", type=int, default=0, dest="seed")
     ap.add_argument("--max-frames", type=int, default=0, help="stop after this many frames (needed when the input loops)")
     ap.add_argument("--device", type=int, default=0)
@@ -49,6 +51,10 @@ def run(args, out=sys.stdout) -> int:
     rx = Dvbs2Hip(mc.name, max_frames=args.n_frames, device=args.device)
     if args.sim_stats:
         rx.timing_enable(True)
+    if args.max_delay is not None:
+        if args.osf != 2:
+            raise ValueError("--chn-max-delay needs --shp-osf 2: the delay tasks run on frames of pl_frame * 2 complex samples")
+        rx.channel_set_delay(args.max_delay)
     print("Channel AWGN", file=out)
     frames, call = 0, 0
     try:
@@ -57,7 +63,10 @@ def run(args, out=sys.stdout) -> int:
                 x = rcv.receive()
             except ProcessingAborted:
                 break
-            y = rx.add_noise(np.float32(sigma), x.astype(np.float32, copy=False), seed=(args.seed << 32) + call, n_frames=args.n_frames)
+            x = x.astype(np.float32, copy=False)
+            if args.max_delay is not None:
+                x = rx.channel_delay(x.reshape(args.n_frames, -1))             # chn_frm_del -> chn_int_del -> chn_frac_del (CH/main.cpp:60-62)
+            y = rx.add_noise(np.float32(sigma), x, seed=(args.seed << 32) + call, n_frames=args.n_frames)
             snd.send(y)
             frames += args.n_frames
             call += 1

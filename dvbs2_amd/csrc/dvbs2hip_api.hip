@@ -121,6 +121,29 @@ struct dvbs2hip_handle {
     // timing
     float nco_nu = 0.f, nco_omega = 0.f;                   // Synchronizer_freq_coarse in the transmission phase: Multiplier_sine_ccc_naive's nu / omega and its sample counter n
     uint32_t nco_n = 0;
+    // symbol-timing recovery (Synchronizer_Gardner_fast_osf2): per-stream state and carry buffers in ping-pong pairs, like the filters' memories
+    struct {
+        float damping = 0.70710678f, nbw = 5e-5f, dg = 2.f;     // Factory/Module/Synchronizer_timing/Synchronizer_timing.hpp:28-30
+        float kp = 0.f, ki = 0.f;
+        int S = 1;                                              // streams per call (dvbs2hip_sync_timing_set_streams)
+        int Fs = 0;                                             // frames per stream of every call since the last reset (0: not yet fixed)
+        int n_alloc = 0;                                        // streams the buffers below hold
+        StmState *st[2] = {nullptr, nullptr};
+        int st_cur = 0;
+        float *carry[2] = {nullptr, nullptr};                   // n_alloc x cap reals
+        int32_t *ccnt[2] = {nullptr, nullptr};                  // reals held per stream
+        int c_cur = 0;
+        long long cap = 0;                                      // reals per stream
+        int32_t *uf = nullptr;                                  // underflow counts per frame slot, max_frames
+    } stm;
+    // the channel's delay tasks: D, the Farrow taps of mu = D - floor(D), floor(D) + 1 samples of history (ping-pong)
+    struct {
+        float D = 2.f;
+        float b[3] = {0.f, 1.f, 0.f};
+        long long H = 3;
+        float *hist[2] = {nullptr, nullptr};
+        int cur = 0;
+    } chn;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[DVBS2HIP_K_COUNT];
     std::string err;
@@ -143,7 +166,8 @@ int fail(dvbs2hip_t *h, int code, const std::string &msg)
     } while (0)
 
 enum BufId { B_IN = 0, B_OUT, B_AUX0, B_AUX1, B_AUX2, B_AUX3, B_LLR, B_PACKED, B_EST, B_CWD0, B_CWD1, B_INFO, B_SIG, B_TXBCH, B_TXLDPC,
-             B_SFM_CORR, B_SFM_MET, B_SFM_SOF, B_SFM_PLSC, B_SFM_DLY, B_SFM_DTAB, B_SFF_TMP, B_SFF_OUT, B_FLT2, B_MON_BE, B_MON_OUT, B_BCHFLAG, B_ORDER, B_LR_TMP0, B_LR_TMP1, B_LR_TMP2, B_LR_TMP3, B_SFM_SCR, B_SFM_NEED };
+             B_SFM_CORR, B_SFM_MET, B_SFM_SOF, B_SFM_PLSC, B_SFM_DLY, B_SFM_DTAB, B_SFF_TMP, B_SFF_OUT, B_FLT2, B_MON_BE, B_MON_OUT, B_BCHFLAG, B_ORDER, B_LR_TMP0, B_LR_TMP1, B_LR_TMP2, B_LR_TMP3, B_SFM_SCR, B_SFM_NEED,
+             B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY };
 
 int ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
 {
@@ -616,6 +640,8 @@ void dvbs2hip_destroy(dvbs2hip_t *h)
     void *sfm_ptrs[] = {h->sfm.xh[0], h->sfm.xh[1], h->sfm.sofh[0], h->sfm.sofh[1], h->sfm.cv, h->sfm.buff2[0], h->sfm.buff2[1], h->sfm.st[0], h->sfm.st[1],
                         h->sfm.yprev[0], h->sfm.yprev[1], h->sfm.keys, h->sfm.metric, h->sfm.frag, h->d_lr_R, h->d_nat_work, h->ldpc.d_nat_tab, h->ldpc.d_nat_haz, h->d_fir_afrag, h->d_upfir_afrag, h->d_bch_shift, h->d_hist_zero, h->d_hist_junk, h->d_red, h->bch.d_prbs_rw};
     for (void *p : sfm_ptrs) if (p) (void)hipFree(p);
+    void *stm_ptrs[] = {h->stm.st[0], h->stm.st[1], h->stm.carry[0], h->stm.carry[1], h->stm.ccnt[0], h->stm.ccnt[1], h->stm.uf, h->chn.hist[0], h->chn.hist[1]};
+    for (void *p : stm_ptrs) if (p) (void)hipFree(p);
     if (h->lr_err_host) (void)hipHostFree(h->lr_err_host);
     if (h->h_red) (void)hipHostFree(h->h_red);
     void *ptrs[] = {h->ldpc.d_cu_ctr, h->ldpc.d_w8_tab, h->ldpc.d_w8_atab, h->ldpc.d_w8_rows, h->ldpc.d_entries, h->ldpc.d_layer_deg, h->ldpc.d_layer_lvl, h->ldpc.d_groups, h->bch.d_syn_tab, h->bch.d_exp, h->bch.d_log,
@@ -1176,6 +1202,236 @@ int dvbs2hip_extract_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx
     Timer tm(h, DVBS2HIP_K_MISC);
     HIPCHK(h, decimate_launch(X, Y, (long long)n_cplx_out * F, osf, offset, (long long)n_cplx_out * F * osf, h->stream));
     return 0;
+}
+
+// ------------------------------------------------------------------ symbol-timing recovery (Synchronizer_Gardner_fast_osf2) and the channel's delay tasks (k_timing.hip)
+// Synchronizer_Gardner_fast_osf2::set_loop_filter_coeffs, Synchronizer_Gardner_fast_osf2.cpp:188-198 (in float, as the reference's R = float build evaluates it)
+static void stm_gains(float damping, float nbw, float dg, float &kp, float &ki)
+{
+    const float K0 = -1.f;
+    const float theta = nbw / 2.0f / (damping + 0.25f / damping);
+    const float d = (1.f + 2.f * damping * theta + theta * theta) * K0 * dg;
+    kp = (4.f * damping * theta) / d;
+    ki = (4.f * theta * theta) / d;
+}
+
+static int stm_frame_cplx(dvbs2hip_t *h) { return h->pl_frame * h->fir_osf; }        // N_in / 2: pl_frame * osf complex samples per frame (DVBS2.cpp:175)
+
+static int stm_check(dvbs2hip_t *h, int F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (h->fir_osf != 2) return fail(h, DVBS2HIP_EUNSUPPORTED, "the timing synchronizer is Synchronizer_Gardner_fast_osf2: two samples per symbol only");
+    if (F % h->stm.S) return fail(h, DVBS2HIP_EINVAL, "'n_frames' has to be a multiple of the stream count ('n_frames' = " + std::to_string(F) + ", streams = " + std::to_string(h->stm.S) + ").");
+    // the carry buffers (4 N F/S reals per stream) and the underflow counters (one per frame slot) are laid out for one F/S: a change needs a reset first
+    if (h->stm.Fs && F / h->stm.S != h->stm.Fs)
+        return fail(h, DVBS2HIP_EINVAL, "'n_frames' / streams has changed since the last reset (" + std::to_string(F / h->stm.S) + " instead of " + std::to_string(h->stm.Fs) +
+                                            " frames per stream): call dvbs2hip_sync_timing_reset first");
+    return 0;
+}
+
+// state for S streams, all zero (= Synchronizer_timing::reset + _reset); the carry buffers are sized on the first extract
+static int stm_alloc(dvbs2hip_t *h, int S)
+{
+    auto &T = h->stm;
+    if (T.n_alloc < S) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < 2; i++) {
+            if (T.st[i]) { HIPCHK(h, hipFree(T.st[i])); T.st[i] = nullptr; }
+            if (T.ccnt[i]) { HIPCHK(h, hipFree(T.ccnt[i])); T.ccnt[i] = nullptr; }
+            if (T.carry[i]) { HIPCHK(h, hipFree(T.carry[i])); T.carry[i] = nullptr; }
+        }
+        T.cap = 0;
+        T.n_alloc = 0;
+        for (int i = 0; i < 2; i++) {
+            if (hipMalloc((void **)&T.st[i], sizeof(StmState) * (size_t)S) != hipSuccess || hipMalloc((void **)&T.ccnt[i], sizeof(int32_t) * (size_t)S) != hipSuccess)
+                return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the timing synchronizer's state failed");
+        }
+        if (!T.uf && hipMalloc((void **)&T.uf, sizeof(int32_t) * (size_t)h->max_frames) != hipSuccess)
+            return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the timing synchronizer's underflow counters failed");
+        T.n_alloc = S;
+    }
+    if (!T.uf && hipMalloc((void **)&T.uf, sizeof(int32_t) * (size_t)h->max_frames) != hipSuccess)
+        return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the timing synchronizer's underflow counters failed");
+    T.st_cur = T.c_cur = 0;
+    T.Fs = 0;
+    HIPCHK(h, hipMemsetAsync(T.st[0], 0, sizeof(StmState) * (size_t)S, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.ccnt[0], 0, sizeof(int32_t) * (size_t)S, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.uf, 0, sizeof(int32_t) * (size_t)h->max_frames, h->stream));
+    return 0;
+}
+
+// carry buffers of at least `cap` reals per stream; what the old ones held moves over (a strided copy)
+static int stm_carry(dvbs2hip_t *h, long long cap)
+{
+    auto &T = h->stm;
+    if (T.cap >= cap) return 0;
+    float *nb[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; i++)
+        if (hipMalloc((void **)&nb[i], sizeof(float) * (size_t)cap * (size_t)T.n_alloc) != hipSuccess) {
+            if (nb[0]) (void)hipFree(nb[0]);
+            return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the timing synchronizer's carry buffers failed");
+        }
+    if (T.cap > 0) {
+        HIPCHK(h, hipMemcpy2DAsync(nb[T.c_cur], sizeof(float) * (size_t)cap, T.carry[T.c_cur], sizeof(float) * (size_t)T.cap, sizeof(float) * (size_t)T.cap, (size_t)T.n_alloc,
+                                   hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    for (int i = 0; i < 2; i++) { if (T.carry[i]) HIPCHK(h, hipFree(T.carry[i])); T.carry[i] = nb[i]; }
+    T.cap = cap;
+    return 0;
+}
+
+int dvbs2hip_sync_timing_set_params(dvbs2hip_t *h, float damping, float nbw, float detector_gain)
+{
+    if (!h) return DVBS2HIP_EINVAL;
+    if (!(damping > 0.f) || !(nbw > 0.f) || !(detector_gain > 0.f) || !std::isfinite(damping) || !std::isfinite(nbw) || !std::isfinite(detector_gain))
+        return fail(h, DVBS2HIP_EINVAL, "'damping', 'nbw' and 'detector_gain' have to be positive");
+    h->stm.damping = damping; h->stm.nbw = nbw; h->stm.dg = detector_gain;
+    stm_gains(damping, nbw, detector_gain, h->stm.kp, h->stm.ki);
+    return 0;
+}
+
+int dvbs2hip_sync_timing_get_gains(dvbs2hip_t *h, float *proportional, float *integrator)
+{
+    if (!h || !proportional || !integrator) return DVBS2HIP_EINVAL;
+    stm_gains(h->stm.damping, h->stm.nbw, h->stm.dg, *proportional, *integrator);
+    return 0;
+}
+
+int dvbs2hip_sync_timing_set_streams(dvbs2hip_t *h, int32_t S)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (S < 1 || S > h->max_frames) return fail(h, DVBS2HIP_EINVAL, "'S' has to be in [1, max_frames] ('S' = " + std::to_string(S) + ").");
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    h->stm.S = S;
+    return stm_alloc(h, S);
+}
+
+int dvbs2hip_sync_timing_reset(dvbs2hip_t *h)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    return stm_alloc(h, h->stm.S);
+}
+
+int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t F)
+{
+    int r = stm_check(h, F); if (r) return r;
+    if (!X_N1 || !Y_N1 || !B_N1 || !MU) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    auto &T = h->stm;
+    if (T.n_alloc < T.S) {
+        if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first synchronize allocates the streams' state");
+        if ((r = stm_alloc(h, T.S))) return r;
+    }
+    T.Fs = F / T.S;
+    if (T.kp == 0.f) stm_gains(T.damping, T.nbw, T.dg, T.kp, T.ki);
+    Timer tm(h, DVBS2HIP_K_MISC);
+    HIPCHK(h, stm_sync_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.kp, T.ki, h->stream));
+    T.st_cur ^= 1;
+    return 0;
+}
+
+int dvbs2hip_sync_timing_synchronize(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t F)
+{
+    int r = stm_check(h, F); if (r) return r;
+    if (!X_N1 || !Y_N1 || !B_N1 || !MU) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    const size_t n = (size_t)F * 2 * stm_frame_cplx(h);
+    void *dx, *dy, *db, *dmu;
+    if ((r = ensure(h, B_STM_X, n * sizeof(float), &dx)) || (r = ensure(h, B_STM_Y, n * sizeof(float), &dy)) || (r = ensure(h, B_STM_B, n * sizeof(int32_t), &db)) ||
+        (r = ensure(h, B_STM_MU, (size_t)F * sizeof(float), &dmu)))
+        return r;
+    HIPCHK(h, hipMemcpyAsync(dx, X_N1, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if ((r = dvbs2hip_sync_timing_synchronize_dev(h, (const float *)dx, (float *)dy, (int32_t *)db, (float *)dmu, F))) return r;
+    HIPCHK(h, hipMemcpyAsync(Y_N1, dy, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(B_N1, db, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(MU, dmu, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int dvbs2hip_sync_timing_extract_dev(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t F)
+{
+    int r = stm_check(h, F); if (r) return r;
+    if (!Y_N1 || !B_N1 || !Y_N2 || !UFW || !RDY) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    auto &T = h->stm;
+    if (T.n_alloc < T.S) {
+        if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first extract allocates the streams' state");
+        if ((r = stm_alloc(h, T.S))) return r;
+    }
+    const int N = stm_frame_cplx(h), Fs = F / T.S;
+    T.Fs = Fs;
+    const long long cap = 4LL * Fs * N;                  // reals per stream: four frames' worth of output per frame of the call
+    if (T.cap < cap) {
+        if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first extract of this size allocates");
+        if ((r = stm_carry(h, cap))) return r;
+    }
+    Timer tm(h, DVBS2HIP_K_MISC);
+    HIPCHK(h, stm_extract_launch(Y_N1, B_N1, Y_N2, UFW, RDY, T.carry[T.c_cur], T.ccnt[T.c_cur], T.carry[T.c_cur ^ 1], T.ccnt[T.c_cur ^ 1], T.uf, T.S, Fs, N, T.cap, h->stream));
+    T.c_cur ^= 1;
+    return 0;
+}
+
+int dvbs2hip_sync_timing_extract(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t F)
+{
+    int r = stm_check(h, F); if (r) return r;
+    if (!Y_N1 || !B_N1 || !Y_N2 || !UFW || !RDY) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    const int N = stm_frame_cplx(h), S = h->stm.S;
+    const size_t n = (size_t)F * 2 * N, n2 = (size_t)F * N;
+    void *dy, *db, *dy2, *du, *dr;
+    if ((r = ensure(h, B_STM_Y, n * sizeof(float), &dy)) || (r = ensure(h, B_STM_B, n * sizeof(int32_t), &db)) || (r = ensure(h, B_STM_Y2, n2 * sizeof(float), &dy2)) ||
+        (r = ensure(h, B_STM_UFW, (size_t)F * sizeof(int32_t), &du)) || (r = ensure(h, B_STM_RDY, (size_t)S * sizeof(int32_t), &dr)))
+        return r;
+    HIPCHK(h, hipMemcpyAsync(dy, Y_N1, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(db, B_N1, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dy2, Y_N2, n2 * sizeof(float), hipMemcpyHostToDevice, h->stream));       // the frames of a stream that is not ready keep what the socket held past the symbols written
+    if ((r = dvbs2hip_sync_timing_extract_dev(h, (const float *)dy, (const int32_t *)db, (float *)dy2, (int32_t *)du, (int32_t *)dr, F))) return r;
+    HIPCHK(h, hipMemcpyAsync(Y_N2, dy2, n2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(UFW, du, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(RDY, dr, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int dvbs2hip_channel_set_delay(dvbs2hip_t *h, float D)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (!(D >= 2.f) || !(D <= 16777216.f)) return fail(h, DVBS2HIP_EINVAL, "Argument 'max_delay' has to be greater than 2.");     // DVBS2.cpp:129-133 (and at most 2^24 samples here)
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    auto &C = h->chn;
+    const float mu = D - floorf(D);                                     // DVBS2.cpp:522
+    const float half_mu = 0.5f * mu, half_mu_square = half_mu * mu;    // Filter_Farrow_ccr_naive::set_mu
+    C.b[0] = half_mu_square - half_mu;
+    C.b[1] = 1.0f - half_mu - half_mu_square;
+    C.b[2] = mu + half_mu - half_mu_square;
+    const long long H = (long long)floorf(D) + 1;                       // (floor(D) - 2) samples of delay line + 3 of the Farrow filter
+    if (H > C.H || !C.hist[0]) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < 2; i++) {
+            if (C.hist[i]) { HIPCHK(h, hipFree(C.hist[i])); C.hist[i] = nullptr; }
+            if (hipMalloc((void **)&C.hist[i], sizeof(float) * 2 * (size_t)H) != hipSuccess) return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the channel delay's history failed");
+        }
+    }
+    C.D = D; C.H = H; C.cur = 0;
+    HIPCHK(h, hipMemsetAsync(C.hist[0], 0, sizeof(float) * 2 * (size_t)H, h->stream));
+    return 0;
+}
+
+int dvbs2hip_channel_delay_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    auto &C = h->chn;
+    if (!C.hist[0] && (r = dvbs2hip_channel_set_delay(h, C.D))) return r;
+    Timer tm(h, DVBS2HIP_K_MISC);
+    HIPCHK(h, chn_delay_launch(X, Y, C.hist[C.cur], C.hist[C.cur ^ 1], C.H, (long long)F * stm_frame_cplx(h), C.b[0], C.b[1], C.b[2], h->stream));
+    C.cur ^= 1;
+    return 0;
+}
+
+int dvbs2hip_channel_delay(dvbs2hip_t *h, const float *X, float *Y, int32_t F)
+{
+    const size_t n = h ? (size_t)2 * stm_frame_cplx(h) : 0;
+    return host_wrap(h, X, n, Y, n, F, [&](const float *a, float *b, int nf) { return dvbs2hip_channel_delay_dev(h, a, b, nf); });
 }
 
 // ------------------------------------------------------------------ N4: frame synchronizer (Synchronizer_frame_DVBS2_fast)

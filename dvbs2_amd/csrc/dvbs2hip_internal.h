@@ -315,4 +315,19 @@ hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float
 hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
                               const int32_t *Dtab, int n, int nbuff2, int F, hipStream_t s, int32_t *list = nullptr, const float **src = nullptr);
 
+// ---------------------------------------------------------------- symbol-timing recovery and the channel's delay tasks (k_timing.hip)
+// one stream's state of Synchronizer_Gardner_fast_osf2 between calls (all zeros = _reset): the Farrow history x[n-1], x[n-2], x[n-3], the TED buffer {T0, T1}, mu (the Farrow
+// taps follow from it), the NCO, the loop filter, the last symbol, the strobe flags
+struct StmState {
+    float h[6];
+    float ted[4];
+    float mu, nco, lf_prev_in, lf_output;
+    float last[2];
+    int32_t is_strobe, prev_is_strobe;
+};
+hipError_t stm_sync_launch(const float *X, float *Y, int32_t *B, float *MU, const StmState *st_in, StmState *st_out, int S, int Fs, int N, float kp, float ki, hipStream_t s);
+hipError_t stm_extract_launch(const float *Y1, const int32_t *B1, float *Y2, int32_t *UFW, int32_t *RDY, const float *c_in, const int32_t *n_in, float *c_out, int32_t *n_out,
+                              int32_t *uf, int S, int Fs, int N, long long cap, hipStream_t s);
+hipError_t chn_delay_launch(const float *X, float *Y, const float *h_in, float *h_out, long long H, long long T, float b0, float b1, float b2, hipStream_t s);
+
 }  // namespace dvbs2

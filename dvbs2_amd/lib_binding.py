@@ -110,6 +110,17 @@ ABI = {
     "dvbs2hip_sync_coarse_reset": (C.c_int, [_vp]),
     "dvbs2hip_sync_coarse_synchronize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
     "dvbs2hip_sync_coarse_synchronize_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "dvbs2hip_sync_timing_set_params": (C.c_int, [_vp, _f, _f, _f]),
+    "dvbs2hip_sync_timing_get_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "dvbs2hip_sync_timing_set_streams": (C.c_int, [_vp, _i]),
+    "dvbs2hip_sync_timing_reset": (C.c_int, [_vp]),
+    "dvbs2hip_sync_timing_synchronize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_timing_synchronize_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_timing_extract": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_timing_extract_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_channel_set_delay": (C.c_int, [_vp, _f]),
+    "dvbs2hip_channel_delay": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_channel_delay_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_pl_descramble": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_pl_descramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_remove_plh": (C.c_int, [_vp, _vp, _vp, _i]),

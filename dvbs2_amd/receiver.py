@@ -229,6 +229,57 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_sync_coarse_synchronize(self.h, _ptr(X), _ptr(FRQ), _ptr(PHS), _ptr(Y), X.size // (2 * n_frames), n_frames))
         return FRQ, PHS, Y
 
+    def sync_timing_set_params(self, damping=0.5 ** 0.5, nbw=5e-5, detector_gain=2.0):
+        self._chk(self.L.dvbs2hip_sync_timing_set_params(self.h, float(damping), float(nbw), float(detector_gain)))
+
+    def sync_timing_gains(self):
+        """(proportional, integrator) gains of the loop filter (Synchronizer_Gardner_fast_osf2::set_loop_filter_coeffs)"""
+        kp, ki = C.c_float(), C.c_float()
+        self._chk(self.L.dvbs2hip_sync_timing_get_gains(self.h, C.byref(kp), C.byref(ki)))
+        return kp.value, ki.value
+
+    def sync_timing_set_streams(self, S):
+        self._chk(self.L.dvbs2hip_sync_timing_set_streams(self.h, int(S)))
+        self.stm_streams = int(S)
+
+    def sync_timing_reset(self):
+        self._chk(self.L.dvbs2hip_sync_timing_reset(self.h))
+
+    def sync_timing_synchronize(self, X_N1):
+        """Gardner timing loop over F frames of pl_frame * 2 complex samples -> (Y_N1, B_N1, MU[F])"""
+        X, F = self._frames(X_N1, 4 * self.pl_frame, np.float32)
+        Y, Bf, MU = np.empty_like(X), np.empty(X.shape, np.int32), np.empty(F, np.float32)
+        self._chk(self.L.dvbs2hip_sync_timing_synchronize(self.h, _ptr(X), _ptr(Y), _ptr(Bf), _ptr(MU), F))
+        return Y, Bf, MU
+
+    def sync_timing_synchronize_dev(self, X, Y, B_N1, MU, n_frames):
+        self._chk(self.L.dvbs2hip_sync_timing_synchronize_dev(self.h, _ptr(X), _ptr(Y), _ptr(B_N1), _ptr(MU), n_frames))
+
+    def sync_timing_extract(self, Y_N1, B_N1, out=None):
+        """strobed samples -> (Y_N2[F, 2 pl_frame], UFW[F], RDY[S]); the frames of a stream that is not ready keep what `out` held past its symbols"""
+        Y, F = self._frames(Y_N1, 4 * self.pl_frame, np.float32)
+        Bf, _ = self._frames(B_N1, 4 * self.pl_frame, np.int32)
+        Y2 = np.zeros((F, 2 * self.pl_frame), np.float32) if out is None else out
+        UFW, RDY = np.empty(F, np.int32), np.empty(getattr(self, "stm_streams", 1), np.int32)
+        self._chk(self.L.dvbs2hip_sync_timing_extract(self.h, _ptr(Y), _ptr(Bf), _ptr(Y2), _ptr(UFW), _ptr(RDY), F))
+        return Y2, UFW, RDY
+
+    def sync_timing_extract_dev(self, Y_N1, B_N1, Y_N2, UFW, RDY, n_frames):
+        self._chk(self.L.dvbs2hip_sync_timing_extract_dev(self.h, _ptr(Y_N1), _ptr(B_N1), _ptr(Y_N2), _ptr(UFW), _ptr(RDY), n_frames))
+
+    def channel_set_delay(self, D):
+        self._chk(self.L.dvbs2hip_channel_set_delay(self.h, float(D)))
+
+    def channel_delay(self, X):
+        """the channel's frame, integer and fractional delay tasks over F consecutive frames of pl_frame * 2 complex samples"""
+        X, F = self._frames(X, 4 * self.pl_frame, np.float32)
+        Y = np.empty_like(X)
+        self._chk(self.L.dvbs2hip_channel_delay(self.h, _ptr(X), _ptr(Y), F))
+        return Y
+
+    def channel_delay_dev(self, X, Y, n_frames):
+        self._chk(self.L.dvbs2hip_channel_delay_dev(self.h, _ptr(X), _ptr(Y), n_frames))
+
     def pl_descramble(self, Y_N1):
         X, F = self._frames(Y_N1, 2 * self.pl_frame, np.float32)
         out = np.empty_like(X)

@@ -1,5 +1,5 @@
-"""`dvbs2_rx` work-alike WITHOUT the sample-serial loops (timing recovery, coarse frequency: out of scope, SURVEY.md
-section 8): raw IQ file -> front gain stage (Multiplier_AGC, RX/main_sched.cpp:197) -> coarse frequency shift (--coarse-freq; :198) -> matched filter (a5) -> extraction at a known symbol phase -> gain stage
+"""`dvbs2_rx` work-alike without the coarse frequency loop (out of scope): raw IQ file -> front gain stage (Multiplier_AGC, RX/main_sched.cpp:197)
+-> coarse frequency shift (--coarse-freq; :198) -> matched filter (a5) -> symbol timing (--stm-type: extraction at a known phase, or FAST, the Gardner loop on the GPU, :202-204) -> gain stage
 (main_sched.cpp:205) -> frame synchronizer (N4) -> pilot-aided phase synchronizer (N4, optional) -> fused RX chain (a7 .. a8) -> monitor against the source pattern -> sink.  It serves
 files made by `dvbs2_amd.tx` / `dvbs2_amd.ch` (or by the reference's dvbs2_tx / dvbs2_ch without timing or frequency
 offsets): README.md:151-169 of the reference.
@@ -40,6 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
                                                                    "phase (the frequency shift) with this as its loop's frozen estimate; the loop itself is sample-serial and out of scope")
+    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="symbol timing: PERFECT takes every osf-th sample from --timing-offset (the default here); "
+                                                                                     "FAST runs the reference's Gardner loop (Synchronizer_Gardner_fast_osf2) on the GPU")
+    ap.add_argument("--stm-df", type=float, default=0.5 ** 0.5, help="damping factor of the Gardner loop filter")
+    ap.add_argument("--stm-nbw", type=float, default=5e-5, help="normalized bandwidth of the Gardner loop filter")
+    ap.add_argument("--stm-dg", type=float, default=2.0, help="detector gain of the Gardner loop filter")
     ap.add_argument("--no-agc", action="store_true", help="leave out the two gain stages of the reference's graph (front_agc on the samples, mult_agc on the symbols)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sim-stats", action="store_true", help="per-kernel-group device time at the end (the reference's --sim-stats)")
@@ -58,6 +63,11 @@ def run(args, out=sys.stdout) -> dict:
         rx.timing_enable(True)
     if args.coarse_freq:
         rx.sync_coarse_set_freq(args.coarse_freq)
+    fast = args.stm_type == "FAST"
+    if fast:
+        if osf != 2:
+            raise ValueError("--stm-type FAST is the Gardner loop at two samples per symbol (--shp-osf 2)")
+        rx.sync_timing_set_params(args.stm_df, args.stm_nbw, args.stm_dg)
     rcv = RadioUserBinary(n * osf, input_filename=args.rad_rx_file_path, auto_reset=not args.rad_rx_no_loop, n_frames=F)
     snk = SinkUserBinary(args.snk_path, mc.K_bch) if args.snk_path else None
     off = args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf          # two group delays of grp_delay * osf samples
@@ -76,13 +86,21 @@ def run(args, out=sys.stdout) -> dict:
                 x = rx.agc(x, n_frames=F, output_energy=1.0 / osf)                  # front_agc: DVBS2.cpp:660-664
             if args.coarse_freq:
                 _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)                  # sync_coarse_f: RX/main_sched.cpp:198-200
-            mf = np.concatenate([tail, rx.filter(x, n_frames=F).reshape(-1, 2)])
-            mf, skip = mf[skip:], 0                                                # perfect timing: every osf-th sample from `off`
-            n_sym = (mf.shape[0] // osf // n) * n                                  # whole frames of symbols
-            if n_sym == 0:
-                tail = mf
-                continue
-            sym, tail = mf[: n_sym * osf : osf], mf[n_sym * osf:]
+            if fast:
+                # sync_timing: synchronize -> extract (RX/main_sched.cpp:202-204); a call that underflows holds its symbols for the next one
+                y, b, _ = rx.sync_timing_synchronize(rx.filter(x, n_frames=F).reshape(F, -1))
+                y2, _, rdy = rx.sync_timing_extract(y, b)
+                if not rdy[0]:
+                    continue
+                sym, n_sym = y2.reshape(-1, 2), F * n
+            else:
+                mf = np.concatenate([tail, rx.filter(x, n_frames=F).reshape(-1, 2)])
+                mf, skip = mf[skip:], 0                                            # perfect timing: every osf-th sample from `off`
+                n_sym = (mf.shape[0] // osf // n) * n                              # whole frames of symbols
+                if n_sym == 0:
+                    tail = mf
+                    continue
+                sym, tail = mf[: n_sym * osf : osf], mf[n_sym * osf:]
             for b0 in range(0, n_sym // n, F):
                 blk = np.ascontiguousarray(sym[b0 * n:(b0 + F) * n])
                 Fb = blk.shape[0] // n

@@ -13,8 +13,9 @@
 //   dvbs2_rx_bb --matched-filter --mod-cod QPSK-S_8/9 -F 4 --in shaped_stream.f32 --src sent_bits.i32 --src-delay 1 --mon-skip 1 --out info_bits.i32
 //      The binding lines between the modules built here are the reference's, character for character (marked "main_sched.cpp:NNN").
 //      The sample-serial loops in between are out of scope and are played by stand-ins defined below:
-//      sync_coarse_f = identity (no frequency offset), sync_timing = decimation by osf at the even phase (perfect timing),
-//      no AGC; the source is a file of the sent payloads delayed by --src-delay frames (the frame synchronizer's latency;
+//      sync_coarse_f = identity (no frequency offset), sync_timing = decimation by osf at the even phase (perfect timing) unless
+//      --stm-type FAST binds Synchronizer_timing_hip (the Gardner loop, main_sched.cpp:202-204; a batch whose extract underflows stops
+//      behind it, as the reference's sequence does at processing_aborted, and the payload source only advances for batches that go through); the source is a file of the sent payloads delayed by --src-delay frames (the frame synchronizer's latency;
 //      what Filter_buffered_delay does in the TX_RX mains).
 //
 // With --src the monitor runs (check_errors in (1), check_errors2 with its BE / FE / BER / FER sockets read by probe stand-ins
@@ -100,7 +101,7 @@ public:
 }}  // namespace aff3ct::module
 
 static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite, float alpha, const std::string &implem, const std::string &in_path,
-                                    const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq)
+                                    const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq, bool stm_fast)
 {
     using namespace module;
     const int osf = 2;
@@ -113,7 +114,8 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     std::unique_ptr<Synchronizer_freq_coarse_hip<>> sync_coarse_f(new Synchronizer_freq_coarse_hip<>(ctx, N_pl * osf));                  // the frequency shift of the transmission phase
     sync_coarse_f->set_curr_freq(coarse_freq);                                                                                          // (what the reference's loop would have settled on: --coarse-freq)
     std::unique_ptr<Filter_FIR_hip>              matched_flt  (new Filter_FIR_hip(ctx, N_pl * osf));
-    std::unique_ptr<Sync_timing_perfect>         sync_timing  (new Sync_timing_perfect(N_pl * osf, osf, F));
+    std::unique_ptr<Sync_timing_perfect>         sync_timing_p(stm_fast ? nullptr : new Sync_timing_perfect(N_pl * osf, osf, F));   // the default: a known phase
+    std::unique_ptr<Synchronizer_timing_hip<>>   sync_timing  (stm_fast ? new Synchronizer_timing_hip<>(ctx) : nullptr);               // --stm-type FAST (Gardner)
     std::unique_ptr<Synchronizer_frame_hip<>>    sync_frame   (new Synchronizer_frame_hip<>(ctx));
     std::unique_ptr<Scrambler_PL_hip>            pl_scrambler (new Scrambler_PL_hip(ctx));
     std::unique_ptr<Synchronizer_freq_fine_hip<>> sync_fine_lr(new Synchronizer_freq_fine_hip<>(ctx, true));
@@ -137,8 +139,15 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     (*matched_flt  )[             flt::sck::filter1      ::X_N1    ] = (*sync_coarse_f)[             sfc::sck::synchronize  ::Y_N2    ];   // main_sched.cpp:199
     (*matched_flt  )[             flt::sck::filter2      ::X_N1    ] = (*sync_coarse_f)[             sfc::sck::synchronize  ::Y_N2    ];   // main_sched.cpp:200
     (*matched_flt  )[             flt::sck::filter2      ::Y_N2h   ] = (*matched_flt  )[             flt::sck::filter1      ::Y_N2    ];   // main_sched.cpp:201
-    sync_timing->in() = (*matched_flt  )[             flt::sck::filter2      ::Y_N2    ];                                                // stand-in for :202-204 (Gardner)
-    (*mult_agc     )[             mlt::sck::imultiply    ::X_N     ] = sync_timing->out();                                              // main_sched.cpp:205, producer = the stand-in
+    if (stm_fast) {
+    (*sync_timing  )[             stm::sck::synchronize  ::X_N1    ] = (*matched_flt  )[             flt::sck::filter2      ::Y_N2    ];   // main_sched.cpp:202
+    (*sync_timing  )[             stm::sck::extract      ::B_N1    ] = (*sync_timing  )[             stm::sck::synchronize  ::B_N1    ];   // main_sched.cpp:203
+    (*sync_timing  )[             stm::sck::extract      ::Y_N1    ] = (*sync_timing  )[             stm::sck::synchronize  ::Y_N1    ];   // main_sched.cpp:204
+    (*mult_agc     )[             mlt::sck::imultiply    ::X_N     ] = (*sync_timing  )[             stm::sck::extract      ::Y_N2    ];   // main_sched.cpp:205
+    } else {
+    sync_timing_p->in() = (*matched_flt)[             flt::sck::filter2      ::Y_N2    ];                                                // stand-in for :202-204 (a known phase)
+    (*mult_agc     )[             mlt::sck::imultiply    ::X_N     ] = sync_timing_p->out();                                            // main_sched.cpp:205, producer = the stand-in
+    }
     (*sync_frame   )[             sfm::sck::synchronize1 ::X_N1    ] = (*mult_agc     )[             mlt::sck::imultiply    ::Z_N     ];   // main_sched.cpp:206
     (*sync_frame   )[             sfm::sck::synchronize2 ::X_N1    ] = (*mult_agc     )[             mlt::sck::imultiply    ::Z_N     ];   // main_sched.cpp:207
     (*sync_frame   )[             sfm::sck::synchronize2 ::cor_SOF ] = (*sync_frame   )[             sfm::sck::synchronize1 ::cor_SOF ];   // main_sched.cpp:208
@@ -161,8 +170,15 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     prb_bfer_ber    [spu::module::prb::sck::probe        ::in      ] = (*monitor      )[             mnt::sck::check_errors2::BER     ];   // main_sched.cpp:246
     prb_bfer_fer    [spu::module::prb::sck::probe        ::in      ] = (*monitor      )[             mnt::sck::check_errors2::FER     ];   // main_sched.cpp:247
 
-    spu::runtime::Sequence seq({&(*source)[spu::module::src::tsk::generate], &(*front_agc)(), &(*sync_coarse_f)(), &(*matched_flt)[flt::tsk::filter1], &(*matched_flt)[flt::tsk::filter2],
-                                &(*sync_timing)(), &(*mult_agc)(), &(*sync_frame)[sfm::tsk::synchronize1], &(*sync_frame)[sfm::tsk::synchronize2], &(*pl_scrambler)(),
+    std::vector<spu::runtime::Task *> timing_tasks;
+    if (stm_fast) timing_tasks = {&(*sync_timing)[stm::tsk::synchronize], &(*sync_timing)[stm::tsk::extract]};
+    else timing_tasks = {&(*sync_timing_p)()};
+    std::vector<spu::runtime::Task *> order = {&(*front_agc)(), &(*sync_coarse_f)(), &(*matched_flt)[flt::tsk::filter1],
+                                               &(*matched_flt)[flt::tsk::filter2]};
+    order.insert(order.end(), timing_tasks.begin(), timing_tasks.end());
+    spu::runtime::Sequence seq(order);
+    // the tasks behind the timing synchronizer: a batch whose extract underflows ends there (the reference's sequence stops at a processing_aborted task)
+    spu::runtime::Sequence seq2({&(*source)[spu::module::src::tsk::generate], &(*mult_agc)(), &(*sync_frame)[sfm::tsk::synchronize1], &(*sync_frame)[sfm::tsk::synchronize2], &(*pl_scrambler)(),
                                 &(*sync_fine_lr)(), &(*sync_fine_pf)(), &(*framer)(), &(*estimator)(), &(*modem)(), &(*itl_rx)(), &(*LDPC_decoder)(),
                                 &(*BCH_decoder)(), &(*bb_scrambler)(), &(*monitor)[mnt::tsk::check_errors2], &prb_bfer_be[spu::module::prb::tsk::probe],
                                 &prb_bfer_fe[spu::module::prb::tsk::probe], &prb_bfer_ber[spu::module::prb::tsk::probe], &prb_bfer_fer[spu::module::prb::tsk::probe]});
@@ -172,8 +188,15 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     std::ofstream out;
     if (!out_path.empty()) out.open(out_path, std::ios::binary);
     size_t batches = 0;
+    size_t aborted = 0;
     while (in.read(reinterpret_cast<char *>(rx_samples.data()), rx_samples.size() * sizeof(float))) {
-        seq.exec_step();
+        try {
+            seq.exec_step();
+        } catch (const spu::tools::processing_aborted &) {
+            aborted++;                  // too few symbols for F frames: they wait in the synchronizer for the next batch
+            continue;
+        }
+        seq2.exec_step();
         if ((int)batches < mon_skip) monitor->reset();       // the synchronizers are still locking: keep these batches out of the statistics (the reference's waiting and learning phases)
         // The fine frequency estimate of ONE frame is noisy (sigma ~2.5e-4 cycles per symbol at 16 dB against the +-3.4e-4 the pilot-aided stage can take back): it lives on its memory of
         // alpha = 0.999.  In the reference the fine synchronizers do not run before the frame synchronizer has locked -- its learning phases 1 and 2 end at sync_frame
@@ -188,6 +211,7 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     monitor->get(fra, be, fe);
     std::printf("# %s F=%d %s ite=%d matched-filter graph | batches %zu | FRA %llu BE %llu FE %llu\n", modcod.c_str(), F, implem.c_str(), n_ite, batches,
                 (unsigned long long)fra, (unsigned long long)be, (unsigned long long)fe);
+    if (stm_fast) std::printf("# timing FAST | batches aborted by an underflow %zu\n", aborted);
     std::printf("# probes | BE %d FE %d BER %.3e FER %.3e | DEL %d FLG %d\n", prb_bfer_be.last, prb_bfer_fe.last, (double)prb_bfer_ber.last, (double)prb_bfer_fer.last,
                 (*sync_frame)[sfm::sck::synchronize2::DEL].get_dataptr<int>()[F - 1], (*sync_frame)[sfm::sck::synchronize2::FLG].get_dataptr<int>()[F - 1]);
     return 0;
@@ -199,7 +223,7 @@ int main(int argc, char **argv)
     int F = 1, n_ite = 50, src_delay = 0, mon_skip = 0;
     float coarse_freq = 0.f;
     float alpha = 1.0f;
-    bool frame_sync = false, matched = false;
+    bool frame_sync = false, matched = false, stm_fast = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; exit(2); } return argv[++i]; };
@@ -216,10 +240,12 @@ int main(int argc, char **argv)
         else if (a == "--coarse-freq") coarse_freq = std::stof(next());      // normalized frequency offset of the received samples (cycles per sample): the coarse synchronizer's frozen estimate
         else if (a == "--frame-sync") frame_sync = true;
         else if (a == "--matched-filter") matched = true;
+        else if (a == "--stm-type") { const std::string t = next(); if (t != "PERFECT" && t != "FAST") { std::cerr << "--stm-type: PERFECT or FAST\n"; return 2; } stm_fast = t == "FAST"; }
         else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
     try {
-        if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq);
+        if (stm_fast && !matched) { std::cerr << "--stm-type FAST needs --matched-filter (the timing synchronizer runs on the samples)\n"; return 2; }
+        if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq, stm_fast);
         auto ctx = std::make_shared<module::Context>(modcod, F, n_ite, alpha, true, 0, implem);
         ctx->pin_sockets = true;            // the sockets below live until the modules go: pin them for overlapped PCIe copies
         module::Scrambler_PL_hip pl_scrambler(ctx);

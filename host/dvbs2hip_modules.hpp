@@ -87,6 +87,9 @@ namespace mnt { enum class tsk : size_t { check_errors, check_errors2, SIZE };
                 namespace sck { enum class check_errors : size_t { U, V, status };
                                 enum class check_errors2 : size_t { U, V, FRA, BE, FE, BER, FER, status }; } }
 namespace rcv { namespace sck { enum class receive : size_t { Y_N1, V_K, CWD_LDPC, CWD_BCH, status }; } }
+// Synchronizer_timing.hxx:48-78 (tasks synchronize and extract)
+namespace stm { enum class tsk : size_t { synchronize, extract, SIZE };
+                namespace sck { enum class synchronize : size_t { X_N1, MU, Y_N1, B_N1, status }; enum class extract : size_t { Y_N1, B_N1, UFW, Y_N2, status }; } }
 // Synchronizer_freq_fine.hpp:14-19
 namespace sff { enum class tsk : size_t { synchronize, SIZE }; namespace sck { enum class synchronize : size_t { X_N1, FRQ, PHS, Y_N2, status }; } }
 // Synchronizer_frame.hpp:15-24
@@ -302,6 +305,53 @@ public:
 private:
     int N_;
     float energy_;
+};
+
+// replaces Synchronizer_timing<B,R> of type FAST = Synchronizer_Gardner_fast_osf2 (Factory/Module/Synchronizer_timing/Synchronizer_timing.cpp:91-96, the factory defaults
+// damping sqrt(0.5), normalized bandwidth 5e-5, detector gain 2: Synchronizer_timing.hpp:28-30; bound RX/main_sched.cpp:202-204).  One stream, N_in = 2 * pl_frame * 2 floats per
+// frame.  extract throws processing_aborted when the stream underflows, as Synchronizer_timing.hxx:302 does: the symbols wait in the handle for the next call.
+template <typename B = int, typename R = float>
+class Synchronizer_timing_hip : public Module_hip {
+public:
+    Synchronizer_timing_hip(std::shared_ptr<Context> c, R damping_factor = (R)0.70710678f, R normalized_bandwidth = (R)5e-5, R detector_gain = (R)2)
+    : Module_hip(std::move(c), "Synchronizer_timing_hip")
+    {
+        static_assert(sizeof(B) == 4 && sizeof(R) == 4, "B = int32, R = float");
+        DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_set_params(ctx->h, (float)damping_factor, (float)normalized_bandwidth, (float)detector_gain));
+        const size_t N_in = 4 * (size_t)ctx->sz.pl_frame_sym;
+        {
+            auto &t = create_task("synchronize");
+            auto sX = create_socket_in<R>(t, "X_N1", N_in);
+            auto sM = create_socket_out<R>(t, "MU", 1);
+            auto sY = create_socket_out<R>(t, "Y_N1", N_in);
+            auto sB = create_socket_out<B>(t, "B_N1", N_in);
+            create_codelet(t, [sX, sM, sY, sB](spu::module::Module &m, spu::runtime::Task &tk, size_t) -> int {
+                auto &me = static_cast<Synchronizer_timing_hip &>(m);
+                DVBS2HIP_CHK(me.ctx, dvbs2hip_sync_timing_synchronize(me.ctx->h, tk[sX].template get_dataptr<const R>(), tk[sY].template get_dataptr<R>(),
+                                                                      (int32_t *)tk[sB].template get_dataptr<B>(), tk[sM].template get_dataptr<R>(), me.F()));
+                return 0;
+            });
+        }
+        {
+            auto &t = create_task("extract");
+            auto sY = create_socket_in<R>(t, "Y_N1", N_in);
+            auto sB = create_socket_in<B>(t, "B_N1", N_in);
+            auto sU = create_socket_out<B>(t, "UFW", 1);
+            auto sY2 = create_socket_out<R>(t, "Y_N2", N_in / 2);
+            create_codelet(t, [sY, sB, sU, sY2](spu::module::Module &m, spu::runtime::Task &tk, size_t) -> int {
+                auto &me = static_cast<Synchronizer_timing_hip &>(m);
+                int32_t rdy = 0;
+                DVBS2HIP_CHK(me.ctx, dvbs2hip_sync_timing_extract(me.ctx->h, tk[sY].template get_dataptr<const R>(), (const int32_t *)tk[sB].template get_dataptr<const B>(),
+                                                                  tk[sY2].template get_dataptr<R>(), (int32_t *)tk[sU].template get_dataptr<B>(), &rdy, me.F()));
+                if (!rdy) throw spu::tools::processing_aborted(__FILE__, __LINE__, __func__);
+                return 0;
+            });
+        }
+    }
+    spu::runtime::Task &operator[](stm::tsk t) { return *tasks[(size_t)t]; }
+    spu::runtime::Socket &operator[](stm::sck::synchronize s) { return (*tasks[(size_t)stm::tsk::synchronize])[(size_t)s]; }
+    spu::runtime::Socket &operator[](stm::sck::extract s) { return (*tasks[(size_t)stm::tsk::extract])[(size_t)s]; }
+    void reset() { DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_reset(ctx->h)); }
 };
 
 // replaces Synchronizer_freq_coarse<R> in the transmission phase: its task `synchronize` is the frequency shift alone (Synchronizer_freq_coarse_DVBS2_aib.cpp:43-50 ->

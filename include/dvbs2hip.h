@@ -360,6 +360,41 @@ int dvbs2hip_add_noise_dev(dvbs2hip_t *h, const float *CP, const float *X_N, flo
  * Y[i] = X[offset + i*osf] for i < n_frames*n_cplx_out; samples outside the batch read as zero.      */
 int dvbs2hip_extract_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx_out, int32_t osf, int64_t offset, int32_t n_frames);
 
+/* ------------------------------------------------------------------ symbol-timing recovery (the reference's `--stm-type FAST`)
+ * replaces: Synchronizer_timing::synchronize -> Synchronizer_Gardner_fast_osf2::_synchronize and Synchronizer_timing::extract -> _extract
+ * -- src/common/Module/Synchronizer/Synchronizer_timing/Synchronizer_Gardner_fast_osf2.cpp:35-198 (Farrow interpolator Filter_Farrow_ccr_naive.hxx, Gardner detector,
+ * PI loop filter, NCO), Synchronizer_timing.hxx:48-78 (tasks and sockets), :189-201 (MU), :243-304 (extract: the carry buffer and the underflow count); built by
+ * Factory/Module/Synchronizer_timing/Synchronizer_timing.cpp:91-96, bound RX/main_sched.cpp:202-204.  Frames of pl_frame * osf complex samples; osf = 2 only (the handle's
+ * fir_osf; the NORMAL, ULTRA and osf != 2 variants are not provided: DVBS2HIP_EUNSUPPORTED).  Results are bit for bit the CPU twin's (tests/timing_twin.c), which restates the reference's order of operations.
+ * Streams: the n_frames frames of a call are S streams of n_frames / S consecutive frames each, stream s = frames [s F/S, (s+1) F/S) (F a multiple of S, else EINVAL).
+ * S = 1 (the default) is the reference's module: one stream.  Every stream keeps its own loop state and carry buffer in the handle between calls; one lane runs one stream.
+ * F/S is fixed by the first call after a reset (or set_streams): a call with another F/S returns EINVAL until dvbs2hip_sync_timing_reset.
+ *   synchronize: X_N1 float[F * 2 N] -> Y_N1 float[F * 2 N] (interpolated samples), B_N1 int32_t[F * 2 N] (1 on both reals of a strobe), MU float[F] (mu after the frame)
+ *   extract    : Y_N1, B_N1 -> Y_N2 float[F * N] (N = pl_frame * osf reals = pl_frame symbols per frame), UFW int32_t[F], RDY int32_t[S]
+ * extract fills a stream's frames with the reals its carry buffer held, then the strobed reals of Y_N1; what does not fit stays in the carry buffer (at most 4 N F/S reals,
+ * four calls' worth of output: a stream whose strobes run that far ahead of its output loses the excess and reports RDY[s] = 2 -- the reference grows its buffer instead).  A stream with too few reals (the reference throws processing_aborted) is NOT READY: RDY[s] = 0, all it had stays
+ * in the carry buffer for the next call, its frames of Y_N2 hold only the reals it had (the rest of the socket is left as it was) and the frame they reached counts an underflow.
+ * UFW[f] = the underflows counted on frame slot f since the stream's last ready call, this call's included; a ready call reports them and clears them.
+ * set_params: damping factor, normalized bandwidth, detector gain (defaults sqrt(0.5), 5e-5, 2: Synchronizer_timing.hpp:28-30); get_gains returns the loop filter's proportional
+ * and integrator gains (set_loop_filter_coeffs, .cpp:188-198).  set_streams and reset clear every stream's state, carry buffer and underflow counts.
+ * Graph capture: these tasks keep a memory, so the rule of dvbs2hip_graph_begin holds -- a replay starts from the state recorded; set_streams / reset refuse an open capture. */
+int dvbs2hip_sync_timing_set_params(dvbs2hip_t *h, float damping, float nbw, float detector_gain);
+int dvbs2hip_sync_timing_get_gains(dvbs2hip_t *h, float *proportional, float *integrator);
+int dvbs2hip_sync_timing_set_streams(dvbs2hip_t *h, int32_t S);
+int dvbs2hip_sync_timing_reset(dvbs2hip_t *h);
+int dvbs2hip_sync_timing_synchronize(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t n_frames);
+int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t n_frames);
+int dvbs2hip_sync_timing_extract(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t n_frames);
+int dvbs2hip_sync_timing_extract_dev(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t n_frames);
+/* The channel's three delay tasks, in the order CH/main.cpp:60-62 and TX_RX/main.cpp:215-218 bind them (test-signal side)
+ * replaces: Filter_buffered_delay::filter ((floor(D) - 2) / N frames), Variable_delay_cc_naive::filter ((floor(D) - 2 + N) % N samples), Filter_Farrow_ccr_naive::filter
+ * (mu = D - floor(D)) -- built DVBS2.cpp:520-544 from --chn-max-delay D >= 2 (DVBS2.cpp:128-133).  The two delay lines start at zero and compose to one of floor(D) - 2 samples;
+ * the frames of a call are consecutive in one stream and the last floor(D) + 1 samples are kept in the handle between calls.  set_delay clears that memory.
+ *   X, Y: float[n_frames * 2 N], N = pl_frame * osf complex samples.  Graph capture: as above (a task with a memory).                                   */
+int dvbs2hip_channel_set_delay(dvbs2hip_t *h, float D);
+int dvbs2hip_channel_delay(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
+int dvbs2hip_channel_delay_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
+
 /* ------------------------------------------------------------------ N4: frame synchronizer
  * replaces: Synchronizer_frame_DVBS2_fast<R> (type "FAST", the factory default,
  * src/common/Factory/Module/Synchronizer_frame/Synchronizer_frame.cpp:71-72, .hpp:26-30) --

@@ -10,7 +10,11 @@ RX/main.cpp: Source_user), an unknown frame start (--off symbols), a constant ca
 leaves behind) -> shaping filter -> AWGN at the sample rate -> matched filter -> every second sample (timing by genie) -> the tasks of the reference's RX graph in its order,
 one C-ABI call per task: frame synchronizer -> PL descrambler -> L&R -> pilot-aided phase -> remove PLH -> estimate -> demodulate + de-interleave -> LDPC -> BCH -> BB
 descrambler.  Variants: `frame` (frame synchronizer only, no rotation applied: its cost alone), `fine` (rotation applied; L&R + phase synchronizer correct it).
-Filters, synchronizers and the delay line keep their state from call to call, so the stream is continuous across the calls."""
+Filters, synchronizers and the delay line keep their state from call to call, so the stream is continuous across the calls.
+
+--chn-max-delay D puts the reference channel's three delay tasks (dvbs2hip_channel_delay) behind the shaping filter, and --stm-type FAST replaces the genie by the
+Gardner timing loop on the GPU (synchronize -> extract, RX/main_sched.cpp:202-204): a call whose extract underflows yields no frames, and the loop's learning frames
+are the first --skip frames, which are not counted."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +30,10 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     frame = frame[:, 0] + 1j * frame[:, 1]
     sigma = np.float32(P.esn0_to_sigma(P.ebn0_to_esn0(ebn0, mc.code_rate, mc.bps)))
     rot = variant == "fine"
+    delay_D = getattr(a, "chn_max_delay", None)
+    fast = getattr(a, "stm_type", "PERFECT") == "FAST"
+    if delay_D is not None:
+        rx.channel_set_delay(delay_D)
     st = dict(frames=0, counted=0, be=0, fe=0, delay=None, stable=0, moved=0)
     t0, k = time.time(), 0
     idx = (np.arange(F * n) - off) % n
@@ -36,11 +44,22 @@ def run_point(Rx, P, mc, ebn0, variant, a):
             s = s * np.exp(1j * (a.phase + 2.0 * np.pi * a.freq * t))
         x = np.empty((F * n, 2), np.float32); x[:, 0] = s.real; x[:, 1] = s.imag
         up = rx.shape_filter(x, n_frames=F, osf=2)
+        if delay_D is not None:
+            up = rx.channel_delay(up.reshape(F, -1))                                    # chn_frm_del -> chn_int_del -> chn_frac_del (TX_RX/main.cpp:215-218)
         noisy = rx.add_noise(sigma, up, seed=(a.seed << 20) + k, n_frames=F)
         if a.agc:
             noisy = rx.agc(noisy, n_frames=F, output_energy=0.5)                        # front_agc (RX/main_sched.cpp:197; DVBS2.cpp:660-664)
         mf = rx.filter(noisy, n_frames=F).reshape(-1, 2)
-        sym = np.ascontiguousarray(mf[0::2]).reshape(F, 2 * n)                         # the two filters delay the stream by 40 symbols: part of the unknown frame start
+        if fast:
+            y, b, _ = rx.sync_timing_synchronize(mf.reshape(F, -1))
+            y2, _, rdy = rx.sync_timing_extract(y, b)
+            k += 1
+            if not rdy[0]:
+                continue                                                                # underflow: the symbols wait in the carry buffer
+            sym = y2.reshape(F, 2 * n)
+        else:
+            sym = np.ascontiguousarray(mf[0::2]).reshape(F, 2 * n)                     # the two filters delay the stream by 40 symbols: part of the unknown frame start
+            k += 1
         if a.agc:
             sym = rx.agc(sym, n_frames=F, output_energy=1.0).reshape(F, 2 * n)          # mult_agc (main_sched.cpp:205; DVBS2.cpp:653-657)
         delay, flags, tri, aligned = rx.sync_frame_synchronize(sym, with_flags=True)
@@ -64,7 +83,6 @@ def run_point(Rx, P, mc, ebn0, variant, a):
             st["delay"] = int(delay[f])
             if st["frames"] > a.skip:                                                   # every frame after the acquisition counts, locked or not (a lost lock is a lost frame)
                 st["counted"] += 1; st["be"] += int(err[f]); st["fe"] += int(err[f] > 0)
-        k += 1
     rx.close()
     st.update(ebn0=ebn0, variant=variant, fer=st["fe"] / max(1, st["counted"]), ber=st["be"] / max(1, st["counted"] * mc.K_bch), seconds=time.time() - t0)
     return st
@@ -85,6 +103,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--est-perfect", action="store_true", help="the channel's sigma instead of the M2M4 estimate (the reference's 16APSK trace: --est-type PERFECT)")
     ap.add_argument("--agc", action="store_true", help="the reference's two gain stages in the loop (front_agc on the samples, mult_agc on the symbols)")
+    ap.add_argument("--chn-max-delay", type=float, default=None, help="the reference channel's delay tasks with this D (>= 2) behind the shaping filter")
+    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="PERFECT: timing by genie; FAST: the Gardner loop on the GPU")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     from dvbs2_amd.receiver import Dvbs2Hip
