@@ -1,0 +1,102 @@
+"""The receiver's waiting and learning phases (the reference's src/mains/RX/main_sched.cpp:407-635) above the C ABI: one function that drives a `Dvbs2Hip`
+handle -- or anything with the same methods -- over a sample source until the coarse frequency, the symbol timing and the frame start are acquired.
+
+  waiting     PLL coefficients (1, damping, nbw_wait); front gain stage -> step_mf (coarse rotation + matched filter + Gardner step + PLL, one fused task) -> extract ->
+              gain stage -> frame synchronizer, the synchronizer's delay fed back to step_mf's DEL by one call (the reference's Feedbacker), until the frame
+              synchronizer raises its packet flag (main_sched.cpp:472-494); then step_mf, the frame synchronizer and the timing synchronizer are reset (:500-502)
+  learning 1  the same sequence for `learn1` frames at nbw1                                                                       (:527-560)
+  learning 2  `learn2` more at nbw2
+  learning 3  the PLL frozen: front gain stage -> coarse frequency SHIFT -> matched filter -> timing synchronize -> extract -> gain stage -> frame synchronizer ->
+              PL descrambler -> L&R -> pilot-aided fine synchronizer, for `learn3` frames                                            (:562-630)
+
+The handle is left where the transmission phase starts: every task's state carries on.  Defaults are the reference's: 150 / 150 / 200 frames, 1e-4 / 1e-4 / 5e-5."""
+from __future__ import annotations
+
+import numpy as np
+
+from .iqfile import ProcessingAborted
+
+
+def acquire(rx, receive, n_frames=1, osf=2, learn1=150, learn2=150, learn3=200, nbw_wait=1e-4, nbw1=1e-4, nbw2=5e-5, damping=0.5 ** 0.5, wait_max=2000, agc=True,
+            on_frames=None):
+    """rx: the handle; receive(): the next n_frames frames of pl_frame * osf complex samples (float32, interleaved), raising ProcessingAborted at the end of the source.
+    on_frames(phase, n): called after every call of a phase with the frames it took (progress).
+    -> dict(acquired: the packet flag came within wait_max frames, and the source lasted through the learning phases; flag: the packet flag came;
+            frames: {"waiting", "learning1", "learning2", "learning3"} frames spent; freq: estimated_freq per stream; nu: the floored frequency in use per stream)"""
+    F = n_frames
+    spent = dict(waiting=0, learning1=0, learning2=0, learning3=0)
+    res = dict(acquired=False, flag=False, frames=spent, freq=None, nu=None)
+    fed_back = np.zeros(F, np.int32)                                  # Feedbacker: what memorize took at the last call, produce gives at this one (zeros at first)
+
+    def front(x):
+        x = np.asarray(x, np.float32).reshape(F, -1)
+        return rx.agc(x, n_frames=F, output_energy=1.0 / osf).reshape(F, -1) if agc else x
+
+    def symbols_to_frame_sync(y2):
+        sym = rx.agc(y2, n_frames=F, output_energy=1.0).reshape(F, -1) if agc else y2
+        return rx.sync_frame_synchronize(sym, with_flags=True)
+
+    def wl12_call():
+        """one run of the waiting / learning 1-2 sequence -> the packet flag after it (None: the sequence was cut short by an underflow)"""
+        nonlocal fed_back
+        x = front(receive())
+        _, _, _, y, b = rx.sync_step_mf_synchronize(fed_back, x)
+        y2, _, rdy = rx.sync_timing_extract(y, b)
+        if not rdy[0]:
+            return None                                               # (the reference's sequence aborts here; the Feedbacker keeps what it had)
+        delay, flags, _, _ = symbols_to_frame_sync(y2)
+        fed_back = np.array(delay, np.int32)
+        return bool(flags[-1])
+
+    try:
+        # ---------------------------------------------------------- waiting
+        rx.sync_coarse_set_pll(1, damping, nbw_wait)
+        while not res["flag"]:
+            if spent["waiting"] >= wait_max:
+                return _finish(rx, res)
+            flag = wl12_call()
+            spent["waiting"] += F
+            if on_frames:
+                on_frames("waiting", F)
+            res["flag"] = bool(flag)
+        rx.sync_step_mf_reset()
+        rx.sync_frame_reset()
+        rx.sync_timing_reset()
+        # ---------------------------------------------------------- learning 1 and 2
+        rx.sync_coarse_set_pll(1, damping, nbw1)
+        m, limit, second = 0, learn1, False
+        while m < limit:
+            wl12_call()
+            m += F
+            spent["learning2" if second else "learning1"] += F
+            if on_frames:
+                on_frames("learning2" if second else "learning1", F)
+            if not second and m >= learn1:
+                second, limit = True, m + learn2
+                rx.sync_coarse_set_pll(1, damping, nbw2)
+        # ---------------------------------------------------------- learning 3
+        m = 0
+        while m < learn3:
+            x = front(receive())
+            _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)
+            y, b, _ = rx.sync_timing_synchronize(rx.filter(x, n_frames=F).reshape(F, -1))
+            y2, _, rdy = rx.sync_timing_extract(y, b)
+            m += F
+            spent["learning3"] += F
+            if on_frames:
+                on_frames("learning3", F)
+            if not rdy[0]:
+                continue
+            _, _, _, aligned = symbols_to_frame_sync(y2)
+            _, _, desc = rx.sync_lr_synchronize(rx.pl_descramble(aligned))
+            rx.sync_freq_phase_synchronize(desc)
+        res["acquired"] = True
+    except ProcessingAborted:
+        pass
+    return _finish(rx, res)
+
+
+def _finish(rx, res):
+    est, nu = rx.sync_coarse_get_freq()
+    res["freq"], res["nu"] = [float(v) for v in est], [float(v) for v in nu]
+    return res

@@ -4,7 +4,7 @@ Mirrors /root/reference src/mains/CH/main.cpp:25-104 for `--chn-type AWGN` (its 
 receive -> add_noise -> send that runs until the input file ends, sigma from `-m` (Eb/N0 in dB) through
 ebn0_to_esn0 / esn0_to_sigma with the code rate K_bch / N_ldpc (main.cpp:35-42), frames of
 p_rad.N = pl_frame * osf complex samples (DVBS2.cpp:175).  --chn-max-delay D adds the SYNCHRO channel's three delay
-tasks (main.cpp:60-62) in front of the noise; its fading and frequency shift (main.cpp:59,63) are not provided.
+tasks (main.cpp:60-62) and --chn-max-freq-shift its frequency shift (main.cpp:63-64) in front of the noise; its fading (main.cpp:59) is not provided.
 
   python -m dvbs2_amd.ch --mod-cod QPSK-S_8/9 -m 4.5 --rad-rx-file-path after_TX.bin \
          --rad-tx-file-path before_RX_4.5dB.bin --rad-rx-no-loop
@@ -33,6 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chn-type", default="AWGN", choices=["AWGN"])
     ap.add_argument("--chn-max-delay", type=float, default=None, dest="max_delay",
                     help="apply the reference channel's three delay tasks (frame, integer and Farrow fractional delay of DVBS2.cpp:520-544) before the noise; D >= 2")
+    ap.add_argument("--chn-max-freq-shift", type=float, default=None, dest="max_freq_shift",
+                    help="apply the reference channel's frequency shift (Multiplier_sine_ccc_naive, DVBS2.cpp:624-626) behind the delay tasks: cycles per sample")
     ap.add_argument("--sim-seed", type=int, default=0, dest="seed")
     ap.add_argument("--max-frames", type=int, default=0, help="stop after this many frames (needed when the input loops)")
     ap.add_argument("--device", type=int, default=0)
@@ -55,6 +57,10 @@ def run(args, out=sys.stdout) -> int:
         if args.osf != 2:
             raise ValueError("--chn-max-delay needs --shp-osf 2: the delay tasks run on frames of pl_frame * 2 complex samples")
         rx.channel_set_delay(args.max_delay)
+    if getattr(args, "max_freq_shift", None) is not None:
+        if args.osf != 2:
+            raise ValueError("--chn-max-freq-shift needs --shp-osf 2: the task runs on frames of pl_frame * 2 complex samples")
+        rx.channel_set_freq_shift(args.max_freq_shift)
     print("Channel AWGN", file=out)
     frames, call = 0, 0
     try:
@@ -66,6 +72,8 @@ def run(args, out=sys.stdout) -> int:
             x = x.astype(np.float32, copy=False)
             if args.max_delay is not None:
                 x = rx.channel_delay(x.reshape(args.n_frames, -1))             # chn_frm_del -> chn_int_del -> chn_frac_del (CH/main.cpp:60-62)
+            if getattr(args, "max_freq_shift", None) is not None:
+                x = rx.channel_freq_shift(x.reshape(args.n_frames, -1))        # freq_shift (CH/main.cpp:63-64)
             y = rx.add_noise(np.float32(sigma), x, seed=(args.seed << 32) + call, n_frames=args.n_frames)
             snd.send(y)
             frames += args.n_frames

@@ -40,6 +40,7 @@ struct dvbs2hip_handle {
     int n_ite = 50, early_stop = 1, implem = 0;
     float alpha = 1.f, code_rate = 0.f;
     int fir_T = 0, fir_osf = 1;
+    bool fir_sym = false;               // taps[i] == taps[T - 1 - i] for every i (what k_stepmf.hip's folded matched filter needs)
     // device state
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -119,8 +120,25 @@ struct dvbs2hip_handle {
     unsigned long long *h_red = nullptr;      // pinned: the reduced counters' way back (a copy into pageable memory would wait for the stream itself -- and for a dead peer for ever)
     int red_rank = 0, red_world = 1;
     // timing
-    float nco_nu = 0.f, nco_omega = 0.f;                   // Synchronizer_freq_coarse in the transmission phase: Multiplier_sine_ccc_naive's nu / omega and its sample counter n
-    uint32_t nco_n = 0;
+    // Synchronizer_freq_coarse_DVBS2_aib, one state per stream (SfcState: the PLL, Multiplier_sine_ccc_naive's nu in millionths and its sample counter n).  The loop
+    // (k_stepmf.hip) runs on the device copy, the block-wise shift of the transmission phase (nco_kernel) takes nu and n as launch arguments from the host copy: `where`
+    // says which of the two is current, and the side that is behind is brought up when it is next needed (one small copy at the switch between the phases)
+    struct {
+        enum { HOST = 0, DEV = 1, BOTH = 2 };
+        int where = HOST;
+        std::vector<SfcState> hs;                               // S entries
+        std::vector<float> frq;                                 // what the shift task reports in FRQ: -nu after set_freq, estimated_freq after the loop
+        int pll_sps = 1;                                        // Synchronizer_freq_coarse_DVBS2_aib.cpp:23 and Factory/Module/Synchronizer_freq_coarse/Synchronizer_freq_coarse.hpp:26-27
+        float damping = 0.70710678f, nbw = 1e-4f;
+        int n_alloc = 0;
+        SfcState *cf[2] = {nullptr, nullptr};
+        int cf_cur = 0;
+        float *hist[2] = {nullptr, nullptr};                    // S > 1: the matched filter's memory per stream (S = 1 shares the block-wise filter's, d_hist)
+        int hist_cur = 0;
+        bool hist_stale = false;                                // the streams started over: their matched-filter memories have to be cleared before the next loop call
+        float *pil = nullptr;                                   // scrambled_pilots, n_p complex entries
+        int n_p = 0;
+    } sfc;
     // symbol-timing recovery (Synchronizer_Gardner_fast_osf2): per-stream state and carry buffers in ping-pong pairs, like the filters' memories
     struct {
         float damping = 0.70710678f, nbw = 5e-5f, dg = 2.f;     // Factory/Module/Synchronizer_timing/Synchronizer_timing.hpp:28-30
@@ -143,6 +161,8 @@ struct dvbs2hip_handle {
         long long H = 3;
         float *hist[2] = {nullptr, nullptr};
         int cur = 0;
+        float fs_omega = 0.f;                                   // the frequency shift: Multiplier_sine_ccc_naive's omega and sample counter
+        uint32_t fs_n = 0;
     } chn;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[DVBS2HIP_K_COUNT];
@@ -167,7 +187,7 @@ int fail(dvbs2hip_t *h, int code, const std::string &msg)
 
 enum BufId { B_IN = 0, B_OUT, B_AUX0, B_AUX1, B_AUX2, B_AUX3, B_LLR, B_PACKED, B_EST, B_CWD0, B_CWD1, B_INFO, B_SIG, B_TXBCH, B_TXLDPC,
              B_SFM_CORR, B_SFM_MET, B_SFM_SOF, B_SFM_PLSC, B_SFM_DLY, B_SFM_DTAB, B_SFF_TMP, B_SFF_OUT, B_FLT2, B_MON_BE, B_MON_OUT, B_BCHFLAG, B_ORDER, B_LR_TMP0, B_LR_TMP1, B_LR_TMP2, B_LR_TMP3, B_SFM_SCR, B_SFM_NEED,
-             B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY };
+             B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY, B_SMF_DEL, B_SMF_FRQ };
 
 int ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
 {
@@ -596,6 +616,8 @@ int dvbs2hip_create(const dvbs2hip_cfg *cfg, dvbs2hip_t **out)
     if (h->fir_T > 0) {
         std::vector<float> rev(h->fir_T);
         for (int i = 0; i < h->fir_T; i++) rev[i] = cfg->fir_taps[h->fir_T - 1 - i];
+        h->fir_sym = true;
+        for (int i = 0; i < h->fir_T; i++) if (rev[i] != cfg->fir_taps[i]) h->fir_sym = false;
         if (upload(h, &h->d_taps_rev, rev.data(), rev.size())) CREATE_FAIL(DVBS2HIP_EHIP, h->err);
         if (h->fir_T <= 81) {
             const std::vector<uint16_t> af = fir_mfma_afrag(rev.data(), h->fir_T);
@@ -640,7 +662,8 @@ void dvbs2hip_destroy(dvbs2hip_t *h)
     void *sfm_ptrs[] = {h->sfm.xh[0], h->sfm.xh[1], h->sfm.sofh[0], h->sfm.sofh[1], h->sfm.cv, h->sfm.buff2[0], h->sfm.buff2[1], h->sfm.st[0], h->sfm.st[1],
                         h->sfm.yprev[0], h->sfm.yprev[1], h->sfm.keys, h->sfm.metric, h->sfm.frag, h->d_lr_R, h->d_nat_work, h->ldpc.d_nat_tab, h->ldpc.d_nat_haz, h->d_fir_afrag, h->d_upfir_afrag, h->d_bch_shift, h->d_hist_zero, h->d_hist_junk, h->d_red, h->bch.d_prbs_rw};
     for (void *p : sfm_ptrs) if (p) (void)hipFree(p);
-    void *stm_ptrs[] = {h->stm.st[0], h->stm.st[1], h->stm.carry[0], h->stm.carry[1], h->stm.ccnt[0], h->stm.ccnt[1], h->stm.uf, h->chn.hist[0], h->chn.hist[1]};
+    void *stm_ptrs[] = {h->stm.st[0], h->stm.st[1], h->stm.carry[0], h->stm.carry[1], h->stm.ccnt[0], h->stm.ccnt[1], h->stm.uf, h->chn.hist[0], h->chn.hist[1],
+                        h->sfc.cf[0], h->sfc.cf[1], h->sfc.hist[0], h->sfc.hist[1], h->sfc.pil};
     for (void *p : stm_ptrs) if (p) (void)hipFree(p);
     if (h->lr_err_host) (void)hipHostFree(h->lr_err_host);
     if (h->h_red) (void)hipHostFree(h->h_red);
@@ -1769,21 +1792,93 @@ int dvbs2hip_agc_imultiply(dvbs2hip_t *h, const float *X, float *Z, int32_t n_cp
     return host_wrap<true>(h, X, n, Z, n, F, [&](const float *a, float *b, int nf) { return dvbs2hip_agc_imultiply_dev(h, a, b, n_cplx, output_energy, nf); });
 }
 
-// ------------------------------------------------------------------ Synchronizer_freq_coarse::synchronize in the transmission phase (the frequency shift; the loop that finds it is sample-serial)
+// ------------------------------------------------------------------ Synchronizer_freq_coarse: the frequency shift of the transmission phase (block-wise) and the loop that finds it (k_stepmf.hip)
+static void sfc_state_reset(dvbs2hip_t *h, SfcState &c)                // Synchronizer_freq_coarse::reset + Synchronizer_freq_coarse_DVBS2_aib::_reset, .cpp:115-129; last_delay is Synchronizer_step_mf_cc's and stays
+{
+    const int32_t last_delay = c.last_delay;
+    c = SfcState{};
+    c.curr_idx = h->pl_frame - 1;
+    c.last_delay = last_delay;
+}
+
+// the host copy of the streams' states, current
+static int sfc_host(dvbs2hip_t *h)
+{
+    auto &C = h->sfc;
+    const size_t S = (size_t)h->stm.S;
+    if (C.hs.size() != S) {                                            // a new stream count: every stream starts over
+        C.hs.assign(S, SfcState{});
+        for (auto &c : C.hs) sfc_state_reset(h, c);
+        C.frq.assign(S, 0.f);
+        C.where = C.HOST;
+        C.hist_stale = true;
+    }
+    if (C.where == C.DEV) {
+        if (h->capturing) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse synchronizer's state has to come back from the device: not inside a capture");
+        HIPCHK(h, hipMemcpyAsync(C.hs.data(), C.cf[C.cf_cur], sizeof(SfcState) * S, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (size_t s = 0; s < S; s++) C.frq[s] = C.hs[s].est;         // after the loop FRQ is estimated_freq (Synchronizer_freq_coarse.hxx:121-124)
+        C.where = C.BOTH;
+    }
+    return 0;
+}
+
+// Synchronizer_freq_coarse_DVBS2_aib::set_PLL_coeffs, .cpp:94-113, R = float (the 0.25 there is a double constant: the quotient is rounded to float once)
+static void sfc_gains(int pll_sps, float damping, float nbw, float &pg, float &ig)
+{
+    const float det_gain = 2.0f;
+    const float bw = nbw * (float)pll_sps;
+    const float K0 = (float)pll_sps;
+    const float theta = (float)((double)bw / (((double)damping + 0.25 / (double)damping) * (double)(float)pll_sps));
+    const float d = 1.0f + 2.0f * damping * theta + theta * theta;
+    pg = (4.0f * damping * theta / d) / (det_gain * K0);
+    ig = (4.0f / (float)pll_sps * theta * theta / d) / (det_gain * K0);
+}
+
+int dvbs2hip_sync_coarse_set_pll(dvbs2hip_t *h, int32_t pll_sps, float damping, float nbw)
+{
+    if (!h) return DVBS2HIP_EINVAL;
+    if (pll_sps < 1 || !(damping > 0.f) || !(nbw > 0.f) || !std::isfinite(damping) || !std::isfinite(nbw))
+        return fail(h, DVBS2HIP_EINVAL, "'pll_sps', 'damping' and 'nbw' have to be positive");
+    h->sfc.pll_sps = pll_sps; h->sfc.damping = damping; h->sfc.nbw = nbw;
+    return 0;
+}
+
+int dvbs2hip_sync_coarse_get_gains(dvbs2hip_t *h, float *proportional, float *integrator)
+{
+    if (!h || !proportional || !integrator) return DVBS2HIP_EINVAL;
+    sfc_gains(h->sfc.pll_sps, h->sfc.damping, h->sfc.nbw, *proportional, *integrator);
+    return 0;
+}
+
+int dvbs2hip_sync_coarse_get_freq(dvbs2hip_t *h, float *estimated_freq, float *nu)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (!estimated_freq || !nu) return fail(h, DVBS2HIP_EINVAL, "null pointer");
+    int r = sfc_host(h); if (r) return r;
+    for (size_t s = 0; s < h->sfc.hs.size(); s++) { estimated_freq[s] = h->sfc.hs[s].est; nu[s] = (float)h->sfc.hs[s].nu_k / 1e6f; }
+    return 0;
+}
+
 int dvbs2hip_sync_coarse_set_freq(dvbs2hip_t *h, float estimated_freq)
 {
     if (!h) return DVBS2HIP_EINVAL;
     if (!(estimated_freq == estimated_freq) || fabsf(estimated_freq) > 0.5f) return fail(h, DVBS2HIP_EINVAL, "'estimated_freq' has to be a normalized frequency in [-0.5, 0.5]");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, DVBS2HIP_EHIP, "hipSetDevice failed");
+    int r = sfc_host(h); if (r) return r;
     const float nu = -estimated_freq;                                  // Synchronizer_freq_coarse_DVBS2_aib.cpp:82: mult.set_nu(-estimated_freq)
-    const float new_nu = floorf(nu * 1e6f) / 1e6f;                     // Multiplier_sine_ccc_naive::set_nu, .cpp:44-51
-    h->nco_nu = new_nu;
-    h->nco_omega = (float)(2 * 3.1415926535897932384626433832795 * new_nu);
+    const float fk = floorf(nu * 1e6f);                                // Multiplier_sine_ccc_naive::set_nu, .cpp:44-51: new_nu = floor(nu 1e6) / 1e6
+    for (size_t s = 0; s < h->sfc.hs.size(); s++) { h->sfc.hs[s].nu_k = (int32_t)fk; h->sfc.frq[s] = -(fk / 1e6f); }
+    h->sfc.where = h->sfc.HOST;
     return 0;
 }
-int dvbs2hip_sync_coarse_reset(dvbs2hip_t *h)                          // Synchronizer_freq_coarse_DVBS2_aib::_reset, .cpp:123-135
+int dvbs2hip_sync_coarse_reset(dvbs2hip_t *h)                          // Synchronizer_freq_coarse_DVBS2_aib::_reset, .cpp:115-129
 {
     if (!h) return DVBS2HIP_EINVAL;
-    h->nco_n = 0; h->nco_nu = 0.f; h->nco_omega = 0.f;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, DVBS2HIP_EHIP, "hipSetDevice failed");
+    int r = sfc_host(h); if (r) return r;
+    for (size_t s = 0; s < h->sfc.hs.size(); s++) { sfc_state_reset(h, h->sfc.hs[s]); h->sfc.frq[s] = 0.f; }
+    h->sfc.where = h->sfc.HOST;
     return 0;
 }
 int dvbs2hip_sync_coarse_synchronize_dev(dvbs2hip_t *h, const float *X, float *FRQ, float *PHS, float *Y, int32_t n_cplx, int32_t F)
@@ -1792,20 +1887,190 @@ int dvbs2hip_sync_coarse_synchronize_dev(dvbs2hip_t *h, const float *X, float *F
     if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     if (n_cplx < 1) return fail(h, DVBS2HIP_EINVAL, "'n_cplx' has to be greater than 0");
     if (h->capturing) return fail(h, DVBS2HIP_EUNSUPPORTED, "the stream position is a launch argument: this task cannot be recorded into a graph");
+    if ((r = sfc_host(h))) return r;
+    const int S = (int)h->sfc.hs.size();
+    if (F % S) return fail(h, DVBS2HIP_EINVAL, "'n_frames' has to be a multiple of the stream count ('n_frames' = " + std::to_string(F) + ", streams = " + std::to_string(S) + ").");
     Timer tm(h, DVBS2HIP_K_MISC);
-    const long long total = (long long)n_cplx * F;
-    HIPCHK(h, nco_launch(X, Y, h->nco_omega, h->nco_n, total, FRQ, PHS, -h->nco_nu, F, h->stream));
-    h->nco_n = (uint32_t)(((unsigned long long)h->nco_n + (unsigned long long)total) % 1000000ull);
+    const int Fs = F / S;
+    const long long total = (long long)n_cplx * Fs;
+    for (int s = 0; s < S; s++) {                                      // stream s = frames [s F/S, (s+1) F/S), each with its own frequency and sample counter
+        SfcState &c = h->sfc.hs[s];
+        const float new_nu = (float)c.nu_k / 1e6f;
+        const float omega = (float)(2 * 3.1415926535897932384626433832795 * new_nu);
+        HIPCHK(h, nco_launch(X + (size_t)2 * total * s, Y + (size_t)2 * total * s, omega, (uint32_t)c.n, total, FRQ ? FRQ + (size_t)s * Fs : nullptr, PHS ? PHS + (size_t)s * Fs : nullptr,
+                             h->sfc.frq[s], Fs, h->stream));
+        c.n = (int32_t)(((unsigned long long)c.n + (unsigned long long)total) % 1000000ull);
+    }
+    h->sfc.where = h->sfc.HOST;
     return 0;
 }
 int dvbs2hip_sync_coarse_synchronize(dvbs2hip_t *h, const float *X, float *FRQ, float *PHS, float *Y, int32_t n_cplx, int32_t F)
 {
     const size_t n = (size_t)2 * (n_cplx > 0 ? n_cplx : 0);
+    if (h && h->stm.S > 1) {                                           // several streams: the whole call at once (a chunk of a pinned socket would cut across the streams)
+        int r = check_frames(h, F); if (r) return r;
+        if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+        void *dx, *dy;
+        if ((r = ensure(h, B_STM_X, n * F * sizeof(float), &dx)) || (r = ensure(h, B_STM_Y, n * F * sizeof(float), &dy))) return r;
+        HIPCHK(h, hipMemcpyAsync(dx, X, n * F * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if ((r = dvbs2hip_sync_coarse_synchronize_dev(h, (const float *)dx, nullptr, nullptr, (float *)dy, n_cplx, F))) return r;
+        HIPCHK(h, hipMemcpyAsync(Y, dy, n * F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int f = 0; f < F; f++) { if (FRQ) FRQ[f] = h->sfc.frq[(size_t)f / (F / h->stm.S)]; if (PHS) PHS[f] = 0.f; }
+        return 0;
+    }
     // (one stream in order: the chunks of pinned sockets advance the sample counter as they come)
     int r = host_wrap<true>(h, X, n, Y, n, F, [&](const float *a, float *b, int nf) { return dvbs2hip_sync_coarse_synchronize_dev(h, a, nullptr, nullptr, b, n_cplx, nf); });
     if (r) return r;
-    for (int f = 0; f < F; f++) { if (FRQ) FRQ[f] = -h->nco_nu; if (PHS) PHS[f] = 0.f; }
+    for (int f = 0; f < F; f++) { if (FRQ) FRQ[f] = h->sfc.frq[0]; if (PHS) PHS[f] = 0.f; }
     return 0;
+}
+
+// the streams' device state for the loop: allocated for S streams, current
+static int sfc_dev(dvbs2hip_t *h)
+{
+    auto &C = h->sfc;
+    const int S = h->stm.S;
+    if ((int)C.hs.size() != S || C.n_alloc < S || !C.pil || C.where == C.HOST || C.hist_stale) {
+        if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first step_mf call allocates and uploads the streams' state");
+        int r = sfc_host(h); if (r) return r;
+    }
+    if (C.n_alloc < S) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < 2; i++) {
+            if (C.cf[i]) { HIPCHK(h, hipFree(C.cf[i])); C.cf[i] = nullptr; }
+            if (C.hist[i]) { HIPCHK(h, hipFree(C.hist[i])); C.hist[i] = nullptr; }
+        }
+        C.n_alloc = 0;
+        for (int i = 0; i < 2; i++)
+            if (hipMalloc((void **)&C.cf[i], sizeof(SfcState) * (size_t)S) != hipSuccess || hipMalloc((void **)&C.hist[i], sizeof(float) * 2 * 80 * (size_t)S) != hipSuccess)
+                return fail(h, DVBS2HIP_ENOMEM, "hipMalloc of the coarse synchronizer's state failed");
+        HIPCHK(h, hipMemsetAsync(C.hist[0], 0, sizeof(float) * 2 * 80 * (size_t)S, h->stream));
+        C.hist_cur = 0;
+        C.n_alloc = S;
+        C.where = C.HOST;
+    }
+    if (C.hist_stale) {                                                // (the buffers just allocated are clear already; older ones hold other streams' samples)
+        HIPCHK(h, hipMemsetAsync(C.hist[C.hist_cur], 0, sizeof(float) * 2 * 80 * (size_t)C.n_alloc, h->stream));
+        C.hist_stale = false;
+    }
+    if (!C.pil) {
+        // scrambled_pilots, .cpp:28-31: 0 below 90, then exp(j pi/2 (R[i - 90] + 0.5)) with (R)M_PI_2 a float, the sum and std::cos / std::sin in double, rounded to float.
+        // 2 pl_frame entries: set_curr_idx takes values below N_out / 2 = 2 pl_frame (Synchronizer_step_mf_cc.cpp:189); entries the reference's table does not have are 0
+        std::vector<uint8_t> seq;
+        pl_sequence(seq);
+        const int n_p = 2 * h->pl_frame;
+        std::vector<float> P(2 * (size_t)n_p, 0.f);
+        const float pi_2 = 1.57079632679489661923132169163975144f;
+        for (int i = 90; i < n_p && i - 90 < (int)seq.size(); i++) {
+            const double a = (double)pi_2 * ((double)(float)seq[i - 90] + 0.5);
+            P[2 * i] = (float)cos(a); P[2 * i + 1] = (float)sin(a);
+        }
+        if (upload(h, &C.pil, P.data(), P.size())) return DVBS2HIP_EHIP;
+        C.n_p = n_p;
+    }
+    if (C.where == C.HOST) {
+        HIPCHK(h, hipMemcpyAsync(C.cf[C.cf_cur], C.hs.data(), sizeof(SfcState) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));                   // (pageable source: the copy has left the host buffer before it can change)
+        C.where = C.BOTH;
+    }
+    return 0;
+}
+
+static int smf_check(dvbs2hip_t *h, int F)
+{
+    int r = stm_check(h, F); if (r) return r;
+    if (h->fir_T != 81) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse-frequency loop carries the 81-tap matched filter: the handle's filter has another length");
+    if (!h->fir_sym) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse-frequency loop folds the matched filter over its symmetry (taps[i] == taps[80 - i]): the handle's taps are not symmetric");
+    return 0;
+}
+
+int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t F)
+{
+    int r = smf_check(h, F); if (r) return r;
+    if (!DEL || !X_N1 || !MU || !FRQ || !PHS || !Y_N1 || !B_N1) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    auto &T = h->stm;
+    auto &C = h->sfc;
+    if (T.n_alloc < T.S) {
+        if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first synchronize allocates the streams' state");
+        if ((r = stm_alloc(h, T.S))) return r;
+    }
+    if ((r = sfc_dev(h))) return r;
+    T.Fs = F / T.S;
+    if (T.kp == 0.f) stm_gains(T.damping, T.nbw, T.dg, T.kp, T.ki);
+    float pg, ig;
+    sfc_gains(C.pll_sps, C.damping, C.nbw, pg, ig);
+    // one stream: the matched filter's memory is the block-wise filter's own (the last 80 input samples, oldest first), so dvbs2hip_filter* carry on from the loop and back
+    const bool shared = T.S == 1;
+    const float *hin = shared ? h->d_hist[h->hist_cur] : C.hist[C.hist_cur];
+    float *hout = shared ? h->d_hist[h->hist_cur ^ 1] : C.hist[C.hist_cur ^ 1];
+    Timer tm(h, DVBS2HIP_K_MISC);
+    HIPCHK(h, stepmf_launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt[T.c_cur], T.st[T.st_cur], T.st[T.st_cur ^ 1], C.cf[C.cf_cur], C.cf[C.cf_cur ^ 1], hin, hout, h->d_taps_rev,
+                            C.pil, C.n_p, T.S, F / T.S, stm_frame_cplx(h), h->pl_frame, T.kp, T.ki, pg, ig, (float)h->fir_osf, h->stream));
+    T.st_cur ^= 1;
+    C.cf_cur ^= 1;
+    if (shared) h->hist_cur ^= 1; else C.hist_cur ^= 1;
+    C.where = C.DEV;
+    return 0;
+}
+
+int dvbs2hip_sync_step_mf_synchronize(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t F)
+{
+    int r = smf_check(h, F); if (r) return r;
+    if (!DEL || !X_N1 || !MU || !FRQ || !PHS || !Y_N1 || !B_N1) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    const size_t n = (size_t)F * 2 * stm_frame_cplx(h);
+    void *dx, *dy, *db, *dmu, *dd, *df;
+    if ((r = ensure(h, B_STM_X, n * sizeof(float), &dx)) || (r = ensure(h, B_STM_Y, n * sizeof(float), &dy)) || (r = ensure(h, B_STM_B, n * sizeof(int32_t), &db)) ||
+        (r = ensure(h, B_STM_MU, (size_t)F * sizeof(float), &dmu)) || (r = ensure(h, B_SMF_DEL, (size_t)F * sizeof(int32_t), &dd)) || (r = ensure(h, B_SMF_FRQ, (size_t)2 * F * sizeof(float), &df)))
+        return r;
+    HIPCHK(h, hipMemcpyAsync(dx, X_N1, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dd, DEL, (size_t)F * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    float *dfrq = (float *)df, *dphs = dfrq + F;
+    if ((r = dvbs2hip_sync_step_mf_synchronize_dev(h, (const int32_t *)dd, (const float *)dx, (float *)dmu, dfrq, dphs, (float *)dy, (int32_t *)db, F))) return r;
+    HIPCHK(h, hipMemcpyAsync(Y_N1, dy, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(B_N1, db, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(MU, dmu, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(FRQ, dfrq, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(PHS, dphs, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h)                         // Synchronizer_step_mf_cc::reset, .cpp:210-217: coarse, matched filter, timing
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    int r = dvbs2hip_sync_coarse_reset(h); if (r) return r;
+    if (h->stm.S == 1) { if (h->fir_T > 1 && h->d_hist[h->hist_cur]) HIPCHK(h, hipMemsetAsync(h->d_hist[h->hist_cur], 0, sizeof(float) * 2 * (size_t)(h->fir_T - 1), h->stream)); }
+    else if (h->sfc.hist[h->sfc.hist_cur]) HIPCHK(h, hipMemsetAsync(h->sfc.hist[h->sfc.hist_cur], 0, sizeof(float) * 2 * 80 * (size_t)h->sfc.n_alloc, h->stream));
+    return stm_alloc(h, h->stm.S);
+}
+
+// ------------------------------------------------------------------ the channel's frequency shift: Multiplier_sine_ccc_naive built by DVBS2.cpp:624-626 from --chn-max-freq-shift, bound CH/main.cpp:63-64
+int dvbs2hip_channel_set_freq_shift(dvbs2hip_t *h, float freq_shift)
+{
+    if (!h) return DVBS2HIP_EINVAL;
+    if (!(freq_shift == freq_shift) || fabsf(freq_shift) > 0.5f) return fail(h, DVBS2HIP_EINVAL, "'freq_shift' has to be a normalized frequency in [-0.5, 0.5]");
+    const float new_nu = floorf(freq_shift / 1.0f * 1e6f) / 1e6f;       // the constructor, Multiplier_sine_ccc_naive.cpp:13-22, Fs = 1
+    h->chn.fs_omega = (float)(2 * 3.1415926535897932384626433832795 * new_nu);
+    h->chn.fs_n = 0;
+    return 0;
+}
+int dvbs2hip_channel_freq_shift_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if (h->capturing) return fail(h, DVBS2HIP_EUNSUPPORTED, "the stream position is a launch argument: this task cannot be recorded into a graph");
+    Timer tm(h, DVBS2HIP_K_MISC);
+    const long long total = (long long)F * stm_frame_cplx(h);
+    HIPCHK(h, nco_launch(X, Y, h->chn.fs_omega, h->chn.fs_n, total, nullptr, nullptr, 0.f, 0, h->stream));
+    h->chn.fs_n = (uint32_t)(((unsigned long long)h->chn.fs_n + (unsigned long long)total) % 1000000ull);
+    return 0;
+}
+int dvbs2hip_channel_freq_shift(dvbs2hip_t *h, const float *X, float *Y, int32_t F)
+{
+    const size_t n = h ? (size_t)2 * stm_frame_cplx(h) : 0;
+    return host_wrap<true>(h, X, n, Y, n, F, [&](const float *a, float *b, int nf) { return dvbs2hip_channel_freq_shift_dev(h, a, b, nf); });
 }
 
 // ------------------------------------------------------------------ a7

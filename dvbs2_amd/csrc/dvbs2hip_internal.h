@@ -330,4 +330,18 @@ hipError_t stm_extract_launch(const float *Y1, const int32_t *B1, float *Y2, int
                               int32_t *uf, int S, int Fs, int N, long long cap, hipStream_t s);
 hipError_t chn_delay_launch(const float *X, float *Y, const float *h_in, float *h_out, long long H, long long T, float b0, float b1, float b2, hipStream_t s);
 
+// ---------------------------------------------------------------- the coarse-frequency loop (k_stepmf.hip)
+// one stream's state of Synchronizer_freq_coarse_DVBS2_aib and its Multiplier_sine_ccc_naive between calls, and Synchronizer_step_mf_cc::last_delay: the detector's two
+// previous pilot symbols, the PI filter, the integrator, estimated_freq, nu in millionths of a cycle per sample (set_nu floors it to six decimals), the sample counter
+// n = 0 .. 999999, the symbol index in the frame.  _reset: all zero but curr_idx = pl_frame - 1; last_delay survives it (Synchronizer_step_mf_cc::reset does not touch it)
+struct SfcState {
+    float prev[2], pprev[2];
+    float lfs, ifs, dds;
+    float est;
+    int32_t nu_k, n, curr_idx, last_delay;
+};
+hipError_t stepmf_launch(const float *X, float *Y, int32_t *B, float *MU, float *FRQ, float *PHS, const int32_t *DEL, const int32_t *ccnt, const StmState *st_in, StmState *st_out,
+                         const SfcState *cf_in, SfcState *cf_out, const float *hist_in, float *hist_out, const float *taps, const float *P, int n_p, int S, int Fs, int N, int pl_frame,
+                         float kp, float ki, float pg, float ig, float sps, hipStream_t s);
+
 }  // namespace dvbs2

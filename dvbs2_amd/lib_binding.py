@@ -121,6 +121,15 @@ ABI = {
     "dvbs2hip_channel_set_delay": (C.c_int, [_vp, _f]),
     "dvbs2hip_channel_delay": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_channel_delay_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_channel_set_freq_shift": (C.c_int, [_vp, _f]),
+    "dvbs2hip_channel_freq_shift": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_channel_freq_shift_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_coarse_set_pll": (C.c_int, [_vp, _i, _f, _f]),
+    "dvbs2hip_sync_coarse_get_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "dvbs2hip_sync_coarse_get_freq": (C.c_int, [_vp, _vp, _vp]),
+    "dvbs2hip_sync_step_mf_synchronize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_step_mf_synchronize_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_sync_step_mf_reset": (C.c_int, [_vp]),
     "dvbs2hip_pl_descramble": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_pl_descramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_remove_plh": (C.c_int, [_vp, _vp, _vp, _i]),

@@ -280,6 +280,53 @@ class Dvbs2Hip:
     def channel_delay_dev(self, X, Y, n_frames):
         self._chk(self.L.dvbs2hip_channel_delay_dev(self.h, _ptr(X), _ptr(Y), n_frames))
 
+    def channel_set_freq_shift(self, freq_shift):
+        self._chk(self.L.dvbs2hip_channel_set_freq_shift(self.h, float(freq_shift)))
+
+    def channel_freq_shift(self, X):
+        """the channel's frequency shift over F consecutive frames of pl_frame * 2 complex samples"""
+        X, F = self._frames(X, 4 * self.pl_frame, np.float32)
+        Y = np.empty_like(X)
+        self._chk(self.L.dvbs2hip_channel_freq_shift(self.h, _ptr(X), _ptr(Y), F))
+        return Y
+
+    def channel_freq_shift_dev(self, X, Y, n_frames):
+        self._chk(self.L.dvbs2hip_channel_freq_shift_dev(self.h, _ptr(X), _ptr(Y), n_frames))
+
+    # ------------------------------------------------------------------ the coarse-frequency loop
+    def sync_coarse_set_pll(self, pll_sps=1, damping=0.5 ** 0.5, nbw=1e-4):
+        self._chk(self.L.dvbs2hip_sync_coarse_set_pll(self.h, int(pll_sps), float(damping), float(nbw)))
+
+    def sync_coarse_gains(self):
+        """(proportional, integrator) gains of the PLL (Synchronizer_freq_coarse_DVBS2_aib::set_PLL_coeffs)"""
+        pg, ig = C.c_float(), C.c_float()
+        self._chk(self.L.dvbs2hip_sync_coarse_get_gains(self.h, C.byref(pg), C.byref(ig)))
+        return pg.value, ig.value
+
+    def sync_coarse_get_freq(self):
+        """per stream: (estimated_freq, the floored nu the rotation uses)"""
+        S = getattr(self, "stm_streams", 1)
+        est, nu = np.empty(S, np.float32), np.empty(S, np.float32)
+        self._chk(self.L.dvbs2hip_sync_coarse_get_freq(self.h, _ptr(est), _ptr(nu)))
+        return est, nu
+
+    def sync_step_mf_synchronize(self, DEL, X_N1):
+        """the fused coarse-frequency / matched-filter / timing loop over F frames of pl_frame * 2 complex samples -> (MU[F], FRQ[F], PHS[F], Y_N1, B_N1)"""
+        X, F = self._frames(X_N1, 4 * self.pl_frame, np.float32)
+        D = np.ascontiguousarray(DEL, dtype=np.int32).ravel()
+        if D.size != F:
+            raise ValueError("DEL holds %d delays for %d frames" % (D.size, F))
+        Y, Bf = np.empty_like(X), np.empty(X.shape, np.int32)
+        MU, FRQ, PHS = (np.empty(F, np.float32) for _ in range(3))
+        self._chk(self.L.dvbs2hip_sync_step_mf_synchronize(self.h, _ptr(D), _ptr(X), _ptr(MU), _ptr(FRQ), _ptr(PHS), _ptr(Y), _ptr(Bf), F))
+        return MU, FRQ, PHS, Y, Bf
+
+    def sync_step_mf_synchronize_dev(self, DEL, X, MU, FRQ, PHS, Y, B_N1, n_frames):
+        self._chk(self.L.dvbs2hip_sync_step_mf_synchronize_dev(self.h, _ptr(DEL), _ptr(X), _ptr(MU), _ptr(FRQ), _ptr(PHS), _ptr(Y), _ptr(B_N1), n_frames))
+
+    def sync_step_mf_reset(self):
+        self._chk(self.L.dvbs2hip_sync_step_mf_reset(self.h))
+
     def pl_descramble(self, Y_N1):
         X, F = self._frames(Y_N1, 2 * self.pl_frame, np.float32)
         out = np.empty_like(X)

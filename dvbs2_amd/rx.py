@@ -1,5 +1,7 @@
-"""`dvbs2_rx` work-alike without the coarse frequency loop (out of scope): raw IQ file -> front gain stage (Multiplier_AGC, RX/main_sched.cpp:197)
--> coarse frequency shift (--coarse-freq; :198) -> matched filter (a5) -> symbol timing (--stm-type: extraction at a known phase, or FAST, the Gardner loop on the GPU, :202-204) -> gain stage
+"""`dvbs2_rx` work-alike: raw IQ file -> [--wl-phases: the waiting and learning phases on the head of the file, dvbs2_amd/acquire.py, which find the carrier offset with the
+coarse frequency loop on the GPU (--wl-frames L1 L2 L3: frames of learning phases 1 to 3, default 150 150 200; --wl-wait-max: frames after which the waiting phase gives up,
+default 2000); without it the offset is handed in by --coarse-freq] -> front gain stage (Multiplier_AGC, RX/main_sched.cpp:197)
+-> coarse frequency shift (:198) -> matched filter (a5) -> symbol timing (--stm-type: extraction at a known phase, or FAST, the Gardner loop on the GPU, :202-204) -> gain stage
 (main_sched.cpp:205) -> frame synchronizer (N4) -> pilot-aided phase synchronizer (N4, optional) -> fused RX chain (a7 .. a8) -> monitor against the source pattern -> sink.  It serves
 files made by `dvbs2_amd.tx` / `dvbs2_amd.ch` (or by the reference's dvbs2_tx / dvbs2_ch without timing or frequency
 offsets): README.md:151-169 of the reference.
@@ -34,12 +36,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dec-ite", type=int, default=50)
     ap.add_argument("--dec-alpha", type=float, default=1.0)
     ap.add_argument("--dec-simd", default="", help="accepted and ignored (the GPU batches frames with -F)")
-    ap.add_argument("--no-wl-phases", action="store_true", help="accepted: there are no waiting / learning phases here")
+    wl = ap.add_mutually_exclusive_group()
+    wl.add_argument("--no-wl-phases", action="store_true", help="accepted: the waiting / learning phases do not run unless --wl-phases asks for them")
+    wl.add_argument("--wl-phases", action="store_true", help="run the reference's waiting and learning phases (main_sched.cpp:407-635) on the head of the file, then decode the rest; "
+                                                             "needs --stm-type FAST, excludes --coarse-freq")
+    ap.add_argument("--wl-frames", type=int, nargs=3, default=[150, 150, 200], metavar=("L1", "L2", "L3"), help="frames of learning phases 1, 2 and 3")
+    ap.add_argument("--wl-wait-max", type=int, default=2000, help="frames after which the waiting phase gives up")
     ap.add_argument("--snk-path", default="", help="decoded payload of every frame, eight bits per byte (the reference's Sink_user_binary: a file sent with dvbs2_tx --src-type USER_BIN comes out as it went in)")
     ap.add_argument("--timing-offset", type=int, default=-1, help="sample index of the first symbol after the matched filter (default: two group delays)")
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
-                                                                   "phase (the frequency shift) with this as its loop's frozen estimate; the loop itself is sample-serial and out of scope")
+                                                                   "phase (the frequency shift) with this as its loop's frozen estimate (--wl-phases runs the loop instead)")
     ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="symbol timing: PERFECT takes every osf-th sample from --timing-offset (the default here); "
                                                                                      "FAST runs the reference's Gardner loop (Synchronizer_Gardner_fast_osf2) on the GPU")
     ap.add_argument("--stm-df", type=float, default=0.5 ** 0.5, help="damping factor of the Gardner loop filter")
@@ -64,6 +71,11 @@ def run(args, out=sys.stdout) -> dict:
     if args.coarse_freq:
         rx.sync_coarse_set_freq(args.coarse_freq)
     fast = args.stm_type == "FAST"
+    wl = getattr(args, "wl_phases", False)
+    if wl and args.coarse_freq:
+        raise ValueError("--wl-phases finds the carrier offset itself: it excludes --coarse-freq")
+    if wl and not fast:
+        raise ValueError("--wl-phases runs the Gardner loop: it needs --stm-type FAST")
     if fast:
         if osf != 2:
             raise ValueError("--stm-type FAST is the Gardner loop at two samples per symbol (--shp-osf 2)")
@@ -76,6 +88,12 @@ def run(args, out=sys.stdout) -> dict:
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
     stable = 0                                                                     # frames since the synchronizer's delay last moved
     try:
+        if wl:
+            from .acquire import acquire
+            l1, l2, l3 = args.wl_frames
+            st["acquisition"] = acq = acquire(rx, rcv.receive, n_frames=F, osf=osf, learn1=l1, learn2=l2, learn3=l3, wait_max=args.wl_wait_max, agc=not args.no_agc)
+            print("# waiting %d | learning %d + %d + %d frames | packet flag %s | coarse frequency %s" % (
+                acq["frames"]["waiting"], acq["frames"]["learning1"], acq["frames"]["learning2"], acq["frames"]["learning3"], acq["flag"], acq["freq"]), file=out)
         while not args.max_frames or st["frames"] < args.max_frames:
             try:
                 x = rcv.receive()
@@ -84,7 +102,7 @@ def run(args, out=sys.stdout) -> dict:
             x = x.astype(np.float32, copy=False)
             if not args.no_agc:
                 x = rx.agc(x, n_frames=F, output_energy=1.0 / osf)                  # front_agc: DVBS2.cpp:660-664
-            if args.coarse_freq:
+            if args.coarse_freq or wl:
                 _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)                  # sync_coarse_f: RX/main_sched.cpp:198-200
             if fast:
                 # sync_timing: synchronize -> extract (RX/main_sched.cpp:202-204); a call that underflows holds its symbols for the next one
@@ -107,10 +125,13 @@ def run(args, out=sys.stdout) -> dict:
                 if not args.no_agc:
                     blk = rx.agc(blk, n_frames=Fb, output_energy=1.0)                   # mult_agc: DVBS2.cpp:653-657
                 delay, flags, tri, aligned = rx.sync_frame_synchronize(blk.reshape(Fb, 2 * n), with_flags=True)
-                if args.sync_fine:
+                if args.sync_fine or wl:
                     # the reference's task order (src/mains/RX/main.cpp): PL descramble -> fine synchronizer -> remove PLH ->
                     # estimate -> demodulate + deinterleave -> LDPC -> BCH -> BB descramble, one C-ABI call per task
-                    _, _, fixed = rx.sync_freq_phase_synchronize(rx.pl_descramble(aligned))
+                    desc = rx.pl_descramble(aligned)
+                    if wl:
+                        _, _, desc = rx.sync_lr_synchronize(desc)                     # what the frozen coarse estimate leaves: L&R, as learning phase 3 has trained it (main_sched.cpp:208)
+                    _, _, fixed = rx.sync_freq_phase_synchronize(desc)
                     xf = rx.remove_plh(fixed)
                     sig, _, _ = rx.estimate(xf)
                     vk, _ = rx.decode_siho(rx.demodulate(sig, xf, deinterleave=True))

@@ -17,9 +17,12 @@
 //      --stm-type FAST binds Synchronizer_timing_hip (the Gardner loop, main_sched.cpp:202-204; a batch whose extract underflows stops
 //      behind it, as the reference's sequence does at processing_aborted, and the payload source only advances for batches that go through); the source is a file of the sent payloads delayed by --src-delay frames (the frame synchronizer's latency;
 //      what Filter_buffered_delay does in the TX_RX mains).
+//      --wl-phases (with --stm-type FAST) runs the reference's waiting and learning phases on the head of the file first (main_sched.cpp:407-635): Synchronizer_step_mf_hip,
+//      the coarse-frequency loop on the GPU, bound as main_sched.cpp:428-432 with a Feedbacker for DEL; --wl-frames L1 L2 L3 (150 150 200), --wl-wait-max (2000).
 //
 // With --src the monitor runs (check_errors in (1), check_errors2 with its BE / FE / BER / FER sockets read by probe stand-ins
 // in (2)) and FRA / BE / FE are printed like the reference's terminal.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -57,6 +60,35 @@ public:
     runtime::Task &operator[](src::tsk) { return *tasks[0]; }
 private:
     int K; std::ifstream in; std::vector<int> fifo;
+};
+// Feedbacker (StreamPU): `produce` hands out what `memorize` took at the iteration before (zeros at first) -- main_sched.cpp:429-430
+namespace fbr { enum class tsk : size_t { produce, memorize }; namespace sck { enum class produce : size_t { Y_N, status }; enum class memorize : size_t { X_N, status }; } }
+template <typename T> class Feedbacker : public Module {
+public:
+    Feedbacker(int size, T init, int n_frames_) : mem((size_t)size * n_frames_, init)
+    {
+        n_frames = (size_t)n_frames_;
+        auto &p = create_task("produce");
+        auto so = create_socket_out<T>(p, "Y_N", size);
+        create_codelet(p, [so](Module &m, runtime::Task &tk, size_t) -> int {
+            auto &f = static_cast<Feedbacker &>(m);
+            std::copy(f.mem.begin(), f.mem.end(), tk[so].template get_dataptr<T>());
+            return 0;
+        });
+        auto &q = create_task("memorize");
+        auto si = create_socket_in<T>(q, "X_N", size);
+        create_codelet(q, [si](Module &m, runtime::Task &tk, size_t) -> int {
+            auto &f = static_cast<Feedbacker &>(m);
+            const T *x = tk[si].template get_dataptr<const T>();
+            std::copy(x, x + f.mem.size(), f.mem.begin());
+            return 0;
+        });
+    }
+    runtime::Socket &operator[](fbr::sck::produce s) { return (*tasks[0])[(size_t)s]; }
+    runtime::Socket &operator[](fbr::sck::memorize s) { return (*tasks[1])[(size_t)s]; }
+    runtime::Task &operator[](fbr::tsk t) { return *tasks[(size_t)t]; }
+private:
+    std::vector<T> mem;
 };
 template <typename T> class Probe_value : public Module {     // keeps the last value of the socket it is bound to
 public:
@@ -101,7 +133,8 @@ public:
 }}  // namespace aff3ct::module
 
 static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite, float alpha, const std::string &implem, const std::string &in_path,
-                                    const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq, bool stm_fast)
+                                    const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq, bool stm_fast,
+                                    bool wl_phases = false, int wl1 = 150, int wl2 = 150, int wl3 = 200, int wl_wait_max = 2000)
 {
     using namespace module;
     const int osf = 2;
@@ -189,6 +222,56 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     if (!out_path.empty()) out.open(out_path, std::ios::binary);
     size_t batches = 0;
     size_t aborted = 0;
+    if (wl_phases) {
+        // the waiting and learning phases of RX/main_sched.cpp:407-635 on the head of the file
+        namespace fbr = spu::module::fbr;
+        std::unique_ptr<Synchronizer_step_mf_hip<>> sync_step_mf(new Synchronizer_step_mf_hip<>(sync_coarse_f.get(), matched_flt.get(), sync_timing.get(), ctx));
+        std::unique_ptr<spu::module::Feedbacker<int>> feedbr(new spu::module::Feedbacker<int>(1, 0, F));
+        // partial binding
+        (*sync_step_mf)[             smf::sck::synchronize::X_N1] = (*front_agc   )[mlt::sck::imultiply   ::Z_N ];   // main_sched.cpp:428
+        (*sync_step_mf)[             smf::sck::synchronize::DEL ] = (*feedbr      )[fbr::sck::produce     ::Y_N ];   // main_sched.cpp:429
+        (*feedbr      )[             fbr::sck::memorize   ::X_N ] = (*sync_frame  )[sfm::sck::synchronize2::DEL ];   // main_sched.cpp:430
+        (*sync_timing )[             stm::sck::extract    ::B_N1] = (*sync_step_mf)[smf::sck::synchronize ::B_N1];   // main_sched.cpp:431
+        (*sync_timing )[             stm::sck::extract    ::Y_N1] = (*sync_step_mf)[smf::sck::synchronize ::Y_N1];   // main_sched.cpp:432
+        // the sequence from the radio to the Feedbacker's memorize (firsts / lasts of main_sched.cpp:438-454); an underflowing extract cuts an iteration short
+        spu::runtime::Sequence wl12a({&(*feedbr)[fbr::tsk::produce], &(*front_agc)(), &(*sync_step_mf)[smf::tsk::synchronize], &(*sync_timing)[stm::tsk::extract]});
+        spu::runtime::Sequence wl12b({&(*mult_agc)(), &(*sync_frame)[sfm::tsk::synchronize1], &(*sync_frame)[sfm::tsk::synchronize2], &(*feedbr)[fbr::tsk::memorize]});
+        auto wl12_step = [&]() -> bool {
+            if (!in.read(reinterpret_cast<char *>(rx_samples.data()), rx_samples.size() * sizeof(float))) return false;
+            try { wl12a.exec_step(); } catch (const spu::tools::processing_aborted &) { return true; }
+            wl12b.exec_step();
+            return true;
+        };
+        int waited = 0;
+        bool more = true, flag = false;
+        sync_coarse_f->set_PLL_coeffs(1, 1 / std::sqrt(2.0), 1e-4);                                                   // main_sched.cpp:472
+        while (!flag && waited < wl_wait_max && (more = wl12_step())) { waited += F; flag = sync_frame->get_packet_flag(); }      // :478-494
+        if (!flag) { std::printf("# waiting phase gave up after %d frames\n", waited); return 4; }
+        sync_step_mf->reset();                                                                                       // main_sched.cpp:500
+        sync_frame  ->reset();                                                                                       // main_sched.cpp:501
+        sync_timing ->reset();                                                                                       // main_sched.cpp:502
+        int m = 0, limit = wl1;
+        bool second = false;
+        sync_coarse_f->set_PLL_coeffs(1, 1 / std::sqrt(2.0), 1e-4);                                                   // main_sched.cpp:529
+        while (m < limit && (more = wl12_step())) {                                                                  // :535-560
+            m += F;
+            if (!second && m >= wl1) { second = true; limit = m + wl2; sync_coarse_f->set_PLL_coeffs(1, 1 / std::sqrt(2.0), 5e-5); }      // :548-558
+        }
+        const int learned12 = m;
+        // learning phase 3: partial binding back to the steady-state graph
+        (*sync_coarse_f)[             sfc::sck::synchronize::X_N1] = (*front_agc    )[mlt::sck::imultiply  ::Z_N ];   // main_sched.cpp:576
+        (*sync_timing  )[             stm::sck::extract    ::B_N1] = (*sync_timing  )[stm::sck::synchronize::B_N1];   // main_sched.cpp:577
+        (*sync_timing  )[             stm::sck::extract    ::Y_N1] = (*sync_timing  )[stm::sck::synchronize::Y_N1];   // main_sched.cpp:578
+        spu::runtime::Sequence l3({&(*mult_agc)(), &(*sync_frame)[sfm::tsk::synchronize1], &(*sync_frame)[sfm::tsk::synchronize2], &(*pl_scrambler)(), &(*sync_fine_lr)(),
+                                   &(*sync_fine_pf)()});                                                            // up to lasts_l3, main_sched.cpp:595
+        m = 0;
+        while (more && m < wl3 && in.read(reinterpret_cast<char *>(rx_samples.data()), rx_samples.size() * sizeof(float))) {      // :613-630
+            m += F;
+            try { seq.exec_step(); } catch (const spu::tools::processing_aborted &) { continue; }
+            l3.exec_step();
+        }
+        std::printf("# wl phases | waiting %d | learning %d + %d frames | coarse frequency %.6f\n", waited, learned12, m, (double)sync_coarse_f->get_estimated_freq());
+    }
     while (in.read(reinterpret_cast<char *>(rx_samples.data()), rx_samples.size() * sizeof(float))) {
         try {
             seq.exec_step();
@@ -202,7 +285,7 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
         // alpha = 0.999.  In the reference the fine synchronizers do not run before the frame synchronizer has locked -- its learning phases 1 and 2 end at sync_frame
         // (main_sched.cpp:454,535) -- and then settle for a learning phase 3 (:597-630) before anything is counted.  Here: the first half of --mon-skip is phases 1 and 2 (what the
         // estimate saw of the unaligned frames is dropped), the second half is phase 3.
-        if ((int)batches < (mon_skip + 1) / 2) sync_fine_lr->reset();
+        if (!wl_phases && (int)batches < (mon_skip + 1) / 2) sync_fine_lr->reset();
         if (out.is_open())
             out.write(reinterpret_cast<const char *>((*bb_scrambler)[scr::sck::descramble::Y_N2].get_dataptr<int>()), (size_t)F * ctx->sz.K_bch * sizeof(int));
         batches++;
@@ -223,7 +306,8 @@ int main(int argc, char **argv)
     int F = 1, n_ite = 50, src_delay = 0, mon_skip = 0;
     float coarse_freq = 0.f;
     float alpha = 1.0f;
-    bool frame_sync = false, matched = false, stm_fast = false;
+    bool frame_sync = false, matched = false, stm_fast = false, wl_phases = false;
+    int wl[3] = {150, 150, 200}, wl_wait_max = 2000;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; exit(2); } return argv[++i]; };
@@ -238,6 +322,9 @@ int main(int argc, char **argv)
         else if (a == "--src-delay") src_delay = std::stoi(next());
         else if (a == "--mon-skip") mon_skip = std::stoi(next());
         else if (a == "--coarse-freq") coarse_freq = std::stof(next());      // normalized frequency offset of the received samples (cycles per sample): the coarse synchronizer's frozen estimate
+        else if (a == "--wl-phases") wl_phases = true;                         // the waiting and learning phases on the head of the file (main_sched.cpp:407-635)
+        else if (a == "--wl-frames") { for (int &w : wl) w = std::stoi(next()); }
+        else if (a == "--wl-wait-max") wl_wait_max = std::stoi(next());
         else if (a == "--frame-sync") frame_sync = true;
         else if (a == "--matched-filter") matched = true;
         else if (a == "--stm-type") { const std::string t = next(); if (t != "PERFECT" && t != "FAST") { std::cerr << "--stm-type: PERFECT or FAST\n"; return 2; } stm_fast = t == "FAST"; }
@@ -245,7 +332,9 @@ int main(int argc, char **argv)
     }
     try {
         if (stm_fast && !matched) { std::cerr << "--stm-type FAST needs --matched-filter (the timing synchronizer runs on the samples)\n"; return 2; }
-        if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq, stm_fast);
+        if (wl_phases && (!stm_fast || coarse_freq != 0.f)) { std::cerr << "--wl-phases needs --matched-filter --stm-type FAST and excludes --coarse-freq\n"; return 2; }
+        if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq, stm_fast, wl_phases,
+                                                     wl[0], wl[1], wl[2], wl_wait_max);
         auto ctx = std::make_shared<module::Context>(modcod, F, n_ite, alpha, true, 0, implem);
         ctx->pin_sockets = true;            // the sockets below live until the modules go: pin them for overlapped PCIe copies
         module::Scrambler_PL_hip pl_scrambler(ctx);

@@ -90,6 +90,9 @@ namespace rcv { namespace sck { enum class receive : size_t { Y_N1, V_K, CWD_LDP
 // Synchronizer_timing.hxx:48-78 (tasks synchronize and extract)
 namespace stm { enum class tsk : size_t { synchronize, extract, SIZE };
                 namespace sck { enum class synchronize : size_t { X_N1, MU, Y_N1, B_N1, status }; enum class extract : size_t { Y_N1, B_N1, UFW, Y_N2, status }; } }
+// Synchronizer_step_mf_cc.cpp:49-56 (task synchronize: DEL, X_N1 in; MU, FRQ, PHS, Y_N1, B_N1 out)
+namespace smf { enum class tsk : size_t { synchronize, SIZE };
+                namespace sck { enum class synchronize : size_t { DEL, X_N1, MU, FRQ, PHS, Y_N1, B_N1, status }; } }
 // Synchronizer_freq_fine.hpp:14-19
 namespace sff { enum class tsk : size_t { synchronize, SIZE }; namespace sck { enum class synchronize : size_t { X_N1, FRQ, PHS, Y_N2, status }; } }
 // Synchronizer_frame.hpp:15-24
@@ -356,7 +359,8 @@ public:
 
 // replaces Synchronizer_freq_coarse<R> in the transmission phase: its task `synchronize` is the frequency shift alone (Synchronizer_freq_coarse_DVBS2_aib.cpp:43-50 ->
 // Multiplier_sine_ccc_naive::imultiply; sockets Synchronizer_freq_coarse.hxx:35-39).  The PLL that finds the frequency (update_phase, one step per pilot symbol fed back from the
-// timing synchronizer in the learning phases) is sample-serial and stays on the CPU: set_curr_freq() takes its result.  N values per frame (2 * pl_frame_size * osf: DVBS2.cpp build_synchronizer_freq_coarse)
+// timing synchronizer in the learning phases) runs on the GPU as well, inside dvbs2hip_sync_step_mf_synchronize (k_stepmf.hip), and this task carries on with the frequency and
+// the sample counter that loop leaves in the handle; set_curr_freq() still sets a frequency by hand.  N values per frame (2 * pl_frame_size * osf: DVBS2.cpp build_synchronizer_freq_coarse)
 template <typename R = float>
 class Synchronizer_freq_coarse_hip : public Module_hip {
 public:
@@ -376,9 +380,48 @@ public:
     }
     void synchronize(const R *X_N1, R *FRQ, R *PHS, R *Y_N2) { DVBS2HIP_CHK(ctx, dvbs2hip_sync_coarse_synchronize(ctx->h, X_N1, FRQ, PHS, Y_N2, N_ / 2, F())); }
     void set_curr_freq(R estimated_freq) { DVBS2HIP_CHK(ctx, dvbs2hip_sync_coarse_set_freq(ctx->h, (float)estimated_freq)); }
+    void set_PLL_coeffs(const int pll_sps, const R damping_factor, const R normalized_bandwidth)      // Synchronizer_freq_coarse_DVBS2_aib.cpp:94-113
+    {
+        DVBS2HIP_CHK(ctx, dvbs2hip_sync_coarse_set_pll(ctx->h, pll_sps, (float)damping_factor, (float)normalized_bandwidth));
+    }
+    R get_estimated_freq() { float e = 0.f, nu = 0.f; DVBS2HIP_CHK(ctx, dvbs2hip_sync_coarse_get_freq(ctx->h, &e, &nu)); return (R)e; }      // (one stream)
     void reset() { DVBS2HIP_CHK(ctx, dvbs2hip_sync_coarse_reset(ctx->h)); }
 private:
     int N_;
+};
+
+// replaces Synchronizer_step_mf_cc<B,R> (Synchronizer_step_mf_cc.cpp:13-71), the task of the waiting and learning phases 1-2 (RX/main_sched.cpp:428-432): the coarse
+// synchronizer's rotation and PLL, the matched filter's step and the timing synchronizer's step, fused per sample (k_stepmf.hip).  The reference builds it from its three
+// modules and runs on their state; here that state lives in the handle, so the modules passed in only have to belong to the same Context.  One stream; sockets by the
+// reference's names.  reset() = Synchronizer_step_mf_cc::reset (coarse, matched filter, timing).
+template <typename B = int, typename R = float>
+class Synchronizer_step_mf_hip : public Module_hip {
+public:
+    Synchronizer_step_mf_hip(Synchronizer_freq_coarse_hip<R> *sync_coarse_f, Filter_FIR_hip *matched_filter, Synchronizer_timing_hip<B, R> *sync_timing, std::shared_ptr<Context> c)
+    : Module_hip(std::move(c), "Sync_step_mf")
+    {
+        static_assert(sizeof(B) == 4 && sizeof(R) == 4, "B = int32, R = float");
+        if (!sync_coarse_f || !matched_filter || !sync_timing) throw spu::tools::invalid_argument(__FILE__, __LINE__, __func__, "the three modules the loop shares its state with are needed");
+        const size_t N = 4 * (size_t)ctx->sz.pl_frame_sym;
+        auto &t = create_task("synchronize");
+        auto sD = create_socket_in<int>(t, "DEL", 1);
+        auto sX = create_socket_in<R>(t, "X_N1", N);
+        auto sM = create_socket_out<R>(t, "MU", 1);
+        auto sF = create_socket_out<R>(t, "FRQ", 1);
+        auto sP = create_socket_out<R>(t, "PHS", 1);
+        auto sY = create_socket_out<R>(t, "Y_N1", N);
+        auto sB = create_socket_out<B>(t, "B_N1", N);
+        create_codelet(t, [sD, sX, sM, sF, sP, sY, sB](spu::module::Module &m, spu::runtime::Task &tk, size_t) -> int {
+            auto &me = static_cast<Synchronizer_step_mf_hip &>(m);
+            DVBS2HIP_CHK(me.ctx, dvbs2hip_sync_step_mf_synchronize(me.ctx->h, (const int32_t *)tk[sD].template get_dataptr<const int>(), tk[sX].template get_dataptr<const R>(),
+                                                                   tk[sM].template get_dataptr<R>(), tk[sF].template get_dataptr<R>(), tk[sP].template get_dataptr<R>(),
+                                                                   tk[sY].template get_dataptr<R>(), (int32_t *)tk[sB].template get_dataptr<B>(), me.F()));
+            return 0;
+        });
+    }
+    spu::runtime::Task &operator[](smf::tsk t) { return *tasks[(size_t)t]; }
+    spu::runtime::Socket &operator[](smf::sck::synchronize s) { return (*tasks[0])[(size_t)s]; }
+    void reset() { DVBS2HIP_CHK(ctx, dvbs2hip_sync_step_mf_reset(ctx->h)); }
 };
 
 // replaces Framer<B>::remove_plh (Framer.hxx:330-343)

@@ -395,6 +395,42 @@ int dvbs2hip_channel_set_delay(dvbs2hip_t *h, float D);
 int dvbs2hip_channel_delay(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
 int dvbs2hip_channel_delay_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
 
+/* The channel's frequency shift, the task between the fractional delay and the noise (CH/main.cpp:63-64)
+ * replaces: Multiplier_sine_ccc_naive::imultiply built by DVBS2.cpp:624-626 from --chn-max-freq-shift (cycles per sample, floored to six decimals; Fs = 1): the stream times
+ * exp(j 2 pi nu n), n = 0 .. 999999 the stream position.  set_freq_shift starts the position over.  X, Y: float[n_frames * 2 N], N = pl_frame * osf.  Graph capture: refused,
+ * as dvbs2hip_sync_coarse_synchronize_dev (the stream position is a launch argument). */
+int dvbs2hip_channel_set_freq_shift(dvbs2hip_t *h, float freq_shift);
+int dvbs2hip_channel_freq_shift(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
+int dvbs2hip_channel_freq_shift_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_frames);
+
+/* ------------------------------------------------------------------ the coarse-frequency loop (the reference's waiting and learning phases 1-2, RX/main_sched.cpp:407-560)
+ * replaces: Synchronizer_step_mf_cc::synchronize -- src/common/Module/Synchronizer/Synchronizer_step_mf_cc.cpp:163-208: per complex sample the coarse synchronizer's rotation
+ * (Multiplier_sine_ccc_naive::step), the 81-tap matched filter's step (Filter_FIR_ccr_naive.hpp:36-49), the timing synchronizer's step (Synchronizer_Gardner_fast_osf2.hxx:8-87)
+ * and, on a strobe, Synchronizer_freq_coarse_DVBS2_aib::update_phase (.cpp:57-92: the pilot-aided detector, PI filter, integrator, set_nu(-estimated_freq)); once per frame
+ * curr_idx = (N_out - DEL + last_delay) mod (N_out / 2) from the frame synchronizer's delay of the call before (the reference's Feedbacker).
+ *   DEL int32_t[F], X_N1 float[F * 2 N] -> MU, FRQ, PHS float[F] (mu, estimated_freq, 0 after each frame), Y_N1 float[F * 2 N], B_N1 int32_t[F * 2 N]; N = pl_frame * 2
+ * Y_N1 / B_N1 are what dvbs2hip_sync_timing_extract takes.  Streams as for the timing entries (dvbs2hip_sync_timing_set_streams; one lane per stream).  Results are bit
+ * for bit the CPU twin's (tests/stepmf_twin.c); its header states the two places where the arithmetic is this library's own: the rotation evaluates cos / sin of the exact
+ * turn fraction (nu n mod 1) and the matched filter sums 41 symmetric products in a fixed order.
+ * State is shared with the block-wise tasks, as the reference's modules share theirs: the loop runs on the timing synchronizer's per-stream state (so that
+ * dvbs2hip_sync_timing_synchronize / _extract carry on from it), on the coarse synchronizer's frequency and sample counter (so that dvbs2hip_sync_coarse_synchronize carries
+ * on with the learned frequency and a continuous phase; with S streams that state is per stream, and set_freq sets all of them) and, with one stream, on the matched
+ * filter's memory (dvbs2hip_filter / filter1 carry on from it and back; with S > 1 the loop keeps a memory per stream of its own, as the block-wise filter is one stream).
+ * set_pll = set_PLL_coeffs(pll_sps, damping, nbw) (.cpp:94-113; defaults 1, sqrt(0.5), 1e-4); get_gains: the proportional and integrator gains that follow;
+ * get_freq: per stream (float[S] each) estimated_freq and the nu in use (floored to six decimals, = -estimated_freq).  step_mf_reset = Synchronizer_step_mf_cc::reset: the coarse
+ * synchronizer, the matched filter's memory and the timing synchronizer.  dvbs2hip_sync_coarse_reset also clears the PLL.
+ * dvbs2hip_sync_coarse_set_freq and dvbs2hip_sync_coarse_reset, host-only setters before the loop existed, now act on the per-stream state: when the loop ran last they
+ * first bring that state back from the device (one small blocking copy on the handle's stream) and, like every entry that needs it on the host, return
+ * DVBS2HIP_EUNSUPPORTED inside an open capture in that case.  Without a step_mf call on the handle they behave as before.
+ * The handle's filter must have 81 symmetric taps (taps[i] == taps[80 - i], checked at create): otherwise step_mf returns DVBS2HIP_EUNSUPPORTED.
+ * Graph capture: a task with a memory, the rule of the timing entries holds; the first call (it allocates and uploads) and the resets refuse an open capture. */
+int dvbs2hip_sync_coarse_set_pll(dvbs2hip_t *h, int32_t pll_sps, float damping, float nbw);
+int dvbs2hip_sync_coarse_get_gains(dvbs2hip_t *h, float *proportional, float *integrator);
+int dvbs2hip_sync_coarse_get_freq(dvbs2hip_t *h, float *estimated_freq, float *nu);
+int dvbs2hip_sync_step_mf_synchronize(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t n_frames);
+int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t n_frames);
+int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h);
+
 /* ------------------------------------------------------------------ N4: frame synchronizer
  * replaces: Synchronizer_frame_DVBS2_fast<R> (type "FAST", the factory default,
  * src/common/Factory/Module/Synchronizer_frame/Synchronizer_frame.cpp:71-72, .hpp:26-30) --

@@ -14,7 +14,11 @@ Filters, synchronizers and the delay line keep their state from call to call, so
 
 --chn-max-delay D puts the reference channel's three delay tasks (dvbs2hip_channel_delay) behind the shaping filter, and --stm-type FAST replaces the genie by the
 Gardner timing loop on the GPU (synchronize -> extract, RX/main_sched.cpp:202-204): a call whose extract underflows yields no frames, and the loop's learning frames
-are the first --skip frames, which are not counted."""
+are the first --skip frames, which are not counted.
+
+--chn-max-freq-shift f puts the channel's frequency shift (dvbs2hip_channel_freq_shift, f cycles per sample) behind the delay tasks, and --wl-phases runs the reference's
+waiting and learning phases (dvbs2_amd/acquire.py: the coarse-frequency loop on the GPU, 150 / 150 / 200 frames) on the head of the stream before anything is counted; the
+transmission phase then shifts by the frozen estimate (dvbs2hip_sync_coarse_synchronize) in front of the matched filter.  --wl-phases needs --stm-type FAST."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,12 +36,23 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     rot = variant == "fine"
     delay_D = getattr(a, "chn_max_delay", None)
     fast = getattr(a, "stm_type", "PERFECT") == "FAST"
+    freq_shift = getattr(a, "chn_max_freq_shift", None)
+    wl = getattr(a, "wl_phases", False)
+    if wl and not fast:
+        raise ValueError("--wl-phases needs --stm-type FAST")
     if delay_D is not None:
         rx.channel_set_delay(delay_D)
+    if freq_shift is not None:
+        rx.channel_set_freq_shift(freq_shift)
     st = dict(frames=0, counted=0, be=0, fe=0, delay=None, stable=0, moved=0)
-    t0, k = time.time(), 0
+    t0 = time.time()
     idx = (np.arange(F * n) - off) % n
-    while st["fe"] < a.fe and st["counted"] < a.max_frames:
+    calls = [0]
+
+    def received():
+        """the next F frames of the receiver's input, before its front gain stage"""
+        k = calls[0]
+        calls[0] += 1
         t = np.arange(F * n, dtype=np.float64) + float(k) * F * n                      # absolute symbol index of this call's stretch of the stream
         s = frame[idx]                                                                 # F n is a multiple of n: the same indices every call
         if rot:
@@ -46,20 +61,30 @@ def run_point(Rx, P, mc, ebn0, variant, a):
         up = rx.shape_filter(x, n_frames=F, osf=2)
         if delay_D is not None:
             up = rx.channel_delay(up.reshape(F, -1))                                    # chn_frm_del -> chn_int_del -> chn_frac_del (TX_RX/main.cpp:215-218)
-        noisy = rx.add_noise(sigma, up, seed=(a.seed << 20) + k, n_frames=F)
+        if freq_shift is not None:
+            up = rx.channel_freq_shift(up.reshape(F, -1))                               # freq_shift (TX_RX/main.cpp:219)
+        return rx.add_noise(sigma, up, seed=(a.seed << 20) + k, n_frames=F)
+
+    if wl:
+        from dvbs2_amd.acquire import acquire
+        st["acquisition"] = acquire(rx, received, n_frames=F, agc=a.agc)
+        if not st["acquisition"]["acquired"]:
+            raise RuntimeError("the waiting phase gave up: %r" % (st["acquisition"],))
+    while st["fe"] < a.fe and st["counted"] < a.max_frames:
+        noisy = received()
         if a.agc:
             noisy = rx.agc(noisy, n_frames=F, output_energy=0.5)                        # front_agc (RX/main_sched.cpp:197; DVBS2.cpp:660-664)
+        if wl:
+            _, _, noisy = rx.sync_coarse_synchronize(noisy, n_frames=F)                 # sync_coarse_f with the loop's frozen estimate (main_sched.cpp:198)
         mf = rx.filter(noisy, n_frames=F).reshape(-1, 2)
         if fast:
             y, b, _ = rx.sync_timing_synchronize(mf.reshape(F, -1))
             y2, _, rdy = rx.sync_timing_extract(y, b)
-            k += 1
             if not rdy[0]:
                 continue                                                                # underflow: the symbols wait in the carry buffer
             sym = y2.reshape(F, 2 * n)
         else:
             sym = np.ascontiguousarray(mf[0::2]).reshape(F, 2 * n)                     # the two filters delay the stream by 40 symbols: part of the unknown frame start
-            k += 1
         if a.agc:
             sym = rx.agc(sym, n_frames=F, output_energy=1.0).reshape(F, 2 * n)          # mult_agc (main_sched.cpp:205; DVBS2.cpp:653-657)
         delay, flags, tri, aligned = rx.sync_frame_synchronize(sym, with_flags=True)
@@ -105,6 +130,8 @@ def main():
     ap.add_argument("--agc", action="store_true", help="the reference's two gain stages in the loop (front_agc on the samples, mult_agc on the symbols)")
     ap.add_argument("--chn-max-delay", type=float, default=None, help="the reference channel's delay tasks with this D (>= 2) behind the shaping filter")
     ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="PERFECT: timing by genie; FAST: the Gardner loop on the GPU")
+    ap.add_argument("--chn-max-freq-shift", type=float, default=None, help="the reference channel's frequency shift (cycles per sample) behind the delay tasks")
+    ap.add_argument("--wl-phases", action="store_true", help="run the waiting and learning phases (the coarse-frequency loop on the GPU) before anything is counted")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     from dvbs2_amd.receiver import Dvbs2Hip
