@@ -1,0 +1,302 @@
+// C ABI, the receiver's frame-level synchronizers: frame synchronizer (sfm_*), L&R fine frequency and pilot phase (sff_call, lr_*).
+#include "dvbs2hip_handle.h"
+
+using namespace dvbs2;
+
+// L&R timeout (sff_lr_fused_kernel): every estimate has been published by the time the launch is over, so the rotation alone is run again (the stores
+// the waiting workgroups dropped) -- with the estimates of THAT launch (the slot's own buffer).  The caller has synchronized the stream.  Returns 0 when there was
+// nothing to do or the recovery succeeded.
+static int lr_check_recover(dvbs2hip_t *h, int slot)
+{
+    auto &ls = h->lr_slot[slot];
+    ls.pending = false;
+    if (!h->lr_err_host || !((volatile uint32_t *)h->lr_err_host)[slot]) return 0;
+    ((volatile uint32_t *)h->lr_err_host)[slot] = 0u;
+    h->lr_timeouts++;
+    auto it = h->bufs.find(B_LR_TMP0 + slot);
+    if (!ls.x || !ls.y || it == h->bufs.end() || !it->second.p || it->second.bytes < sizeof(float) * 4 * (size_t)ls.F)
+        return fail(h, DVBS2HIP_EHIP, "L&R: a rotating workgroup timed out waiting for the recurrence and the call cannot be repeated (buffers unknown); re-run it with DVBS2HIP_LR=unfused");
+    HIPCHK(h, sff_lr_recover(ls.x, ls.y, (float *)it->second.p, ls.n, ls.F, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// every device-form L&R call that has not been looked at yet, oldest first (the stream is synchronized here)
+int dvbs2::lr_check_all(dvbs2hip_t *h)
+{
+    bool any = false;
+    for (int i = 0; i < dvbs2hip_handle::LR_SLOTS; i++) any |= h->lr_slot[i].pending;
+    if (!any) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int r = 0;
+    for (int i = 0; i < dvbs2hip_handle::LR_SLOTS; i++) {
+        const int s = (h->lr_next + i) % dvbs2hip_handle::LR_SLOTS;          // lr_next is the oldest slot
+        if (h->lr_slot[s].pending) { const int ri = lr_check_recover(h, s); if (ri && !r) r = ri; }
+    }
+    return r;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------ N4: frame synchronizer (Synchronizer_frame_DVBS2_fast)
+// DVBS2HIP_SYNC=valu (read at every call): the correlators as fp32 vector sums in the reference's order instead of the matrix cores
+static const uint16_t *sfm_frag(dvbs2hip_t *h)
+{
+    const char *e = getenv("DVBS2HIP_SYNC");
+    return e && !strcmp(e, "valu") ? nullptr : h->sfm.frag;
+}
+
+static int sfm_state_reset(dvbs2hip_t *h, bool all)
+{
+    const int n = h->pl_frame;
+    auto &S = h->sfm;
+    const float one[2] = {1.f, 0.f};                                               // reg_channel = (1, 0), .cpp:19 / :309
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(h, hipMemsetAsync(S.xh[i], 0, sizeof(float) * 2 * 64, h->stream));
+        HIPCHK(h, hipMemsetAsync(S.buff2[i], 0, sizeof(float) * (size_t)S.nbuff2, h->stream));
+        const int st[2] = {0, 1};                                                  // head2 = 0, first_time = true
+        HIPCHK(h, hipMemcpyAsync(S.st[i], st, sizeof st, hipMemcpyHostToDevice, h->stream));
+        if (all) HIPCHK(h, hipMemsetAsync(S.sofh[i], 0, sizeof(float) * 2 * 64, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(S.xh[S.xh_cur] + 2 * 63, one, sizeof one, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(S.cv, 0, sizeof(float) * (size_t)n, h->stream));
+    if (all) { HIPCHK(h, hipMemsetAsync(S.yprev[S.yp_cur], 0, sizeof(float) * 2 * (size_t)n, h->stream)); HIPCHK(h, hipMemsetAsync(S.metric, 0, sizeof(float), h->stream)); }
+    HIPCHK(h, hipStreamSynchronize(h->stream));                                    // `one` / `st` live on this stack
+    return 0;
+}
+
+static int sfm_ready(dvbs2hip_t *h)
+{
+    auto &S = h->sfm;
+    if (S.ready) return 0;
+    const int n = h->pl_frame;
+    S.nbuff2 = 4 * (n + 1);                                                        // Variable_delay_cc_naive(N, N/2, N/2): buff2(4 (max_delay + 1))
+    for (int i = 0; i < 2; i++) {
+        DEV_ALLOC_CHK(h, &S.xh[i], sizeof(float) * 2 * 64);
+        DEV_ALLOC_CHK(h, &S.sofh[i], sizeof(float) * 2 * 64);
+        DEV_ALLOC_CHK(h, &S.buff2[i], sizeof(float) * (size_t)S.nbuff2);
+        DEV_ALLOC_CHK(h, &S.st[i], sizeof(int) * 4);
+    }
+    DEV_ALLOC_CHK(h, &S.cv, sizeof(float) * (size_t)n);
+    for (int i = 0; i < 2; i++) DEV_ALLOC_CHK(h, &S.yprev[i], sizeof(float) * 2 * (size_t)n);
+    DEV_ALLOC_CHK(h, &S.keys, sizeof(unsigned long long) * (size_t)h->max_frames * (size_t)((n + 63) / 64) + sizeof(float) * 2 * (size_t)((h->max_frames + SYNC_SUB - 1) / SYNC_SUB) * (size_t)n);      // (+ the segments' {A, B} of the average over frames: k_sync.hip)
+    DEV_ALLOC_CHK(h, &S.metric, sizeof(float));
+    const std::vector<uint16_t> fr = sync_frag_default();
+    DEV_ALLOC_CHK(h, &S.frag, fr.size() * sizeof(uint16_t));
+    HIPCHK(h, hipMemcpy(S.frag, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    int r = sfm_state_reset(h, true);
+    if (r) return r;
+    S.ready = true;
+    return 0;
+}
+
+int dvbs2hip_sync_frame_set_params(dvbs2hip_t *h, float alpha, float trigger, int32_t vec_width)
+{
+    if (!h) return DVBS2HIP_EINVAL;
+    if (vec_width < 1) return fail(h, DVBS2HIP_EINVAL, "'vec_width' has to be greater than 0");
+    h->sfm.alpha = alpha; h->sfm.trigger = trigger; h->sfm.vec_width = vec_width;
+    return 0;
+}
+
+int dvbs2hip_sync_frame_reset(dvbs2hip_t *h)
+{
+    int r;
+    if ((r = enter(h)) || (r = sfm_ready(h))) return r;
+    return sfm_state_reset(h, false);                                              // .cpp:304-318: SOF_PLSC_delay keeps its memory
+}
+
+int dvbs2hip_sync_frame_synchronize1_dev(dvbs2hip_t *h, const float *X_N1, float *cor_SOF, float *cor_PLSC, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!X_N1 || !cor_SOF || !cor_PLSC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if ((r = sfm_ready(h))) return r;
+    auto &S = h->sfm;
+    Timer tm(h, DVBS2HIP_K_MISC);
+    HIPCHK(h, sync_corr_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * F, h->stream));
+    S.xh_cur ^= 1;
+    return 0;
+}
+
+// synchronize2, or (cor_SOF == cor_PLSC == null) the whole one-task synchronize with the correlators fused into the metric
+static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, const float *cor_PLSC, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F, const float **SRC = nullptr)
+{
+    int r = check_frames(h, F); if (r) return r;
+    int32_t *delay = DEL;
+    const bool fused = !cor_SOF && !cor_PLSC;
+    if (!X_N1 || (!fused && (!cor_SOF || !cor_PLSC)) || !delay || (!Y_N2 && !SRC)) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if ((r = sfm_ready(h))) return r;
+    auto &S = h->sfm;
+    const int n = h->pl_frame;
+    void *corr, *met;
+    void *dtab;
+    if ((r = ensure(h, B_SFM_CORR, sizeof(float) * (size_t)n * F, &corr)) || (r = ensure(h, B_SFM_MET, sizeof(float) * (size_t)F, &met)) ||
+        (r = ensure(h, B_SFM_DTAB, sizeof(int32_t) * (size_t)F, &dtab))) return r;
+    Timer tm(h, DVBS2HIP_K_MISC);
+    if (TRI) met = TRI;
+    const SyncTail tail{S.keys, delay, (float *)met, FLG, S.trigger, (int32_t *)dtab, S.metric, reinterpret_cast<float *>(S.keys + (size_t)h->max_frames * (size_t)((n + 63) / 64))};
+    if (fused) {
+        HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], S.cv, (float *)corr, tail,
+                                          n, F, S.alpha, S.vec_width, h->stream));
+        S.xh_cur ^= 1;
+    } else
+        HIPCHK(h, sync_metric_launch(cor_SOF, S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], cor_PLSC, S.cv, (float *)corr, tail, n, F, S.alpha, S.vec_width, h->stream));
+    S.sofh_cur ^= 1;
+    // the delay line is a recurrence from frame to frame made of copies only: resolved per output sample, one launch (k_sync.hip)
+    void *need = nullptr;
+    if (SRC) {      // located form: only the frames that are not a run of the input stream are materialized (into the handle's scratch); SRC[f] says where frame f starts
+        void *scr;
+        if ((r = ensure(h, B_SFM_SCR, sizeof(float) * 2 * (size_t)n * F, &scr)) || (r = ensure(h, B_SFM_NEED, sizeof(int32_t) * ((size_t)F + 2), &need))) return r;
+        Y_N2 = (float *)scr;
+    }
+    HIPCHK(h, sync_vdelay_launch(X_N1, S.yprev[S.yp_cur], S.yprev[S.yp_cur ^ 1], Y_N2, S.buff2[S.od_cur], S.buff2[S.od_cur ^ 1], S.st[S.od_cur], S.st[S.od_cur ^ 1],
+                                 (const int32_t *)dtab, n, S.nbuff2, F, h->stream, (int32_t *)need, SRC));
+    S.od_cur ^= 1;
+    S.yp_cur ^= 1;
+    return 0;
+}
+
+int dvbs2hip_sync_frame_synchronize2_dev(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, const float *cor_PLSC, int32_t *DEL, int32_t *FLG,
+                                         float *TRI, float *Y_N2, int32_t F)
+{
+    if (h && (!cor_SOF || !cor_PLSC)) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    return sfm_sync2(h, X_N1, cor_SOF, cor_PLSC, DEL, FLG, TRI, Y_N2, F);
+}
+
+int dvbs2hip_sync_frame_synchronize_dev(dvbs2hip_t *h, const float *X_N1, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F)
+{
+    // the one-task form: the two correlations are no sockets here and stay on chip (sync_corr_m_kernel); DVBS2HIP_SYNC_UNFUSED keeps
+    // the two-task path through device scratch (same numbers)
+    if (!getenv("DVBS2HIP_SYNC_UNFUSED")) return sfm_sync2(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, Y_N2, F);
+    int r = check_frames(h, F); if (r) return r;
+    const size_t nb = sizeof(float) * 2 * (size_t)h->pl_frame * F;
+    void *cs, *cp;
+    if ((r = ensure(h, B_SFM_SOF, nb, &cs)) || (r = ensure(h, B_SFM_PLSC, nb, &cp))) return r;
+    if ((r = dvbs2hip_sync_frame_synchronize1_dev(h, X_N1, (float *)cs, (float *)cp, F))) return r;
+    return dvbs2hip_sync_frame_synchronize2_dev(h, X_N1, (const float *)cs, (const float *)cp, DEL, FLG, TRI, Y_N2, F);
+}
+
+// (round 5) the frame synchronizer for a consumer of this library: instead of the delayed copy Y_N2 it returns, per frame, WHERE the aligned frame starts -- inside X_N1 for a
+// frame that is one run of the input stream (every frame in lock but the first and the last of a call), inside the handle's scratch for the others.  X_N1 and the table stay
+// valid until the next synchronizer call on this handle; the frames are 8-byte aligned.  DEL / FLG / TRI and the synchronizer's state are those of `synchronize`.
+int dvbs2hip_sync_frame_locate_dev(dvbs2hip_t *h, const float *X_N1, int32_t *DEL, int32_t *FLG, float *TRI, const float **SRC, int32_t F)
+{
+    if (h && !SRC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    return sfm_sync2(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, nullptr, F, SRC);
+}
+
+int dvbs2hip_sync_frame_synchronize1(dvbs2hip_t *h, const float *X_N1, float *cor_SOF, float *cor_PLSC, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    const size_t nb = sizeof(float) * 2 * (size_t)h->pl_frame * F;
+    return host_call(h, F, false, {{X_N1, B_IN, nb}}, {{cor_SOF, B_SFM_SOF, nb}, {cor_PLSC, B_SFM_PLSC, nb}},
+                     [&](void *const *i, void *const *o, int nf) { return dvbs2hip_sync_frame_synchronize1_dev(h, (const float *)i[0], (float *)o[0], (float *)o[1], nf); });
+}
+
+// host-socket forms of synchronize2 / synchronize: DEL, FLG, TRI have one entry per frame (Synchronizer_frame.hxx:42-44); FLG, TRI may be NULL
+static int sfm_host(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, const float *cor_PLSC, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    const size_t nb = sizeof(float) * 2 * (size_t)h->pl_frame * F, nf4 = 4 * (size_t)F;
+    return host_call(h, F, false, {{X_N1, B_IN, nb}, {cor_SOF, B_SFM_SOF, nb, 0, true}, {cor_PLSC, B_SFM_PLSC, nb, 0, true}},
+                     {{DEL, B_SFM_DLY, nf4}, {FLG, B_SFM_DLY, nf4, nf4, true}, {TRI, B_SFM_DLY, nf4, 2 * nf4, true}, {Y_N2, B_OUT, nb}}, [&](void *const *i, void *const *o, int nf) {
+        if (cor_SOF) return dvbs2hip_sync_frame_synchronize2_dev(h, (const float *)i[0], (const float *)i[1], (const float *)i[2], (int32_t *)o[0], (int32_t *)o[1], (float *)o[2], (float *)o[3], nf);
+        return dvbs2hip_sync_frame_synchronize_dev(h, (const float *)i[0], (int32_t *)o[0], (int32_t *)o[1], (float *)o[2], (float *)o[3], nf);
+    });
+}
+
+int dvbs2hip_sync_frame_synchronize2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, const float *cor_PLSC, int32_t *DEL, int32_t *FLG,
+                                     float *TRI, float *Y_N2, int32_t F)
+{
+    if (h && (!cor_SOF || !cor_PLSC)) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    return sfm_host(h, X_N1, cor_SOF, cor_PLSC, DEL, FLG, TRI, Y_N2, F);
+}
+
+int dvbs2hip_sync_frame_synchronize(dvbs2hip_t *h, const float *X_N1, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F)
+{
+    return sfm_host(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, Y_N2, F);
+}
+
+// ------------------------------------------------------------------ N4: fine frequency / phase synchronizers (sockets X_N1, FRQ, PHS, Y_N2)
+static int sff_call(dvbs2hip_t *h, bool lr, bool host, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!X_N1 || !Y_N2) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    const int n = h->pl_frame;
+    if (n <= 1530) return fail(h, DVBS2HIP_EUNSUPPORTED, "the PL frame holds no pilot block");
+    if (lr && !h->d_lr_R) { DEV_ALLOC_CHK(h, &h->d_lr_R, 2 * sizeof(float)); HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float), h->stream)); }
+    if (lr && !h->lr_err_host) {
+        HIPCHK(h, hipHostMalloc((void **)&h->lr_err_host, dvbs2hip_handle::LR_SLOTS * sizeof(uint32_t), hipHostMallocMapped));
+        for (int i = 0; i < dvbs2hip_handle::LR_SLOTS; i++) h->lr_err_host[i] = 0u;
+        HIPCHK(h, hipHostGetDevicePointer((void **)&h->lr_err_dev, h->lr_err_host, 0));
+    }
+    const size_t nb = sizeof(float) * 2 * (size_t)n * F, nf4 = sizeof(float) * (size_t)F;
+    void *tmp;
+    // the estimates: the pilot-phase synchronizer's buffer is its own; an L&R call takes the next of LR_SLOTS slots (estimates + error word).  A slot whose last
+    // device-form call has not been looked at yet (LR_SLOTS such calls without a dvbs2hip_synchronize between them) is looked at first -- one stream synchronization,
+    // and only then -- so that its repair never meets estimates of another launch
+    const int slot = lr ? h->lr_next : 0;
+    if (lr) {
+        if (h->lr_slot[slot].pending) { HIPCHK(h, hipStreamSynchronize(h->stream)); if ((r = lr_check_recover(h, slot))) return r; }
+        h->lr_next = (slot + 1) % dvbs2hip_handle::LR_SLOTS;
+    }
+    if ((r = ensure(h, lr ? B_LR_TMP0 + slot : B_SFF_TMP, sizeof(float) * 4 * (size_t)F, &tmp))) return r;
+    auto launch = [&](const float *x, float *frq, float *phs, float *y) {
+        Timer tm(h, DVBS2HIP_K_MISC);
+        if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, h->lr_alpha, h->lr_err_dev + slot, h->stream));
+        else HIPCHK(h, sff_fp_launch(x, y, (float *)tmp, frq, phs, n, F, h->stream));
+        if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host; }
+        return 0;
+    };
+    if (!host) return launch(X_N1, FRQ, PHS, Y_N2);
+    if ((r = lr_check_all(h))) return r;          // (the host form reuses B_IN / B_OUT: nothing of an earlier device-form call is left pending behind it)
+    void *dout = nullptr;
+    r = host_call(h, F, false, {{X_N1, B_IN, nb}}, {{Y_N2, B_OUT, nb}, {FRQ, B_SFF_OUT, nf4, 0, true}, {PHS, B_SFF_OUT, nf4, nf4, true}},
+                  [&](void *const *i, void *const *o, int) { dout = o[0]; return launch((const float *)i[0], (float *)o[1], (float *)o[2], (float *)o[0]); });
+    if (r) return r;
+    if (lr && h->lr_err_host && ((volatile uint32_t *)h->lr_err_host)[slot]) {      // timeout in the fused L&R launch: rotate again, copy again
+        if ((r = lr_check_recover(h, slot))) return r;
+        HIPCHK(h, hipMemcpyAsync(Y_N2, dout, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+int dvbs2hip_sync_lr_synchronize(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F) { return sff_call(h, true, true, X_N1, FRQ, PHS, Y_N2, F); }
+int dvbs2hip_sync_lr_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F) { return sff_call(h, true, false, X_N1, FRQ, PHS, Y_N2, F); }
+int dvbs2hip_sync_freq_phase_synchronize(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F) { return sff_call(h, false, true, X_N1, FRQ, PHS, Y_N2, F); }
+int dvbs2hip_sync_freq_phase_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F) { return sff_call(h, false, false, X_N1, FRQ, PHS, Y_N2, F); }
+
+int dvbs2hip_sync_lr_set_alpha(dvbs2hip_t *h, float alpha)
+{
+    if (!h) return DVBS2HIP_EINVAL;
+    h->lr_alpha = alpha;
+    return 0;
+}
+
+int dvbs2hip_sync_lr_timeouts(dvbs2hip_t *h, int32_t *n)
+{
+    if (!h || !n) return DVBS2HIP_EINVAL;
+    *n = h->lr_timeouts;
+    return 0;
+}
+
+int dvbs2hip_sync_lr_reset(dvbs2hip_t *h)          // Synchronizer_Luise_Reggiannini_DVBS2_aib::_reset, .cpp:170-176
+{
+    int r = enter(h); if (r) return r;
+    if (h->d_lr_R) HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float), h->stream));
+    return 0;
+}
+
+int dvbs2hip_sync_frame_get_metric(dvbs2hip_t *h, float *max_corr, int32_t *packet_flag)
+{
+    if (!h || !max_corr || !packet_flag) return DVBS2HIP_EINVAL;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, DVBS2HIP_EHIP, "hipSetDevice failed");
+    int r = sfm_ready(h); if (r) return r;
+    float m = 0.f;
+    HIPCHK(h, hipMemcpyAsync(&m, h->sfm.metric, sizeof m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *max_corr = m; *packet_flag = m > h->sfm.trigger ? 1 : 0;                      // _get_metric / _get_packet_flag, .hpp:59-60
+    return 0;
+}
+
+}  // extern "C"
