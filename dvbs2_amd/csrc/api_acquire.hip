@@ -116,7 +116,29 @@ int dvbs2hip_sync_timing_reset(dvbs2hip_t *h)
 {
     int r0 = enter(h); if (r0) return r0;
     if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    h->stm.act = false;                                                 // Synchronizer_timing::reset, Synchronizer_timing.hxx:109
     return stm_alloc(h, h->stm.S);
+}
+
+int dvbs2hip_sync_timing_set_type(dvbs2hip_t *h, int32_t type, int32_t hold_size)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (type != DVBS2HIP_STM_FAST && type != DVBS2HIP_STM_ULTRA)
+        return fail(h, DVBS2HIP_EINVAL, "'type' has to be DVBS2HIP_STM_FAST or DVBS2HIP_STM_ULTRA ('type' = " + std::to_string(type) + ").");
+    if (type == DVBS2HIP_STM_ULTRA && hold_size <= 4)                   // Synchronizer_Gardner_ultra_osf2.cpp:27
+        return fail(h, DVBS2HIP_EINVAL, "'hold_size' has to be greater than 4 ('hold_size' = " + std::to_string(hold_size) + ").");
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    h->stm.type = type;
+    if (type == DVBS2HIP_STM_ULTRA) h->stm.hold = hold_size;
+    h->stm.act = false;
+    return stm_alloc(h, h->stm.S);
+}
+
+int dvbs2hip_sync_timing_set_act(dvbs2hip_t *h, int32_t act)
+{
+    int r0 = enter(h); if (r0) return r0;
+    h->stm.act = act != 0;
+    return 0;
 }
 
 int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t F)
@@ -126,7 +148,10 @@ int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float
     auto &T = h->stm;
     if ((r = stm_begin(h, F, "synchronize"))) return r;
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, stm_sync_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.kp, T.ki, h->stream));
+    if (T.type == DVBS2HIP_STM_ULTRA)
+        HIPCHK(h, stm_ultra_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.hold, T.act ? 1 : 0, T.kp, T.ki, h->stream));
+    else
+        HIPCHK(h, stm_sync_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.kp, T.ki, h->stream));
     T.st_cur ^= 1;
     return 0;
 }
@@ -390,6 +415,8 @@ static int sfc_dev(dvbs2hip_t *h)
 static int smf_check(dvbs2hip_t *h, int F)
 {
     int r = stm_check(h, F); if (r) return r;
+    if (h->stm.type == DVBS2HIP_STM_ULTRA)
+        return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse-frequency loop steps Synchronizer_Gardner_fast_osf2: with DVBS2HIP_STM_ULTRA it is not provided (dvbs2hip_sync_timing_set_type)");
     if (h->fir_T != SMF_TAPS) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse-frequency loop carries the 81-tap matched filter: the handle's filter has another length");
     if (!h->fir_sym) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse-frequency loop folds the matched filter over its symmetry (taps[i] == taps[80 - i]): the handle's taps are not symmetric");
     return 0;
@@ -435,6 +462,7 @@ int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h)                         // Synchr
     int r = dvbs2hip_sync_coarse_reset(h); if (r) return r;
     if (h->stm.S == 1) { if (h->fir_T > 1 && h->d_hist[h->hist_cur]) HIPCHK(h, hipMemsetAsync(h->d_hist[h->hist_cur], 0, sizeof(float) * 2 * (size_t)(h->fir_T - 1), h->stream)); }
     else if (h->sfc.hist[h->sfc.hist_cur]) HIPCHK(h, hipMemsetAsync(h->sfc.hist[h->sfc.hist_cur], 0, SMF_HIST_BYTES * (size_t)h->sfc.n_alloc, h->stream));
+    h->stm.act = false;
     return stm_alloc(h, h->stm.S);
 }
 

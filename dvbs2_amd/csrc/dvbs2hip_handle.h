@@ -133,6 +133,8 @@ struct dvbs2hip_handle {
         float damping = 0.70710678f, nbw = 5e-5f, dg = 2.f;     // Factory/Module/Synchronizer_timing/Synchronizer_timing.hpp:28-30
         float kp = 0.f, ki = 0.f;
         int S = 1;                                              // streams per call (dvbs2hip_sync_timing_set_streams)
+        int type = DVBS2HIP_STM_FAST, hold = 101;               // dvbs2hip_sync_timing_set_type: the loop and, for ULTRA, its hold size (--stm-hold-size)
+        bool act = false;                                       // Synchronizer_timing::set_act: ULTRA holds only while it is set
         int Fs = 0;                                             // frames per stream of every call since the last reset (0: not yet fixed)
         int n_alloc = 0;                                        // streams the buffers below hold
         dvbs2::StmState *st[2] = {nullptr, nullptr};

@@ -326,6 +326,9 @@ struct StmState {
     int32_t is_strobe, prev_is_strobe;
 };
 hipError_t stm_sync_launch(const float *X, float *Y, int32_t *B, float *MU, const StmState *st_in, StmState *st_out, int S, int Fs, int N, float kp, float ki, hipStream_t s);
+// the held loop (k_timing_ultra.hip): the same state, a wave per stream; H the hold size, act as Synchronizer_timing::set_act
+hipError_t stm_ultra_launch(const float *X, float *Y, int32_t *B, float *MU, const StmState *st_in, StmState *st_out, int S, int Fs, int N, int H, int act, float kp, float ki,
+                            hipStream_t s);
 hipError_t stm_extract_launch(const float *Y1, const int32_t *B1, float *Y2, int32_t *UFW, int32_t *RDY, const float *c_in, const int32_t *n_in, float *c_out, int32_t *n_out,
                               int32_t *uf, int S, int Fs, int N, long long cap, hipStream_t s);
 hipError_t chn_delay_launch(const float *X, float *Y, const float *h_in, float *h_out, long long H, long long T, float b0, float b1, float b2, hipStream_t s);

@@ -245,6 +245,17 @@ class Dvbs2Hip:
     def sync_timing_reset(self):
         self._chk(self.L.dvbs2hip_sync_timing_reset(self.h))
 
+    STM_TYPES = {"FAST": 0, "ULTRA": 1}                       # DVBS2HIP_STM_FAST, DVBS2HIP_STM_ULTRA
+
+    def sync_timing_set_type(self, stm_type="FAST", hold_size=101):
+        """the loop behind sync_timing_synchronize: "FAST", or "ULTRA" (Synchronizer_Gardner_ultra_osf2) with its hold size; clears every stream's state"""
+        code = self.STM_TYPES[stm_type] if isinstance(stm_type, str) else int(stm_type)
+        self._chk(self.L.dvbs2hip_sync_timing_set_type(self.h, code, int(hold_size)))
+
+    def sync_timing_set_act(self, act=True):
+        """Synchronizer_timing::set_act: ULTRA holds mu over its hold blocks while it is set (no effect on FAST); sync_timing_reset clears it"""
+        self._chk(self.L.dvbs2hip_sync_timing_set_act(self.h, 1 if act else 0))
+
     def sync_timing_synchronize(self, X_N1):
         """Gardner timing loop over F frames of pl_frame * 2 complex samples -> (Y_N1, B_N1, MU[F])"""
         X, F = self._frames(X_N1, 4 * self.pl_frame, np.float32)

@@ -1,7 +1,7 @@
 """`dvbs2_rx` work-alike: raw IQ file -> [--wl-phases: the waiting and learning phases on the head of the file, dvbs2_amd/acquire.py, which find the carrier offset with the
 coarse frequency loop on the GPU (--wl-frames L1 L2 L3: frames of learning phases 1 to 3, default 150 150 200; --wl-wait-max: frames after which the waiting phase gives up,
 default 2000); without it the offset is handed in by --coarse-freq] -> front gain stage (Multiplier_AGC, RX/main_sched.cpp:197)
--> coarse frequency shift (:198) -> matched filter (a5) -> symbol timing (--stm-type: extraction at a known phase, or FAST, the Gardner loop on the GPU, :202-204) -> gain stage
+-> coarse frequency shift (:198) -> matched filter (a5) -> symbol timing (--stm-type: extraction at a known phase, or FAST / ULTRA, the Gardner loop on the GPU, :202-204) -> gain stage
 (main_sched.cpp:205) -> frame synchronizer (N4) -> pilot-aided phase synchronizer (N4, optional) -> fused RX chain (a7 .. a8) -> monitor against the source pattern -> sink.  It serves
 files made by `dvbs2_amd.tx` / `dvbs2_amd.ch` (or by the reference's dvbs2_tx / dvbs2_ch without timing or frequency
 offsets): README.md:151-169 of the reference.
@@ -47,8 +47,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
                                                                    "phase (the frequency shift) with this as its loop's frozen estimate (--wl-phases runs the loop instead)")
-    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="symbol timing: PERFECT takes every osf-th sample from --timing-offset (the default here); "
-                                                                                     "FAST runs the reference's Gardner loop (Synchronizer_Gardner_fast_osf2) on the GPU")
+    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST", "ULTRA"], help="symbol timing: PERFECT takes every osf-th sample from --timing-offset (the default here); "
+                                                                                     "FAST runs the reference's Gardner loop (Synchronizer_Gardner_fast_osf2) on the GPU; "
+                                                                                     "ULTRA its held form (Synchronizer_Gardner_ultra_osf2), a wave per stream")
+    ap.add_argument("--stm-hold-size", type=int, default=101, help="ULTRA: samples per hold block; mu is held over all but the last four of them once the loop holds")
+    ap.add_argument("--stm-learn-frames", type=int, default=None, help="ULTRA: frames the whole loop runs on every sample before it starts to hold (the reference's learning phases, "
+                                                                       "then set_act(true), main_sched.cpp:655); default: the sum of --wl-frames")
     ap.add_argument("--stm-df", type=float, default=0.5 ** 0.5, help="damping factor of the Gardner loop filter")
     ap.add_argument("--stm-nbw", type=float, default=5e-5, help="normalized bandwidth of the Gardner loop filter")
     ap.add_argument("--stm-dg", type=float, default=2.0, help="detector gain of the Gardner loop filter")
@@ -74,12 +78,21 @@ def run(args, out=sys.stdout) -> dict:
     wl = getattr(args, "wl_phases", False)
     if wl and args.coarse_freq:
         raise ValueError("--wl-phases finds the carrier offset itself: it excludes --coarse-freq")
+    ultra = args.stm_type == "ULTRA"
+    if wl and ultra:
+        raise ValueError("--wl-phases steps FAST's detector inside the coarse-frequency loop: with --stm-type ULTRA it is not provided (use --stm-learn-frames)")
     if wl and not fast:
         raise ValueError("--wl-phases runs the Gardner loop: it needs --stm-type FAST")
-    if fast:
+    if fast or ultra:
         if osf != 2:
-            raise ValueError("--stm-type FAST is the Gardner loop at two samples per symbol (--shp-osf 2)")
+            raise ValueError("--stm-type %s is the Gardner loop at two samples per symbol (--shp-osf 2)" % args.stm_type)
         rx.sync_timing_set_params(args.stm_df, args.stm_nbw, args.stm_dg)
+    learn = 0
+    if ultra:
+        rx.sync_timing_set_type("ULTRA", args.stm_hold_size)
+        learn = sum(args.wl_frames) if args.stm_learn_frames is None else args.stm_learn_frames
+        fast = True                                                                # the same two tasks from here on
+    fed = 0                                                                        # frames the timing loop has taken
     rcv = RadioUserBinary(n * osf, input_filename=args.rad_rx_file_path, auto_reset=not args.rad_rx_no_loop, n_frames=F)
     snk = SinkUserBinary(args.snk_path, mc.K_bch) if args.snk_path else None
     off = args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf          # two group delays of grp_delay * osf samples
@@ -106,7 +119,10 @@ def run(args, out=sys.stdout) -> dict:
                 _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)                  # sync_coarse_f: RX/main_sched.cpp:198-200
             if fast:
                 # sync_timing: synchronize -> extract (RX/main_sched.cpp:202-204); a call that underflows holds its symbols for the next one
+                if ultra and fed >= learn:
+                    rx.sync_timing_set_act(True)                                     # the learning frames are over: the loop holds (calls are whole: the first one at or past N)
                 y, b, _ = rx.sync_timing_synchronize(rx.filter(x, n_frames=F).reshape(F, -1))
+                fed += F
                 y2, _, rdy = rx.sync_timing_extract(y, b)
                 if not rdy[0]:
                     continue

@@ -14,7 +14,7 @@
 //      The binding lines between the modules built here are the reference's, character for character (marked "main_sched.cpp:NNN").
 //      The sample-serial loops in between are out of scope and are played by stand-ins defined below:
 //      sync_coarse_f = identity (no frequency offset), sync_timing = decimation by osf at the even phase (perfect timing) unless
-//      --stm-type FAST binds Synchronizer_timing_hip (the Gardner loop, main_sched.cpp:202-204; a batch whose extract underflows stops
+//      --stm-type FAST (or ULTRA [--stm-hold-size H] [--stm-learn-frames N]: the held loop, holding after N frames) binds Synchronizer_timing_hip (the Gardner loop, main_sched.cpp:202-204; a batch whose extract underflows stops
 //      behind it, as the reference's sequence does at processing_aborted, and the payload source only advances for batches that go through); the source is a file of the sent payloads delayed by --src-delay frames (the frame synchronizer's latency;
 //      what Filter_buffered_delay does in the TX_RX mains).
 //      --wl-phases (with --stm-type FAST) runs the reference's waiting and learning phases on the head of the file first (main_sched.cpp:407-635): Synchronizer_step_mf_hip,
@@ -134,7 +134,8 @@ public:
 
 static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite, float alpha, const std::string &implem, const std::string &in_path,
                                     const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq, bool stm_fast,
-                                    bool wl_phases = false, int wl1 = 150, int wl2 = 150, int wl3 = 200, int wl_wait_max = 2000)
+                                    bool wl_phases = false, int wl1 = 150, int wl2 = 150, int wl3 = 200, int wl_wait_max = 2000, bool stm_ultra = false, int stm_hold_size = 101,
+                                    int stm_learn_frames = 500)
 {
     using namespace module;
     const int osf = 2;
@@ -148,7 +149,7 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     sync_coarse_f->set_curr_freq(coarse_freq);                                                                                          // (what the reference's loop would have settled on: --coarse-freq)
     std::unique_ptr<Filter_FIR_hip>              matched_flt  (new Filter_FIR_hip(ctx, N_pl * osf));
     std::unique_ptr<Sync_timing_perfect>         sync_timing_p(stm_fast ? nullptr : new Sync_timing_perfect(N_pl * osf, osf, F));   // the default: a known phase
-    std::unique_ptr<Synchronizer_timing_hip<>>   sync_timing  (stm_fast ? new Synchronizer_timing_hip<>(ctx) : nullptr);               // --stm-type FAST (Gardner)
+    std::unique_ptr<Synchronizer_timing_hip<>>   sync_timing  (stm_fast ? new Synchronizer_timing_hip<>(ctx, 0.70710678f, 5e-5f, 2.f, stm_ultra ? DVBS2HIP_STM_ULTRA : DVBS2HIP_STM_FAST, stm_hold_size) : nullptr);   // --stm-type FAST | ULTRA (Gardner)
     std::unique_ptr<Synchronizer_frame_hip<>>    sync_frame   (new Synchronizer_frame_hip<>(ctx));
     std::unique_ptr<Scrambler_PL_hip>            pl_scrambler (new Scrambler_PL_hip(ctx));
     std::unique_ptr<Synchronizer_freq_fine_hip<>> sync_fine_lr(new Synchronizer_freq_fine_hip<>(ctx, true));
@@ -272,7 +273,10 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
         }
         std::printf("# wl phases | waiting %d | learning %d + %d frames | coarse frequency %.6f\n", waited, learned12, m, (double)sync_coarse_f->get_estimated_freq());
     }
+    size_t fed = 0;                                                       // frames the timing synchronizer has taken
     while (in.read(reinterpret_cast<char *>(rx_samples.data()), rx_samples.size() * sizeof(float))) {
+        if (stm_ultra && fed >= (size_t)stm_learn_frames) sync_timing->set_act(true);      // the learning frames are over: the loop holds (main_sched.cpp:655)
+        fed += (size_t)F;
         try {
             seq.exec_step();
         } catch (const spu::tools::processing_aborted &) {
@@ -294,7 +298,8 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
     monitor->get(fra, be, fe);
     std::printf("# %s F=%d %s ite=%d matched-filter graph | batches %zu | FRA %llu BE %llu FE %llu\n", modcod.c_str(), F, implem.c_str(), n_ite, batches,
                 (unsigned long long)fra, (unsigned long long)be, (unsigned long long)fe);
-    if (stm_fast) std::printf("# timing FAST | batches aborted by an underflow %zu\n", aborted);
+    if (stm_ultra) std::printf("# timing ULTRA hold size %d, holding after %d frames | batches aborted by an underflow %zu\n", stm_hold_size, stm_learn_frames, aborted);
+    else if (stm_fast) std::printf("# timing FAST | batches aborted by an underflow %zu\n", aborted);
     std::printf("# probes | BE %d FE %d BER %.3e FER %.3e | DEL %d FLG %d\n", prb_bfer_be.last, prb_bfer_fe.last, (double)prb_bfer_ber.last, (double)prb_bfer_fer.last,
                 (*sync_frame)[sfm::sck::synchronize2::DEL].get_dataptr<int>()[F - 1], (*sync_frame)[sfm::sck::synchronize2::FLG].get_dataptr<int>()[F - 1]);
     return 0;
@@ -306,8 +311,8 @@ int main(int argc, char **argv)
     int F = 1, n_ite = 50, src_delay = 0, mon_skip = 0;
     float coarse_freq = 0.f;
     float alpha = 1.0f;
-    bool frame_sync = false, matched = false, stm_fast = false, wl_phases = false;
-    int wl[3] = {150, 150, 200}, wl_wait_max = 2000;
+    bool frame_sync = false, matched = false, stm_fast = false, stm_ultra = false, wl_phases = false;
+    int wl[3] = {150, 150, 200}, wl_wait_max = 2000, stm_hold_size = 101, stm_learn_frames = -1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; exit(2); } return argv[++i]; };
@@ -327,14 +332,23 @@ int main(int argc, char **argv)
         else if (a == "--wl-wait-max") wl_wait_max = std::stoi(next());
         else if (a == "--frame-sync") frame_sync = true;
         else if (a == "--matched-filter") matched = true;
-        else if (a == "--stm-type") { const std::string t = next(); if (t != "PERFECT" && t != "FAST") { std::cerr << "--stm-type: PERFECT or FAST\n"; return 2; } stm_fast = t == "FAST"; }
+        else if (a == "--stm-type") {
+            const std::string t = next();
+            if (t != "PERFECT" && t != "FAST" && t != "ULTRA") { std::cerr << "--stm-type: PERFECT, FAST or ULTRA\n"; return 2; }
+            stm_ultra = t == "ULTRA"; stm_fast = t != "PERFECT";        // stm_fast: the timing module is bound; stm_ultra: as Synchronizer_Gardner_ultra_osf2
+        }
+        else if (a == "--stm-hold-size") stm_hold_size = std::stoi(next());
+        else if (a == "--stm-learn-frames") stm_learn_frames = std::stoi(next());      // ULTRA: frames before set_act(true); default: the sum of --wl-frames
         else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
     try {
-        if (stm_fast && !matched) { std::cerr << "--stm-type FAST needs --matched-filter (the timing synchronizer runs on the samples)\n"; return 2; }
+        if (stm_fast && !matched) { std::cerr << "--stm-type FAST | ULTRA needs --matched-filter (the timing synchronizer runs on the samples)\n"; return 2; }
+        if (stm_ultra && stm_hold_size <= 4) { std::cerr << "--stm-hold-size has to be greater than 4\n"; return 2; }
+        if (stm_ultra && wl_phases) { std::cerr << "--wl-phases steps FAST's detector inside the coarse-frequency loop: with --stm-type ULTRA it is not provided (use --stm-learn-frames)\n"; return 2; }
+        if (stm_learn_frames < 0) stm_learn_frames = wl[0] + wl[1] + wl[2];
         if (wl_phases && (!stm_fast || coarse_freq != 0.f)) { std::cerr << "--wl-phases needs --matched-filter --stm-type FAST and excludes --coarse-freq\n"; return 2; }
         if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq, stm_fast, wl_phases,
-                                                     wl[0], wl[1], wl[2], wl_wait_max);
+                                                     wl[0], wl[1], wl[2], wl_wait_max, stm_ultra, stm_hold_size, stm_learn_frames);
         auto ctx = std::make_shared<module::Context>(modcod, F, n_ite, alpha, true, 0, implem);
         ctx->pin_sockets = true;            // the sockets below live until the modules go: pin them for overlapped PCIe copies
         module::Scrambler_PL_hip pl_scrambler(ctx);

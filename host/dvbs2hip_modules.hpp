@@ -313,14 +313,17 @@ private:
 // replaces Synchronizer_timing<B,R> of type FAST = Synchronizer_Gardner_fast_osf2 (Factory/Module/Synchronizer_timing/Synchronizer_timing.cpp:91-96, the factory defaults
 // damping sqrt(0.5), normalized bandwidth 5e-5, detector gain 2: Synchronizer_timing.hpp:28-30; bound RX/main_sched.cpp:202-204).  One stream, N_in = 2 * pl_frame * 2 floats per
 // frame.  extract throws processing_aborted when the stream underflows, as Synchronizer_timing.hxx:302 does: the symbols wait in the handle for the next call.
+// type DVBS2HIP_STM_ULTRA with a hold size is Synchronizer_Gardner_ultra_osf2 (--stm-type ULTRA --stm-hold-size); set_act as Synchronizer_timing::set_act (main_sched.cpp:655).
 template <typename B = int, typename R = float>
 class Synchronizer_timing_hip : public Module_hip {
 public:
-    Synchronizer_timing_hip(std::shared_ptr<Context> c, R damping_factor = (R)0.70710678f, R normalized_bandwidth = (R)5e-5, R detector_gain = (R)2)
+    Synchronizer_timing_hip(std::shared_ptr<Context> c, R damping_factor = (R)0.70710678f, R normalized_bandwidth = (R)5e-5, R detector_gain = (R)2,
+                            int type = DVBS2HIP_STM_FAST, int hold_size = 101)
     : Module_hip(std::move(c), "Synchronizer_timing_hip")
     {
         static_assert(sizeof(B) == 4 && sizeof(R) == 4, "B = int32, R = float");
         DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_set_params(ctx->h, (float)damping_factor, (float)normalized_bandwidth, (float)detector_gain));
+        if (type != DVBS2HIP_STM_FAST) DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_set_type(ctx->h, type, hold_size));
         const size_t N_in = 4 * (size_t)ctx->sz.pl_frame_sym;
         {
             auto &t = create_task("synchronize");
@@ -355,6 +358,7 @@ public:
     spu::runtime::Socket &operator[](stm::sck::synchronize s) { return (*tasks[(size_t)stm::tsk::synchronize])[(size_t)s]; }
     spu::runtime::Socket &operator[](stm::sck::extract s) { return (*tasks[(size_t)stm::tsk::extract])[(size_t)s]; }
     void reset() { DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_reset(ctx->h)); }
+    void set_act(bool act) { DVBS2HIP_CHK(ctx, dvbs2hip_sync_timing_set_act(ctx->h, act ? 1 : 0)); }
 };
 
 // replaces Synchronizer_freq_coarse<R> in the transmission phase: its task `synchronize` is the frequency shift alone (Synchronizer_freq_coarse_DVBS2_aib.cpp:43-50 ->

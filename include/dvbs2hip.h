@@ -365,7 +365,7 @@ int dvbs2hip_extract_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx
  * -- src/common/Module/Synchronizer/Synchronizer_timing/Synchronizer_Gardner_fast_osf2.cpp:35-198 (Farrow interpolator Filter_Farrow_ccr_naive.hxx, Gardner detector,
  * PI loop filter, NCO), Synchronizer_timing.hxx:48-78 (tasks and sockets), :189-201 (MU), :243-304 (extract: the carry buffer and the underflow count); built by
  * Factory/Module/Synchronizer_timing/Synchronizer_timing.cpp:91-96, bound RX/main_sched.cpp:202-204.  Frames of pl_frame * osf complex samples; osf = 2 only (the handle's
- * fir_osf; the NORMAL, ULTRA and osf != 2 variants are not provided: DVBS2HIP_EUNSUPPORTED).  Results are bit for bit the CPU twin's (tests/timing_twin.c), which restates the reference's order of operations.
+ * fir_osf; the NORMAL and osf != 2 variants are not provided: DVBS2HIP_EUNSUPPORTED; ULTRA is chosen with dvbs2hip_sync_timing_set_type, below).  Results are bit for bit the CPU twin's (tests/timing_twin.c), which restates the reference's order of operations.
  * Streams: the n_frames frames of a call are S streams of n_frames / S consecutive frames each, stream s = frames [s F/S, (s+1) F/S) (F a multiple of S, else EINVAL).
  * S = 1 (the default) is the reference's module: one stream.  Every stream keeps its own loop state and carry buffer in the handle between calls; one lane runs one stream.
  * F/S is fixed by the first call after a reset (or set_streams): a call with another F/S returns EINVAL until dvbs2hip_sync_timing_reset.
@@ -386,6 +386,24 @@ int dvbs2hip_sync_timing_synchronize(dvbs2hip_t *h, const float *X_N1, float *Y_
 int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t n_frames);
 int dvbs2hip_sync_timing_extract(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t n_frames);
 int dvbs2hip_sync_timing_extract_dev(dvbs2hip_t *h, const float *Y_N1, const int32_t *B_N1, float *Y_N2, int32_t *UFW, int32_t *RDY, int32_t n_frames);
+/* The held Gardner loop (the reference's `--stm-type ULTRA --stm-hold-size H`)
+ * replaces: Synchronizer_Gardner_ultra_osf2::_synchronize -- Synchronizer_timing/Synchronizer_Gardner_ultra_osf2.cpp:59-133 (hold blocks, control samples, the tail),
+ * .hxx:58-120 (TED_update, loop_filter, interpolation_control), :341-351 (the gains: FAST's formula); Synchronizer_timing::set_act, Synchronizer_timing.hxx:109 and
+ * RX/main_sched.cpp:655; built by Factory/Module/Synchronizer_timing/Synchronizer_timing.cpp from --stm-type ULTRA, --stm-hold-size (default 101).
+ * set_type chooses the loop behind dvbs2hip_sync_timing_synchronize / _dev: DVBS2HIP_STM_FAST (the default; hold_size is ignored) or DVBS2HIP_STM_ULTRA with its hold size
+ * (hold_size <= 4 with ULTRA: DVBS2HIP_EINVAL, the reference's assertion).  It clears every stream's state like set_streams and refuses an open capture.  The sockets, the
+ * streams rule and the F/S rule are those above; extract is the same task behind either loop.  A handle that never calls set_type is the FAST loop.
+ * set_act: while it is clear (after create, set_type, reset: Synchronizer_timing::reset clears it) ULTRA runs the whole loop on every sample; once it is set -- the reference
+ * sets it when its learning phases are over -- every frame is cut into N / hold_size blocks (N = pl_frame * osf; the blocks start over at every frame) that hold mu over
+ * their first hold_size - 4 samples and run the whole loop on the last four, and a tail of N mod hold_size samples with the whole loop.  The flag is a launch argument: a
+ * captured graph keeps the value it was recorded with.  It is stored for FAST too and has no effect there.
+ * One wave runs one stream, its lanes across the held samples of a block (S streams are S waves).  Results are bit for bit the CPU twin's (tests/timing_ultra_twin.c).
+ * In the _dev form X_N1 and Y_N1 must not overlap under ULTRA: the kernel reads a sample's three predecessors from X_N1 after it has written their outputs.
+ * Not provided yet: ULTRA's detector inside the coarse-frequency loop.  While the type is ULTRA dvbs2hip_sync_step_mf_synchronize / _dev return DVBS2HIP_EUNSUPPORTED (the
+ * loop's sample-by-sample `step` with ULTRA's forms of TED_update and loop_filter is a later change). */
+enum { DVBS2HIP_STM_FAST = 0, DVBS2HIP_STM_ULTRA = 1 };
+int dvbs2hip_sync_timing_set_type(dvbs2hip_t *h, int32_t type, int32_t hold_size);
+int dvbs2hip_sync_timing_set_act(dvbs2hip_t *h, int32_t act);
 /* The channel's three delay tasks, in the order CH/main.cpp:60-62 and TX_RX/main.cpp:215-218 bind them (test-signal side)
  * replaces: Filter_buffered_delay::filter ((floor(D) - 2) / N frames), Variable_delay_cc_naive::filter ((floor(D) - 2 + N) % N samples), Filter_Farrow_ccr_naive::filter
  * (mu = D - floor(D)) -- built DVBS2.cpp:520-544 from --chn-max-delay D >= 2 (DVBS2.cpp:128-133).  The two delay lines start at zero and compose to one of floor(D) - 2 samples;

@@ -18,7 +18,8 @@ are the first --skip frames, which are not counted.
 
 --chn-max-freq-shift f puts the channel's frequency shift (dvbs2hip_channel_freq_shift, f cycles per sample) behind the delay tasks, and --wl-phases runs the reference's
 waiting and learning phases (dvbs2_amd/acquire.py: the coarse-frequency loop on the GPU, 150 / 150 / 200 frames) on the head of the stream before anything is counted; the
-transmission phase then shifts by the frozen estimate (dvbs2hip_sync_coarse_synchronize) in front of the matched filter.  --wl-phases needs --stm-type FAST."""
+transmission phase then shifts by the frozen estimate (dvbs2hip_sync_coarse_synchronize) in front of the matched filter.  --wl-phases needs --stm-type FAST.
+--stm-type ULTRA --stm-hold-size H is the held loop (dvbs2hip_sync_timing_set_type): the whole loop for --stm-learn-frames frames, then it holds."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,9 +38,14 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     delay_D = getattr(a, "chn_max_delay", None)
     fast = getattr(a, "stm_type", "PERFECT") == "FAST"
     freq_shift = getattr(a, "chn_max_freq_shift", None)
+    ultra = getattr(a, "stm_type", "PERFECT") == "ULTRA"
     wl = getattr(a, "wl_phases", False)
     if wl and not fast:
         raise ValueError("--wl-phases needs --stm-type FAST")
+    if ultra:
+        rx.sync_timing_set_type("ULTRA", a.stm_hold_size)                              # the held loop: the whole loop for --stm-learn-frames frames, then set_act
+        fast = True
+    fed = 0
     if delay_D is not None:
         rx.channel_set_delay(delay_D)
     if freq_shift is not None:
@@ -78,6 +84,9 @@ def run_point(Rx, P, mc, ebn0, variant, a):
             _, _, noisy = rx.sync_coarse_synchronize(noisy, n_frames=F)                 # sync_coarse_f with the loop's frozen estimate (main_sched.cpp:198)
         mf = rx.filter(noisy, n_frames=F).reshape(-1, 2)
         if fast:
+            if ultra and fed >= a.stm_learn_frames:
+                rx.sync_timing_set_act(True)
+            fed += F
             y, b, _ = rx.sync_timing_synchronize(mf.reshape(F, -1))
             y2, _, rdy = rx.sync_timing_extract(y, b)
             if not rdy[0]:
@@ -113,7 +122,7 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     return st
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mod-cod", default="QPSK-S_8/9")
     ap.add_argument("--ebn0", type=float, nargs="+", default=[3.7, 3.8])
@@ -129,11 +138,17 @@ def main():
     ap.add_argument("--est-perfect", action="store_true", help="the channel's sigma instead of the M2M4 estimate (the reference's 16APSK trace: --est-type PERFECT)")
     ap.add_argument("--agc", action="store_true", help="the reference's two gain stages in the loop (front_agc on the samples, mult_agc on the symbols)")
     ap.add_argument("--chn-max-delay", type=float, default=None, help="the reference channel's delay tasks with this D (>= 2) behind the shaping filter")
-    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST"], help="PERFECT: timing by genie; FAST: the Gardner loop on the GPU")
+    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST", "ULTRA"], help="PERFECT: timing by genie; FAST: the Gardner loop on the GPU; ULTRA: its held form")
+    ap.add_argument("--stm-hold-size", type=int, default=101, help="ULTRA: samples per hold block")
+    ap.add_argument("--stm-learn-frames", type=int, default=500, help="ULTRA: frames before the loop starts to hold (the learning phases' 150 + 150 + 200)")
     ap.add_argument("--chn-max-freq-shift", type=float, default=None, help="the reference channel's frequency shift (cycles per sample) behind the delay tasks")
     ap.add_argument("--wl-phases", action="store_true", help="run the waiting and learning phases (the coarse-frequency loop on the GPU) before anything is counted")
     ap.add_argument("--json", default=None)
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     from dvbs2_amd.receiver import Dvbs2Hip
     from dvbs2_amd import params as P
     mc = P.get_modcod(a.mod_cod)
