@@ -1,5 +1,6 @@
 // C ABI, acquisition: symbol timing (stm_*), coarse frequency and the step_mf loop (sfc_*, smf_*), the channel's delay and frequency shift.
 #include "dvbs2hip_handle.h"
+#include "gardner_loop.h"
 
 using namespace dvbs2;
 
@@ -200,11 +201,7 @@ int dvbs2hip_channel_set_delay(dvbs2hip_t *h, float D)
     if (!(D >= 2.f) || !(D <= 16777216.f)) return fail(h, DVBS2HIP_EINVAL, "Argument 'max_delay' has to be greater than 2.");     // DVBS2.cpp:129-133 (and at most 2^24 samples here)
     if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
     auto &C = h->chn;
-    const float mu = D - floorf(D);                                     // DVBS2.cpp:522
-    const float half_mu = 0.5f * mu, half_mu_square = half_mu * mu;    // Filter_Farrow_ccr_naive::set_mu
-    C.b[0] = half_mu_square - half_mu;
-    C.b[1] = 1.0f - half_mu - half_mu_square;
-    C.b[2] = mu + half_mu - half_mu_square;
+    farrow_taps(D - floorf(D), C.b[0], C.b[1], C.b[2]);                 // mu: DVBS2.cpp:522
     const long long H = (long long)floorf(D) + 1;                       // (floor(D) - 2) samples of delay line + 3 of the Farrow filter
     if (H > C.H || !C.hist[0]) {
         HIPCHK(h, hipStreamSynchronize(h->stream));

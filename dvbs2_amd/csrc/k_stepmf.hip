@@ -11,14 +11,14 @@
 //
 // Arithmetic contract (tests/stepmf_twin.c, bit for bit): the rotation takes cos / sin of the exact turn fraction (k n mod 1e6) / 1e6 from nco_turn.h -- nu = k 1e-6 and n
 // are whole numbers, so nothing is rounded before the polynomial; the matched filter uses the taps' symmetry, 41 products summed in the order the twin's header states; the
-// timing step is Synchronizer_Gardner_fast_osf2::step as written (it differs from the _synchronize body of k_timing.hip in TED_update's cases and in (NCO + 1) - W).
+// timing step is Synchronizer_Gardner_fast_osf2::step as written: gardner_step of gardner_loop.h, which lists how it differs from the _synchronize body of k_timing.hip.
 //
 // LDS: a lane's row holds its filter window and its tile in one run of float2: [80 samples of history | T new samples].  Sample i of the tile is rotated in place at
 // row[80 + i], the filter reads row[i .. i + 80], and the interpolated output goes to row[i], which no later sample reads.  After the tile the last 80 samples move to the
 // front.  The row stride is SMF_ROW = 125 float2 = 250 dwords: twice an odd number, so the 32 lanes that one ds_read_b64 serves together (bank = dword mod 64) and the 16
 // that a ds_write_b64 serves together (mod 32) all sit on different banks on their lane-private walks.  64 x 125 x 8 B = 62.5 KB + 512 B of strobe masks per workgroup of
 // one wave: two workgroups per CU (160 KB).  Nothing of the window lives in scratch.
-#include "dvbs2hip_internal.h"
+#include "gardner_loop.h"
 #include "nco_turn.h"
 
 namespace dvbs2 {
@@ -26,15 +26,6 @@ namespace dvbs2 {
 constexpr int SMF_T = 44;                          // samples per stream and tile
 constexpr int SMF_H = 80;                          // the matched filter's memory: taps - 1
 constexpr int SMF_ROW = SMF_H + SMF_T + 1;         // float2 per LDS row: 125, odd
-
-__device__ __forceinline__ void smf_farrow_taps(float mu, float &b0, float &b1, float &b2)
-{
-    const float half_mu = 0.5f * mu;
-    const float half_mu_square = half_mu * mu;
-    b0 = half_mu_square - half_mu;
-    b1 = 1.0f - half_mu - half_mu_square;
-    b2 = mu + half_mu - half_mu_square;
-}
 
 __global__ void __launch_bounds__(64)
 stepmf_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__restrict__ B, float *__restrict__ MU, float *__restrict__ FRQ, float *__restrict__ PHS,
@@ -55,12 +46,8 @@ stepmf_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__rest
     SfcState cf = {};
     int carry_cplx = 0;
     if (act) { st = st_in[s]; cf = cf_in[s]; carry_cplx = ccnt[s] / 2; }          // Synchronizer_timing::get_delay() = outbuf_cur_sz / 2
-    float h1r = st.h[0], h1i = st.h[1], h2r = st.h[2], h2i = st.h[3], h3r = st.h[4], h3i = st.h[5];
-    float t0r = st.ted[0], t0i = st.ted[1], t1r = st.ted[2], t1i = st.ted[3];
-    float mu = st.mu, nco = st.nco, lfp = st.lf_prev_in, lfo = st.lf_output, lsr = st.last[0], lsi = st.last[1];
-    int is = st.is_strobe, prev = st.prev_is_strobe;
-    float b0, b1, b2;
-    smf_farrow_taps(mu, b0, b1, b2);
+    GardnerRegs g;
+    g.load(st);
     int n = cf.n, nu_k = cf.nu_k, curr_idx = cf.curr_idx;
     int kmod = nu_k % NCO_TURN_UNITS;
     if (kmod < 0) kmod += NCO_TURN_UNITS;
@@ -120,32 +107,9 @@ stepmf_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__rest
                 const float mr = ((ar[0] + ar[1]) + (ar[2] + ar[3])) + taps[40] * mid.x;
                 const float mi = ((ai[0] + ai[1]) + (ai[2] + ai[3])) + taps[40] * mid.y;
                 // 3. the timing step
-                const float yr = (h3r * b0 + h2r * b1) + (h1r * b2 + mr * b0);
-                const float yi = (h3i * b0 + h2i * b1) + (h1i * b2 + mi * b0);
-                h3r = h2r; h3i = h2i; h2r = h1r; h2i = h1i; h1r = mr; h1i = mi;
-                const int strobe = is;
-                if (strobe) { lsr = yr; lsi = yi; }
-                const int hist = is + 2 * prev;
-                float e = 0.0f;
-                if (hist == 1) {
-                    e = t1r * (t0r - yr) + t1i * (t0i - yi);
-                    t0r = 0.f; t0i = 0.f; t1r = yr; t1i = yi;
-                } else if (hist != 0) {
-                    t0r = t1r; t0i = t1i; t1r = yr; t1i = yi;
-                }
-                const float vp = e * kp;
-                const float vi = lfp + e * ki;
-                lfp = vi;
-                lfo = vp + vi;
-                const float W = lfo + 0.5f;
-                prev = is;
-                is = nco < W ? 1 : 0;
-                if (is) {
-                    mu = nco / W;
-                    smf_farrow_taps(mu, b0, b1, b2);
-                    nco = nco + 1.0f;
-                }
-                nco = nco - W;
+                float yr, yi;
+                g.farrow(mr, mi, yr, yi);
+                const int strobe = gardner_step(g, yr, yi, kp, ki);
                 w[0] = make_float2(yr, yi);
                 m |= (unsigned long long)strobe << i;
                 // 4. the PLL
@@ -179,8 +143,8 @@ stepmf_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__rest
                     curr_idx = (curr_idx + 1) % pl_frame;
                 }
                 if (--to_frame_end == 0) {
-                    const size_t g = (size_t)s * Fs + frame;
-                    MU[g] = mu; FRQ[g] = cf.est; PHS[g] = 0.f;
+                    const size_t o = (size_t)s * Fs + frame;
+                    MU[o] = g.mu; FRQ[o] = cf.est; PHS[o] = 0.f;
                     frame++;
                     to_frame_end = N;
                 }
@@ -206,10 +170,7 @@ stepmf_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__rest
     for (int r = 0; r < rows; r++)
         for (int j = lane; j < SMF_H; j += 64) hist_out[(size_t)(s0 + r) * SMF_H + j] = tile[r * SMF_ROW + j];
     if (act) {
-        st.h[0] = h1r; st.h[1] = h1i; st.h[2] = h2r; st.h[3] = h2i; st.h[4] = h3r; st.h[5] = h3i;
-        st.ted[0] = t0r; st.ted[1] = t0i; st.ted[2] = t1r; st.ted[3] = t1i;
-        st.mu = mu; st.nco = nco; st.lf_prev_in = lfp; st.lf_output = lfo; st.last[0] = lsr; st.last[1] = lsi;
-        st.is_strobe = is; st.prev_is_strobe = prev;
+        g.store(st);
         st_out[s] = st;
         cf.n = n; cf.nu_k = nu_k; cf.curr_idx = curr_idx;
         cf_out[s] = cf;

@@ -1,17 +1,8 @@
 // Symbol-timing recovery (the reference's `--stm-type FAST` synchronizer, Gardner's detector at two samples per symbol) and the channel's delay tasks.
 //
-// Synchronizer_Gardner_fast_osf2::_synchronize (src/common/Module/Synchronizer/Synchronizer_timing/Synchronizer_Gardner_fast_osf2.cpp:35-166), restated:
-//   every complex input sample x goes through the 4-tap piecewise-parabolic Farrow interpolator (Filter_Farrow_ccr_naive.hxx, set_mu / step):
-//       b0 = mu^2/2 - mu/2,  b1 = 1 - mu/2 - mu^2/2,  b2 = mu + mu/2 - mu^2/2,  b3 = b0;   y = (b0 x[n-3] + b1 x[n-2]) + (b2 x[n-1] + b3 x[n])
-//   then, with h = is_strobe + 2 prev_is_strobe (the strobe history):
-//       h == 1 (a strobe): B = 1, Gardner's error e = T1 . (T0 - y) on the TED buffer {T0, T1}, the PI loop filter lf_prev_in += e ki, lf_output = lf_prev_in + e kp,
-//                          the TED buffer shifts in y
-//       h == 2           : B = 0, the TED buffer shifts in y (the mid-symbol sample), lf_output = lf_prev_in
-//       h == 3 (stuffing): B = 1, T0 = 0, T1 = y, lf_output = lf_prev_in
-//       h == 0 (skipping): B = 0, lf_output = lf_prev_in
-//   and in every case the NCO: W = lf_output + 1/2, prev_is_strobe = is_strobe, is_strobe = NCO < W; a strobe sets mu = NCO / W (the Farrow taps follow) and
-//   NCO += 1 - W, otherwise NCO -= W.  B is written for both reals of the sample (the int socket B_N1), MU per frame is mu after the frame (Synchronizer_timing.hxx:189-201).
-// The chain from one sample to the next is NCO compare -> mu = NCO / W (correctly rounded) -> taps -> Farrow -> TED -> PI -> W: sample-serial within a stream.
+// stm_sync_kernel is Synchronizer_Gardner_fast_osf2::_synchronize (src/common/Module/Synchronizer/Synchronizer_timing/Synchronizer_Gardner_fast_osf2.cpp:35-166): per input sample the
+// Farrow step and gardner_synchronize of gardner_loop.h, which states the loop.  B is written for both reals of the sample (the int socket B_N1), MU per frame is mu after the
+// frame (Synchronizer_timing.hxx:189-201).  The loop is sample-serial within a stream.
 // Across streams it is not: one lane per stream, a wave carries 64 streams.  The frames of a call are stream-major (stream s = frames [s F/S, (s+1) F/S)), so a lane's samples
 // are one contiguous run and the 64 runs of a wave lie a stream apart; tiles of 64 samples of the 64 streams go through LDS (coalesced row loads, a lane-private walk over its own
 // row, the outputs written back into the same slots, coalesced row stores).  The tile's loads and the LDS reads do not depend on the chain.
@@ -24,7 +15,7 @@
 // (Filter_buffered_delay, (floor(D) - 2) / N frames) and the integer delay (Variable_delay_cc_naive, (floor(D) - 2) mod N samples) are zero-initialised delay lines whose
 // composition is one delay line of floor(D) - 2 samples; the fractional delay is the same Farrow interpolator with mu = D - floor(D) fixed.  Data-parallel: a thread per sample,
 // floor(D) + 1 samples of history kept between calls.
-#include "dvbs2hip_internal.h"
+#include "gardner_loop.h"
 
 namespace dvbs2 {
 
@@ -32,15 +23,6 @@ constexpr int STM_T = 64;                    // samples per stream and tile
 constexpr int STM_ROW = 2 * STM_T + 1;       // floats per LDS row: odd, so that the 64 lanes' walks hit 64 different banks
 constexpr int STM_FROW = STM_T + 1;          // strobe flags per LDS row
 constexpr int STM_EX_THREADS = 256;
-
-__device__ __forceinline__ void farrow_taps(float mu, float &b0, float &b1, float &b2)
-{
-    const float half_mu = 0.5f * mu;
-    const float half_mu_square = half_mu * mu;
-    b0 = half_mu_square - half_mu;
-    b1 = 1.0f - half_mu - half_mu_square;
-    b2 = mu + half_mu - half_mu_square;
-}
 
 __global__ void __launch_bounds__(64)
 stm_sync_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__restrict__ B, float *__restrict__ MU, const StmState *__restrict__ st_in,
@@ -57,12 +39,8 @@ stm_sync_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__re
 
     StmState st = {};
     if (act) st = st_in[s];
-    float h1r = st.h[0], h1i = st.h[1], h2r = st.h[2], h2i = st.h[3], h3r = st.h[4], h3i = st.h[5];
-    float t0r = st.ted[0], t0i = st.ted[1], t1r = st.ted[2], t1i = st.ted[3];
-    float mu = st.mu, nco = st.nco, lfp = st.lf_prev_in, lfo = st.lf_output, lsr = st.last[0], lsi = st.last[1];
-    int is = st.is_strobe, prev = st.prev_is_strobe;
-    float b0, b1, b2;
-    farrow_taps(mu, b0, b1, b2);
+    GardnerRegs g;
+    g.load(st);
     int to_frame_end = N;                                       // samples left in the current frame
     int frame = 0;
     float *row = tile + lane * STM_ROW;
@@ -81,38 +59,14 @@ stm_sync_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__re
         __syncthreads();
         if (act) {
             for (int i = 0; i < cnt; i++) {
-                const float xr = row[2 * i], xi = row[2 * i + 1];
-                const float yr = (b0 * h3r + b1 * h2r) + (b2 * h1r + b0 * xr);
-                const float yi = (b0 * h3i + b1 * h2i) + (b2 * h1i + b0 * xi);
-                h3r = h2r; h3i = h2i; h2r = h1r; h2i = h1i; h1r = xr; h1i = xi;
-                const int hist = is + 2 * prev;
-                if (hist == 1) {
-                    const float e = t1r * (t0r - yr) + t1i * (t0i - yi);
-                    lfp = lfp + e * ki;
-                    lfo = lfp + e * kp;
-                    t0r = t1r; t0i = t1i; t1r = yr; t1i = yi;
-                } else {
-                    lfo = lfp;
-                    if (hist == 2) { t0r = t1r; t0i = t1i; t1r = yr; t1i = yi; }
-                    else if (hist == 3) { t0r = 0.f; t0i = 0.f; t1r = yr; t1i = yi; }
-                }
-                const int strobe = hist & 1;
-                if (strobe) { lsr = yr; lsi = yi; }
-                const float W = lfo + 0.5f;
-                prev = is;
-                is = nco < W ? 1 : 0;
-                if (is) {
-                    mu = nco / W;
-                    farrow_taps(mu, b0, b1, b2);
-                    nco = nco + (1.0f - W);
-                } else {
-                    nco = nco - W;
-                }
+                float yr, yi;
+                g.farrow(row[2 * i], row[2 * i + 1], yr, yi);
+                const int strobe = gardner_synchronize(g, yr, yi, kp, ki);
                 row[2 * i] = yr;
                 row[2 * i + 1] = yi;
                 frow[i] = strobe;
                 if (--to_frame_end == 0) {
-                    MU[(size_t)s * Fs + frame] = mu;
+                    MU[(size_t)s * Fs + frame] = g.mu;
                     frame++;
                     to_frame_end = N;
                 }
@@ -131,10 +85,7 @@ stm_sync_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, int2 *__re
         __syncthreads();
     }
     if (act) {
-        st.h[0] = h1r; st.h[1] = h1i; st.h[2] = h2r; st.h[3] = h2i; st.h[4] = h3r; st.h[5] = h3i;
-        st.ted[0] = t0r; st.ted[1] = t0i; st.ted[2] = t1r; st.ted[3] = t1i;
-        st.mu = mu; st.nco = nco; st.lf_prev_in = lfp; st.lf_output = lfo; st.last[0] = lsr; st.last[1] = lsi;
-        st.is_strobe = is; st.prev_is_strobe = prev;
+        g.store(st);
         st_out[s] = st;
     }
 }
@@ -237,7 +188,7 @@ chn_delay_kernel(const float2 *__restrict__ X, float2 *__restrict__ Y, const flo
     auto c = [&](long long j) { return j < H ? h_in[j] : X[j - H]; };
     if (n < T) {
         const float2 c0 = c(n), c1 = c(n + 1), c2 = c(n + 2), c3 = c(n + 3);
-        Y[n] = make_float2((b0 * c0.x + b1 * c1.x) + (b2 * c2.x + b0 * c3.x), (b0 * c0.y + b1 * c1.y) + (b2 * c2.y + b0 * c3.y));
+        Y[n] = make_float2(farrow_sum(b0, b1, b2, c0.x, c1.x, c2.x, c3.x), farrow_sum(b0, b1, b2, c0.y, c1.y, c2.y, c3.y));
     }
     if (n < H) h_out[n] = c(T + n);
 }

@@ -2,18 +2,12 @@
 -ffp-contract=off, loaded with ctypes) driven stream by stream like libdvbs2hip's S-stream calls and sharing the timing twin's state (tests/timing_ref.py), and a
 pure-Python restatement in numpy float32 scalars, written module by module from the reference's sources, that pins the twin itself."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import timing_ref as TR
+import twin_build
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "stepmf_twin.c")
-_HDR = os.path.join(_HERE, "..", "dvbs2_amd", "csrc", "nco_turn.h")
 _lib = None
 
 
@@ -25,15 +19,7 @@ class SfcState(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        src = open(_SRC, "rb").read() + open(_HDR, "rb").read()
-        d = os.path.join(tempfile.gettempdir(), "dvbs2_stepmf_twin_%d" % os.getuid())
-        os.makedirs(d, exist_ok=True)
-        so = os.path.join(d, "stepmf_twin_%s.so" % hashlib.sha1(src).hexdigest()[:12])
-        if not os.path.exists(so):
-            cc = os.environ.get("CC", "cc")
-            subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so + ".tmp", _SRC, "-lm"])
-            os.replace(so + ".tmp", so)
-        L = C.CDLL(so)
+        L = twin_build.load("stepmf_twin.c")
         fp, vp, i, f = C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_float
         L.twin_pll_gains.argtypes = [i, f, f, fp, fp]
         L.twin_pilots.argtypes = [vp, i, vp, i]

@@ -15,17 +15,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include "../dvbs2_amd/csrc/nco_turn.h"
+#include "gardner_twin.h"
 
 #define MF_T 81
-
-/* the timing loop's state, as tests/timing_twin.c and libdvbs2hip's StmState lay it out (all zeros = reset) */
-typedef struct {
-    float h[6];           /* Farrow history x[n-1], x[n-2], x[n-3] (re, im) */
-    float ted[4];         /* TED_buffer[0], TED_buffer[1] (re, im) */
-    float mu, nco, lf_prev_in, lf_output;
-    float last[2];        /* last_symbol */
-    int is_strobe, prev_is_strobe;
-} twin_stm;
 
 /* the coarse synchronizer's state (Synchronizer_freq_coarse_DVBS2_aib + its Multiplier_sine_ccc_naive) and Synchronizer_step_mf_cc::last_delay */
 typedef struct {
@@ -62,16 +54,6 @@ void twin_pilots(const unsigned char *seq, int n_seq, float *P, int n_p)
         P[2 * i] = (float)cos(a);
         P[2 * i + 1] = (float)sin(a);
     }
-}
-
-/* Filter_Farrow_ccr_naive::set_mu, Module/Filter/Filter_FIR/Farrow/Filter_Farrow_ccr_naive.hxx (b[3] = b[0]) */
-static void farrow_taps(float mu, float b[3])
-{
-    float half_mu = 0.5f * mu;
-    float half_mu_square = half_mu * mu;
-    b[0] = half_mu_square - half_mu;
-    b[1] = 1.0f - half_mu - half_mu_square;
-    b[2] = mu + half_mu - half_mu_square;
 }
 
 /* Synchronizer_freq_coarse_DVBS2_aib::update_phase, .cpp:57-92, with Multiplier_sine_ccc_naive::set_nu (Module/Multiplier/Sine/Multiplier_sine_ccc_naive.cpp:43-51) */
@@ -150,12 +132,8 @@ void twin_stepmf(twin_stm *st, twin_sfc *c, float *ring, const float *taps, cons
             const float mr = ((ar[0] + ar[1]) + (ar[2] + ar[3])) + taps[40] * wi[80];
             const float mi = ((ai[0] + ai[1]) + (ai[2] + ai[3])) + taps[40] * wi[81];
             /* sync_timing->step, Synchronizer_Gardner_fast_osf2.hxx:8-21: farrow_flt.step */
-            const float r0 = st->h[4] * b[0], i0 = st->h[5] * b[0];
-            const float r1 = st->h[2] * b[1], i1 = st->h[3] * b[1];
-            const float r2 = st->h[0] * b[2], i2 = st->h[1] * b[2];
-            const float r3 = mr * b[0], i3 = mi * b[0];
-            const float yr = (r0 + r1) + (r2 + r3), yi = (i0 + i1) + (i2 + i3);
-            st->h[4] = st->h[2]; st->h[5] = st->h[3]; st->h[2] = st->h[0]; st->h[3] = st->h[1]; st->h[0] = mr; st->h[1] = mi;
+            float yr, yi;
+            farrow(st, b, mr, mi, &yr, &yi);
             Y[2 * k] = yr; Y[2 * k + 1] = yi;
             const int strobe = st->is_strobe;
             B[2 * k] = strobe; B[2 * k + 1] = strobe;

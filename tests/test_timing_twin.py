@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import timing_ref as TR
+import twin_build
 from dvbs2_amd import params as P
 
 PL = P.get_modcod("QPSK-S_8/9").pl_frame          # 8370 symbols, 16740 complex samples per frame at osf = 2
@@ -108,3 +109,21 @@ def test_channel_delay_twin_is_a_delay_line_then_the_farrow_filter():
     ch2 = TR.ChannelDelay(4.5)
     parts = np.concatenate([ch2(x[:6]), ch2(x[6:800]), ch2(x[800:])])      # history across calls, including a call shorter than the history
     assert np.array_equal(whole, parts)
+
+
+def test_twin_cache_key_covers_the_included_headers(tmp_path):
+    """an edit to a header a twin includes must not reuse the cached shared object: on copies of timing_twin.c and gardner_twin.h, a comment appended to the header
+    changes the key and the file the loader builds"""
+    import os
+    import shutil
+    here = os.path.dirname(os.path.abspath(__file__))
+    for f in ("timing_twin.c", "gardner_twin.h"):
+        shutil.copy(os.path.join(here, f), tmp_path / f)
+    src = str(tmp_path / "timing_twin.c")
+    assert twin_build.sources(src) == [src, str(tmp_path / "gardner_twin.h")]
+    k0, so0 = twin_build.key(src), twin_build.load(src)._name
+    assert k0 == twin_build.key(os.path.join(here, "timing_twin.c")) and k0 in so0
+    with open(tmp_path / "gardner_twin.h", "a") as f:
+        f.write("/* edited */\n")
+    k1, so1 = twin_build.key(src), twin_build.load(src)._name
+    assert k1 != k0 and so1 != so0 and k1 in so1

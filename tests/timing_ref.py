@@ -2,15 +2,11 @@
 the system compiler and -O2 -ffp-contract=off, loaded with ctypes) driven stream by stream like libdvbs2hip's S-stream calls, and a pure-Python restatement of
 the Gardner loop in numpy float32 scalars that pins the twin itself."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "timing_twin.c")
+import twin_build
+
 _lib = None
 
 
@@ -22,15 +18,7 @@ class StmState(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        src = open(_SRC, "rb").read()
-        d = os.path.join(tempfile.gettempdir(), "dvbs2_timing_twin_%d" % os.getuid())
-        os.makedirs(d, exist_ok=True)
-        so = os.path.join(d, "timing_twin_%s.so" % hashlib.sha1(src).hexdigest()[:12])
-        if not os.path.exists(so):
-            cc = os.environ.get("CC", "cc")
-            subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so + ".tmp", _SRC, "-lm"])
-            os.replace(so + ".tmp", so)
-        L = C.CDLL(so)
+        L = twin_build.load("timing_twin.c")
         fp, ip, vp = C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p
         L.twin_gains.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp]
         L.twin_synchronize.argtypes = [C.POINTER(StmState), vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float]

@@ -5,35 +5,10 @@
  */
 #include <math.h>
 #include <string.h>
-
-/* one stream's state (all zeros = Synchronizer_timing::reset, Synchronizer_timing.hxx:96-111, and Synchronizer_Gardner_fast_osf2::_reset, .cpp:168-186) */
-typedef struct {
-    float h[6];           /* Farrow history x[n-1], x[n-2], x[n-3] (re, im) */
-    float ted[4];         /* TED_buffer[0], TED_buffer[1] (re, im) */
-    float mu, nco, lf_prev_in, lf_output;
-    float last[2];        /* last_symbol */
-    int is_strobe, prev_is_strobe;
-} twin_stm;
-
-/* Filter_Farrow_ccr_naive::set_mu, Module/Filter/Filter_FIR/Farrow/Filter_Farrow_ccr_naive.hxx (b[3] = b[0]) */
-static void farrow_taps(float mu, float b[3])
-{
-    float half_mu = 0.5f * mu;
-    float half_mu_square = half_mu * mu;
-    b[0] = half_mu_square - half_mu;
-    b[1] = 1.0f - half_mu - half_mu_square;
-    b[2] = mu + half_mu - half_mu_square;
-}
+#include "gardner_twin.h"
 
 /* Synchronizer_Gardner_fast_osf2::set_loop_filter_coeffs, Module/Synchronizer/Synchronizer_timing/Synchronizer_Gardner_fast_osf2.cpp:188-198 */
-void twin_gains(float damping, float nbw, float dg, float *kp, float *ki)
-{
-    float K0 = -1.f;
-    float theta = nbw / 2.0f / (damping + 0.25f / damping);
-    float d = (1.f + 2.f * damping * theta + theta * theta) * K0 * dg;
-    *kp = (4.f * damping * theta) / d;
-    *ki = (4.f * theta * theta) / d;
-}
+void twin_gains(float damping, float nbw, float dg, float *kp, float *ki) { loop_gains(damping, nbw, dg, kp, ki); }
 
 /* Synchronizer_timing::synchronize (Synchronizer_timing.hxx:189-201) over n_frames frames of N complex samples of ONE stream,
  * each frame Synchronizer_Gardner_fast_osf2::_synchronize (.cpp:35-166) with the Farrow step of Filter_Farrow_ccr_naive.hxx */
@@ -47,12 +22,8 @@ void twin_synchronize(twin_stm *st, const float *X, float *Y, int *B, float *MU,
             const float xr = X[2 * k], xi = X[2 * k + 1];
             const int hist = st->is_strobe + st->prev_is_strobe * 2;          /* strobe_history, .cpp:44,68 */
             /* farrow_flt.step (in every branch; the set_mu(mu) of branch 3, .cpp:116, sets the taps they already hold) */
-            const float r0 = st->h[4] * b[0], i0 = st->h[5] * b[0];
-            const float r1 = st->h[2] * b[1], i1 = st->h[3] * b[1];
-            const float r2 = st->h[0] * b[2], i2 = st->h[1] * b[2];
-            const float r3 = xr * b[0], i3 = xi * b[0];
-            const float yr = (r0 + r1) + (r2 + r3), yi = (i0 + i1) + (i2 + i3);
-            st->h[4] = st->h[2]; st->h[5] = st->h[3]; st->h[2] = st->h[0]; st->h[3] = st->h[1]; st->h[0] = xr; st->h[1] = xi;
+            float yr, yi;
+            farrow(st, b, xr, xi, &yr, &yi);
             Y[2 * k] = yr; Y[2 * k + 1] = yi;
             const int strobe = hist == 1 || hist == 3;
             B[2 * k] = strobe; B[2 * k + 1] = strobe;

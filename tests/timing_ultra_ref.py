@@ -3,17 +3,12 @@
 block a vectorised Farrow filter and vectorised detector errors, two in-order float32 accumulations, four control steps -- which proves that decomposition to be the serial
 algorithm bit for bit.  Also the inputs the CPU and the GPU tests share, with the coverage condition they assert on the twin's trace."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import timing_ref as TR
+import twin_build
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "timing_ultra_twin.c")
 _lib = None
 
 StmState = TR.StmState          # the same layout: the library keeps one state per stream for both loops
@@ -22,15 +17,7 @@ StmState = TR.StmState          # the same layout: the library keeps one state p
 def lib():
     global _lib
     if _lib is None:
-        src = open(_SRC, "rb").read()
-        d = os.path.join(tempfile.gettempdir(), "dvbs2_timing_twin_%d" % os.getuid())
-        os.makedirs(d, exist_ok=True)
-        so = os.path.join(d, "timing_ultra_twin_%s.so" % hashlib.sha1(src).hexdigest()[:12])
-        if not os.path.exists(so):
-            cc = os.environ.get("CC", "cc")
-            subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so + ".tmp", _SRC, "-lm"])
-            os.replace(so + ".tmp", so)
-        L = C.CDLL(so)
+        L = twin_build.load("timing_ultra_twin.c")
         fp, vp = C.POINTER(C.c_float), C.c_void_p
         L.twin_ultra_gains.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp]
         L.twin_ultra_synchronize.argtypes = [C.POINTER(StmState), vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp]

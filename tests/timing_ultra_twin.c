@@ -10,48 +10,10 @@
  * sample is a control sample.  (Synchronizer_Gardner_ultra_osf2.cpp:59-133.)
  */
 #include <string.h>
+#include "gardner_twin.h"
 
-/* one stream's state, the layout of timing_twin.c's twin_stm and of the library's StmState; all zeros = reset (.cpp:322-339).  `prev_is_strobe` is the low bit of the
- * reference's strobe_history: the is_strobe the detector saw last.  `last` is not maintained by _synchronize. */
-typedef struct {
-    float h[6];           /* Farrow history x[n-1], x[n-2], x[n-3] (re, im) */
-    float ted[4];         /* TED_buffer[0], TED_buffer[1] (re, im) */
-    float mu, nco, lf_prev_in, lf_output;
-    float last[2];
-    int is_strobe, prev_is_strobe;
-} twin_stm;
-
-/* Filter_Farrow_ccr_naive::set_mu (b[3] = b[0]) */
-static void farrow_taps(float mu, float b[3])
-{
-    float half_mu = 0.5f * mu;
-    float half_mu_square = half_mu * mu;
-    b[0] = half_mu_square - half_mu;
-    b[1] = 1.0f - half_mu - half_mu_square;
-    b[2] = mu + half_mu - half_mu_square;
-}
-
-/* set_loop_filter_coeffs, .cpp:341-351 (in float, as the reference's R = float build evaluates it): the same formula as FAST */
-void twin_ultra_gains(float damping, float nbw, float dg, float *kp, float *ki)
-{
-    float K0 = -1.f;
-    float theta = nbw / 2.0f / (damping + 0.25f / damping);
-    float d = (1.f + 2.f * damping * theta + theta * theta) * K0 * dg;
-    *kp = (4.f * damping * theta) / d;
-    *ki = (4.f * theta * theta) / d;
-}
-
-/* one Farrow output: Filter_Farrow_ccr_naive::step, and Filter_FIR_ccr::_filter with four taps (Filter_FIR_ccr.cpp:68-142), which sums in the same order */
-static void farrow(twin_stm *st, const float b[3], float xr, float xi, float *yr, float *yi)
-{
-    const float r0 = st->h[4] * b[0], i0 = st->h[5] * b[0];
-    const float r1 = st->h[2] * b[1], i1 = st->h[3] * b[1];
-    const float r2 = st->h[0] * b[2], i2 = st->h[1] * b[2];
-    const float r3 = xr * b[0], i3 = xi * b[0];
-    *yr = (r0 + r1) + (r2 + r3);
-    *yi = (i0 + i1) + (i2 + i3);
-    st->h[4] = st->h[2]; st->h[5] = st->h[3]; st->h[2] = st->h[0]; st->h[3] = st->h[1]; st->h[0] = xr; st->h[1] = xi;
-}
+/* set_loop_filter_coeffs, .cpp:341-351: the same formula as FAST */
+void twin_ultra_gains(float damping, float nbw, float dg, float *kp, float *ki) { loop_gains(damping, nbw, dg, kp, ki); }
 
 /* TED_update (.hxx:58-87) then loop_filter (.hxx:89-100); returns the strobe history of the sample */
 static int detector_and_filter(twin_stm *st, float yr, float yi, float kp, float ki)
