@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from .iqfile import ProcessingAborted
+from .rx_sequence import RxSequence
 
 
 def acquire(rx, receive, n_frames=1, osf=2, learn1=150, learn2=150, learn3=200, nbw_wait=1e-4, nbw1=1e-4, nbw2=5e-5, damping=0.5 ** 0.5, wait_max=2000, agc=True,
@@ -28,23 +29,18 @@ def acquire(rx, receive, n_frames=1, osf=2, learn1=150, learn2=150, learn3=200, 
     res = dict(acquired=False, flag=False, frames=spent, freq=None, nu=None)
     fed_back = np.zeros(F, np.int32)                                  # Feedbacker: what memorize took at the last call, produce gives at this one (zeros at first)
 
-    def front(x):
-        x = np.asarray(x, np.float32).reshape(F, -1)
-        return rx.agc(x, n_frames=F, output_energy=1.0 / osf).reshape(F, -1) if agc else x
-
-    def symbols_to_frame_sync(y2):
-        sym = rx.agc(y2, n_frames=F, output_energy=1.0).reshape(F, -1) if agc else y2
-        return rx.sync_frame_synchronize(sym, with_flags=True)
+    # the gain stages and the frame synchronizer of every phase, and learning phase 3, are the transmission phase's (rx_sequence.py)
+    seq = RxSequence(rx, F, osf, agc=agc, coarse=True, timing="FAST", fine=True, lr=True)
 
     def wl12_call():
         """one run of the waiting / learning 1-2 sequence -> the packet flag after it (None: the sequence was cut short by an underflow)"""
         nonlocal fed_back
-        x = front(receive())
+        x = seq.front(receive())
         _, _, _, y, b = rx.sync_step_mf_synchronize(fed_back, x)
         y2, _, rdy = rx.sync_timing_extract(y, b)
         if not rdy[0]:
             return None                                               # (the reference's sequence aborts here; the Feedbacker keeps what it had)
-        delay, flags, _, _ = symbols_to_frame_sync(y2)
+        delay, flags, _, _ = seq.align(y2)
         fed_back = np.array(delay, np.int32)
         return bool(flags[-1])
 
@@ -77,19 +73,13 @@ def acquire(rx, receive, n_frames=1, osf=2, learn1=150, learn2=150, learn3=200, 
         # ---------------------------------------------------------- learning 3
         m = 0
         while m < learn3:
-            x = front(receive())
-            _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)
-            y, b, _ = rx.sync_timing_synchronize(rx.filter(x, n_frames=F).reshape(F, -1))
-            y2, _, rdy = rx.sync_timing_extract(y, b)
+            sym = seq.symbols(seq.front(receive()))
             m += F
             spent["learning3"] += F
             if on_frames:
                 on_frames("learning3", F)
-            if not rdy[0]:
-                continue
-            _, _, _, aligned = symbols_to_frame_sync(y2)
-            _, _, desc = rx.sync_lr_synchronize(rx.pl_descramble(aligned))
-            rx.sync_freq_phase_synchronize(desc)
+            if sym is not None:
+                seq.fine_sync(seq.align(sym)[3])
         res["acquired"] = True
     except ProcessingAborted:
         pass

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import params as P
 from .iqfile import ProcessingAborted, RadioUserBinary
+from .rx_sequence import LockTracker, RxSequence, add_timing_args
 from .srcfile import SinkUserBinary, load_src
 
 
@@ -47,12 +48,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
                                                                    "phase (the frequency shift) with this as its loop's frozen estimate (--wl-phases runs the loop instead)")
-    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST", "ULTRA"], help="symbol timing: PERFECT takes every osf-th sample from --timing-offset (the default here); "
-                                                                                     "FAST runs the reference's Gardner loop (Synchronizer_Gardner_fast_osf2) on the GPU; "
-                                                                                     "ULTRA its held form (Synchronizer_Gardner_ultra_osf2), a wave per stream")
-    ap.add_argument("--stm-hold-size", type=int, default=101, help="ULTRA: samples per hold block; mu is held over all but the last four of them once the loop holds")
-    ap.add_argument("--stm-learn-frames", type=int, default=None, help="ULTRA: frames the whole loop runs on every sample before it starts to hold (the reference's learning phases, "
-                                                                       "then set_act(true), main_sched.cpp:655); default: the sum of --wl-frames")
+    add_timing_args(ap, learn_default=None)
     ap.add_argument("--stm-df", type=float, default=0.5 ** 0.5, help="damping factor of the Gardner loop filter")
     ap.add_argument("--stm-nbw", type=float, default=5e-5, help="normalized bandwidth of the Gardner loop filter")
     ap.add_argument("--stm-dg", type=float, default=2.0, help="detector gain of the Gardner loop filter")
@@ -91,15 +87,14 @@ def run(args, out=sys.stdout) -> dict:
     if ultra:
         rx.sync_timing_set_type("ULTRA", args.stm_hold_size)
         learn = sum(args.wl_frames) if args.stm_learn_frames is None else args.stm_learn_frames
-        fast = True                                                                # the same two tasks from here on
-    fed = 0                                                                        # frames the timing loop has taken
     rcv = RadioUserBinary(n * osf, input_filename=args.rad_rx_file_path, auto_reset=not args.rad_rx_no_loop, n_frames=F)
     snk = SinkUserBinary(args.snk_path, mc.K_bch) if args.snk_path else None
-    off = args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf          # two group delays of grp_delay * osf samples
-    tail = np.zeros((0, 2), np.float32)                                            # matched-filter samples not yet turned into symbols
-    skip = off
+    # the task sequence (rx_sequence.py); --wl-phases: the frozen coarse estimate in front, and L&R as learning phase 3 has trained it, for what that estimate leaves
+    seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq or wl), timing=args.stm_type, learn_frames=learn,
+                     timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf,      # two group delays of grp_delay * osf samples
+                     fine=bool(args.sync_fine or wl), lr=wl)
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
-    stable = 0                                                                     # frames since the synchronizer's delay last moved
+    lock = LockTracker()
     try:
         if wl:
             from .acquire import acquire
@@ -107,63 +102,23 @@ def run(args, out=sys.stdout) -> dict:
             st["acquisition"] = acq = acquire(rx, rcv.receive, n_frames=F, osf=osf, learn1=l1, learn2=l2, learn3=l3, wait_max=args.wl_wait_max, agc=not args.no_agc)
             print("# waiting %d | learning %d + %d + %d frames | packet flag %s | coarse frequency %s" % (
                 acq["frames"]["waiting"], acq["frames"]["learning1"], acq["frames"]["learning2"], acq["frames"]["learning3"], acq["flag"], acq["freq"]), file=out)
-        while not args.max_frames or st["frames"] < args.max_frames:
+        while not args.max_frames or lock.frames < args.max_frames:
             try:
                 x = rcv.receive()
             except ProcessingAborted:
                 break
-            x = x.astype(np.float32, copy=False)
-            if not args.no_agc:
-                x = rx.agc(x, n_frames=F, output_energy=1.0 / osf)                  # front_agc: DVBS2.cpp:660-664
-            if args.coarse_freq or wl:
-                _, _, x = rx.sync_coarse_synchronize(x, n_frames=F)                  # sync_coarse_f: RX/main_sched.cpp:198-200
-            if fast:
-                # sync_timing: synchronize -> extract (RX/main_sched.cpp:202-204); a call that underflows holds its symbols for the next one
-                if ultra and fed >= learn:
-                    rx.sync_timing_set_act(True)                                     # the learning frames are over: the loop holds (calls are whole: the first one at or past N)
-                y, b, _ = rx.sync_timing_synchronize(rx.filter(x, n_frames=F).reshape(F, -1))
-                fed += F
-                y2, _, rdy = rx.sync_timing_extract(y, b)
-                if not rdy[0]:
-                    continue
-                sym, n_sym = y2.reshape(-1, 2), F * n
-            else:
-                mf = np.concatenate([tail, rx.filter(x, n_frames=F).reshape(-1, 2)])
-                mf, skip = mf[skip:], 0                                            # perfect timing: every osf-th sample from `off`
-                n_sym = (mf.shape[0] // osf // n) * n                              # whole frames of symbols
-                if n_sym == 0:
-                    tail = mf
-                    continue
-                sym, tail = mf[: n_sym * osf : osf], mf[n_sym * osf:]
-            for b0 in range(0, n_sym // n, F):
-                blk = np.ascontiguousarray(sym[b0 * n:(b0 + F) * n])
-                Fb = blk.shape[0] // n
-                if not args.no_agc:
-                    blk = rx.agc(blk, n_frames=Fb, output_energy=1.0)                   # mult_agc: DVBS2.cpp:653-657
-                delay, flags, tri, aligned = rx.sync_frame_synchronize(blk.reshape(Fb, 2 * n), with_flags=True)
-                if args.sync_fine or wl:
-                    # the reference's task order (src/mains/RX/main.cpp): PL descramble -> fine synchronizer -> remove PLH ->
-                    # estimate -> demodulate + deinterleave -> LDPC -> BCH -> BB descramble, one C-ABI call per task
-                    desc = rx.pl_descramble(aligned)
-                    if wl:
-                        _, _, desc = rx.sync_lr_synchronize(desc)                     # what the frozen coarse estimate leaves: L&R, as learning phase 3 has trained it (main_sched.cpp:208)
-                    _, _, fixed = rx.sync_freq_phase_synchronize(desc)
-                    xf = rx.remove_plh(fixed)
-                    sig, _, _ = rx.estimate(xf)
-                    vk, _ = rx.decode_siho(rx.demodulate(sig, xf, deinterleave=True))
-                    bits = rx.bb_descramble(rx.decode_hiho(vk)[0])
-                else:
-                    bits, _, _ = rx.rx_bb(aligned)
-                for f in range(Fb):
-                    st["frames"] += 1
-                    stable = stable + 1 if st["delay"] is not None and delay[f] == st["delay"] else 0
-                    locked = stable >= 2                                           # the delay line has settled on this alignment
-                    st["delay"] = int(delay[f])
-                    if snk:
-                        snk.send(bits[f])
-                    if pattern is not None and locked:
-                        e = min(int((bits[f] != p).sum()) for p in pattern)
-                        st["locked_frames"] += 1; st["be"] += e; st["fe"] += e > 0
+            sym = seq.symbols(seq.front(x))
+            if sym is None:
+                continue
+            delay, flags, tri, aligned = seq.align(sym)
+            bits = seq.decode(aligned)
+            for f in range(len(sym)):
+                locked = lock.update(delay[f]) >= 2                                # the delay line has settled on this alignment
+                if snk:
+                    snk.send(bits[f])
+                if pattern is not None and locked:
+                    e = min(int((bits[f] != p).sum()) for p in pattern)
+                    st["locked_frames"] += 1; st["be"] += e; st["fe"] += e > 0
     finally:
         if args.sim_stats:
             from .sim import print_stats
@@ -171,6 +126,7 @@ def run(args, out=sys.stdout) -> dict:
         rx.close(); rcv.close()
         if snk:
             snk.close()
+    st["frames"], st["delay"] = lock.frames, lock.delay
     st["ber"] = st["be"] / max(1, st["locked_frames"] * mc.K_bch)
     st["fer"] = st["fe"] / max(1, st["locked_frames"])
     print("# frames %(frames)d | in lock %(locked_frames)d | BE %(be)d | FE %(fe)d | BER %(ber).2e | FER %(fer).2e | delay %(delay)s" % st, file=out)

@@ -406,3 +406,134 @@ class TwinHandle:
 
     def sync_coarse_get_freq(self):
         return np.array([c.est for c in self.sm.cf], np.float32), np.array([np.float32(c.nu_k) / np.float32(1e6) for c in self.sm.cf], np.float32)
+
+
+# ------------------------------------------------------------------ a recording stand-in: what dvbs2_amd/rx.py, tools/sync_in_loop.py and dvbs2_amd/acquire.py call, no GPU
+class RecordingHandle:
+    """Every method the three callers use appends [name, scalar arguments, crc32 of each array argument] to `log` and returns arrays of the handle's shapes and dtypes
+    whose contents are a function of that entry alone, so equal logs mean the same tasks in the same order on the same data with the same scalars.  The timing
+    extract's RDY and the frame synchronizer's packet flag follow a script: `not_ready` holds the extract calls (counted from 0) that underflow, `flag_from` the
+    frame-synchronizer call from which the flag is up; delays are 7 but at the calls in `delay_moves`.  Subclass to set the script; `made` keeps the instances."""
+    not_ready, flag_from, delay_moves = (), 0, ()
+    made = None
+
+    def __init__(self, modcod="QPSK-S_8/9", max_frames=1, **kw):
+        from dvbs2_amd import params as P
+        self.mc = P.get_modcod(modcod)
+        self.n = self.mc.pl_frame
+        self.log = []
+        self.n_extract = self.n_frame_sync = 0
+        if self.made is not None:
+            self.made.append(self)
+        self._rec("init", [modcod, max_frames] + [[k, kw[k]] for k in sorted(kw)])
+
+    def _rec(self, name, scalars=(), *arrays):
+        import zlib
+        e = [name, [v if isinstance(v, (str, list, bool, type(None))) else float(v) for v in scalars], [zlib.crc32(np.ascontiguousarray(a).tobytes()) for a in arrays]]
+        self.log.append(e)
+        return zlib.crc32(repr(e).encode())
+
+    @staticmethod
+    def _fill(seed, shape, dtype=np.float32, k=0):
+        h = (np.arange(int(np.prod(shape)), dtype=np.uint32) + np.uint32(seed)) * np.uint32(2654435761) + np.uint32(k)
+        h ^= h >> np.uint32(15)
+        return ((h & np.uint32(1)).astype(np.int32) if dtype == np.int32 else (h & np.uint32(0xFFFF)).astype(np.float32) / np.float32(32768) - np.float32(1)).reshape(shape)
+
+    def _same(self, name, X, scalars=()):
+        """a task whose output has its input's size (float32, flat as libdvbs2hip's wrappers give it)"""
+        return self._fill(self._rec(name, scalars, X), np.asarray(X).size)
+
+    # setters and resets: scalars only
+    def timing_enable(self, on=True): self._rec("timing_enable", [on])
+    def sync_coarse_set_freq(self, estimated_freq): self._rec("sync_coarse_set_freq", [estimated_freq])
+    def sync_timing_set_params(self, damping=0.5 ** 0.5, nbw=5e-5, detector_gain=2.0): self._rec("sync_timing_set_params", [damping, nbw, detector_gain])
+    def sync_timing_set_type(self, stm_type="FAST", hold_size=101): self._rec("sync_timing_set_type", [stm_type, hold_size])
+    def sync_timing_set_act(self, act=True): self._rec("sync_timing_set_act", [act])
+    def sync_coarse_set_pll(self, pll_sps=1, damping=0.5 ** 0.5, nbw=1e-4): self._rec("sync_coarse_set_pll", [pll_sps, damping, nbw])
+    def channel_set_delay(self, D): self._rec("channel_set_delay", [D])
+    def channel_set_freq_shift(self, freq_shift): self._rec("channel_set_freq_shift", [freq_shift])
+    def sync_step_mf_reset(self): self._rec("sync_step_mf_reset")
+    def sync_frame_reset(self): self._rec("sync_frame_reset")
+    def sync_timing_reset(self): self._rec("sync_timing_reset")
+    def close(self): self._rec("close")
+
+    def sync_coarse_get_freq(self):
+        s = self._rec("sync_coarse_get_freq")
+        return self._fill(s, 1), self._fill(s, 1, k=1)
+
+    # the receiver's tasks
+    def agc(self, X_N, n_frames=1, output_energy=1.0): return self._same("agc", X_N, [n_frames, output_energy])
+    def filter(self, X_N1, n_frames=1): return self._same("filter", X_N1, [n_frames])
+    def pl_descramble(self, Y_N1): return self._same("pl_descramble", Y_N1).reshape(-1, 2 * self.n)
+
+    def sync_coarse_synchronize(self, X_N1, n_frames=1):
+        s = self._rec("sync_coarse_synchronize", [n_frames], X_N1)
+        return self._fill(s, n_frames), self._fill(s, n_frames, k=1), self._fill(s, np.asarray(X_N1).size, k=2)
+
+    def sync_timing_synchronize(self, X_N1):
+        X = np.asarray(X_N1).reshape(-1, 4 * self.n)
+        s = self._rec("sync_timing_synchronize", (), X)
+        return self._fill(s, X.shape), self._fill(s, X.shape, np.int32, k=1), self._fill(s, X.shape[0], k=2)
+
+    def sync_timing_extract(self, Y_N1, B_N1, out=None):
+        F = np.asarray(Y_N1).reshape(-1, 4 * self.n).shape[0]
+        s = self._rec("sync_timing_extract", (), Y_N1, B_N1)
+        rdy = np.array([self.n_extract not in self.not_ready], np.int32)
+        self.n_extract += 1
+        return self._fill(s, (F, 2 * self.n)), np.zeros(F, np.int32), rdy
+
+    def sync_step_mf_synchronize(self, DEL, X_N1):
+        X = np.asarray(X_N1).reshape(-1, 4 * self.n)
+        s, F = self._rec("sync_step_mf_synchronize", (), DEL, X), X.shape[0]
+        return self._fill(s, F), self._fill(s, F, k=1), self._fill(s, F, k=2), self._fill(s, X.shape, k=3), self._fill(s, X.shape, np.int32, k=4)
+
+    def sync_frame_synchronize(self, X_N1, with_flags=False):
+        X = np.asarray(X_N1).reshape(-1, 2 * self.n)
+        s, F = self._rec("sync_frame_synchronize", [with_flags], X), X.shape[0]
+        delay = np.full(F, 7 + 3 * (self.n_frame_sync in self.delay_moves), np.int32)
+        flags = np.full(F, int(self.n_frame_sync >= self.flag_from), np.int32)
+        self.n_frame_sync += 1
+        return delay, flags, self._fill(s, F), self._fill(s, X.shape, k=1)
+
+    def _sff(self, name, X_N1):
+        X = np.asarray(X_N1).reshape(-1, 2 * self.n)
+        s = self._rec(name, (), X)
+        return self._fill(s, X.shape[0]), self._fill(s, X.shape[0], k=1), self._fill(s, X.shape, k=2)
+
+    def sync_lr_synchronize(self, X_N1): return self._sff("sync_lr_synchronize", X_N1)
+    def sync_freq_phase_synchronize(self, X_N1): return self._sff("sync_freq_phase_synchronize", X_N1)
+
+    def remove_plh(self, Y_N1):
+        F = np.asarray(Y_N1).reshape(-1, 2 * self.n).shape[0]
+        return self._fill(self._rec("remove_plh", (), Y_N1), (F, 2 * self.mc.N_ldpc // self.mc.bps))
+
+    def estimate(self, X_N):
+        s, F = self._rec("estimate", (), X_N), len(X_N)
+        return self._fill(s, F), self._fill(s, F, k=1), self._fill(s, F, k=2)
+
+    def demodulate(self, CP, Y_N1, deinterleave=False): return self._fill(self._rec("demodulate", [deinterleave], CP, Y_N1), (len(Y_N1), self.mc.N_ldpc))
+
+    def decode_siho(self, Y_N, with_post=False, out=None):
+        s = self._rec("decode_siho", [with_post], Y_N)
+        return self._fill(s, (len(Y_N), self.mc.K_ldpc), np.int32), self._fill(s, len(Y_N), np.int32, k=1)
+
+    def decode_hiho(self, Y_N):
+        s = self._rec("decode_hiho", (), Y_N)
+        return self._fill(s, (len(Y_N), self.mc.K_bch), np.int32), self._fill(s, len(Y_N), np.int32, k=1)
+
+    def bb_descramble(self, Y_N1): return self._fill(self._rec("bb_descramble", (), Y_N1), np.asarray(Y_N1).shape, np.int32)
+
+    def rx_bb(self, pl_frames, sigma=None, out=None):
+        F = np.asarray(pl_frames).reshape(-1, 2 * self.n).shape[0]
+        s = self._rec("rx_bb", [sigma], pl_frames)
+        return self._fill(s, (F, self.mc.K_bch), np.int32), self._fill(s, F, np.int32, k=1), self._fill(s, F, np.int32, k=2)
+
+    # the tool's transmitter and channel
+    def tx_bb(self, n_frames, info=None, seed=0, sigma=None):
+        s = self._rec("tx_bb", [n_frames, seed, sigma], info)
+        return info, self._fill(s, (n_frames, 2 * self.n))
+
+    def shape_filter(self, X_N1, n_frames=1, osf=2): return self._fill(self._rec("shape_filter", [n_frames, osf], X_N1), np.asarray(X_N1).size * osf)
+    def channel_delay(self, X): return self._same("channel_delay", X)
+    def channel_freq_shift(self, X): return self._same("channel_freq_shift", X)
+    def add_noise(self, sigma, X_N, seed=0, n_frames=1): return self._same("add_noise", X_N, [sigma, seed, n_frames])

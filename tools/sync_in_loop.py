@@ -24,6 +24,9 @@ import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from dvbs2_amd.rx_sequence import LockTracker, RxSequence, add_timing_args      # noqa: E402
+
+LEARN_FRAMES = 500                                                                 # --stm-learn-frames: the learning phases' 150 + 150 + 200
 
 
 def run_point(Rx, P, mc, ebn0, variant, a):
@@ -36,21 +39,23 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     sigma = np.float32(P.esn0_to_sigma(P.ebn0_to_esn0(ebn0, mc.code_rate, mc.bps)))
     rot = variant == "fine"
     delay_D = getattr(a, "chn_max_delay", None)
-    fast = getattr(a, "stm_type", "PERFECT") == "FAST"
+    stm_type = getattr(a, "stm_type", "PERFECT")
     freq_shift = getattr(a, "chn_max_freq_shift", None)
-    ultra = getattr(a, "stm_type", "PERFECT") == "ULTRA"
     wl = getattr(a, "wl_phases", False)
-    if wl and not fast:
+    if wl and stm_type != "FAST":
         raise ValueError("--wl-phases needs --stm-type FAST")
-    if ultra:
+    if stm_type == "ULTRA":
         rx.sync_timing_set_type("ULTRA", a.stm_hold_size)                              # the held loop: the whole loop for --stm-learn-frames frames, then set_act
-        fast = True
-    fed = 0
     if delay_D is not None:
         rx.channel_set_delay(delay_D)
     if freq_shift is not None:
         rx.channel_set_freq_shift(freq_shift)
+    # the receiver's tasks (dvbs2_amd/rx_sequence.py): timing by genie is its PERFECT at offset 0 -- the two filters delay the stream by 40 symbols, part of the unknown
+    # frame start; --wl-phases: the shift by the loop's frozen estimate in front of the matched filter; `fine` runs L&R always
+    seq = RxSequence(rx, F, 2, pl_frame=n, agc=a.agc, coarse=wl, timing=stm_type, timing_offset=0, learn_frames=getattr(a, "stm_learn_frames", LEARN_FRAMES),
+                     fine=rot, lr=rot, sigma=sigma if a.est_perfect else None)
     st = dict(frames=0, counted=0, be=0, fe=0, delay=None, stable=0, moved=0)
+    lock = LockTracker()
     t0 = time.time()
     idx = (np.arange(F * n) - off) % n
     calls = [0]
@@ -77,48 +82,17 @@ def run_point(Rx, P, mc, ebn0, variant, a):
         if not st["acquisition"]["acquired"]:
             raise RuntimeError("the waiting phase gave up: %r" % (st["acquisition"],))
     while st["fe"] < a.fe and st["counted"] < a.max_frames:
-        noisy = received()
-        if a.agc:
-            noisy = rx.agc(noisy, n_frames=F, output_energy=0.5)                        # front_agc (RX/main_sched.cpp:197; DVBS2.cpp:660-664)
-        if wl:
-            _, _, noisy = rx.sync_coarse_synchronize(noisy, n_frames=F)                 # sync_coarse_f with the loop's frozen estimate (main_sched.cpp:198)
-        mf = rx.filter(noisy, n_frames=F).reshape(-1, 2)
-        if fast:
-            if ultra and fed >= a.stm_learn_frames:
-                rx.sync_timing_set_act(True)
-            fed += F
-            y, b, _ = rx.sync_timing_synchronize(mf.reshape(F, -1))
-            y2, _, rdy = rx.sync_timing_extract(y, b)
-            if not rdy[0]:
-                continue                                                                # underflow: the symbols wait in the carry buffer
-            sym = y2.reshape(F, 2 * n)
-        else:
-            sym = np.ascontiguousarray(mf[0::2]).reshape(F, 2 * n)                     # the two filters delay the stream by 40 symbols: part of the unknown frame start
-        if a.agc:
-            sym = rx.agc(sym, n_frames=F, output_energy=1.0).reshape(F, 2 * n)          # mult_agc (main_sched.cpp:205; DVBS2.cpp:653-657)
-        delay, flags, tri, aligned = rx.sync_frame_synchronize(sym, with_flags=True)
-        if variant == "frame":
-            bits, _, _ = rx.rx_bb(aligned, sigma=sigma if a.est_perfect else None)
-        else:
-            desc = rx.pl_descramble(aligned)
-            _, _, desc = rx.sync_lr_synchronize(desc)
-            _, _, fixed = rx.sync_freq_phase_synchronize(desc)
-            xf = rx.remove_plh(fixed)
-            sg = np.full(F, sigma, np.float32) if a.est_perfect else rx.estimate(xf)[0]
-            vk, _ = rx.decode_siho(rx.demodulate(sg, xf, deinterleave=True))
-            bits = rx.bb_descramble(rx.decode_hiho(vk)[0])
-        err = (bits != pattern[None, :]).sum(axis=1)
+        sym = seq.symbols(seq.front(received()))
+        if sym is None:
+            continue                                                                    # underflow: the symbols wait in the carry buffer
+        delay, flags, tri, aligned = seq.align(sym)
+        err = (seq.decode(aligned) != pattern[None, :]).sum(axis=1)
         for f in range(F):
-            st["frames"] += 1
-            same = st["delay"] is not None and delay[f] == st["delay"]
-            st["stable"] = st["stable"] + 1 if same else 0
-            if not same and st["frames"] > 8:
-                st["moved"] += 1                                                        # the synchronizer left its alignment after the acquisition
-            st["delay"] = int(delay[f])
-            if st["frames"] > a.skip:                                                   # every frame after the acquisition counts, locked or not (a lost lock is a lost frame)
+            lock.update(delay[f])
+            if lock.frames > a.skip:                                                    # every frame after the acquisition counts, locked or not (a lost lock is a lost frame)
                 st["counted"] += 1; st["be"] += int(err[f]); st["fe"] += int(err[f] > 0)
     rx.close()
-    st.update(ebn0=ebn0, variant=variant, fer=st["fe"] / max(1, st["counted"]), ber=st["be"] / max(1, st["counted"] * mc.K_bch), seconds=time.time() - t0)
+    st.update(frames=lock.frames, delay=lock.delay, stable=lock.stable, moved=lock.moved, ebn0=ebn0, variant=variant, fer=st["fe"] / max(1, st["counted"]), ber=st["be"] / max(1, st["counted"] * mc.K_bch), seconds=time.time() - t0)
     return st
 
 
@@ -138,9 +112,7 @@ def build_parser():
     ap.add_argument("--est-perfect", action="store_true", help="the channel's sigma instead of the M2M4 estimate (the reference's 16APSK trace: --est-type PERFECT)")
     ap.add_argument("--agc", action="store_true", help="the reference's two gain stages in the loop (front_agc on the samples, mult_agc on the symbols)")
     ap.add_argument("--chn-max-delay", type=float, default=None, help="the reference channel's delay tasks with this D (>= 2) behind the shaping filter")
-    ap.add_argument("--stm-type", default="PERFECT", choices=["PERFECT", "FAST", "ULTRA"], help="PERFECT: timing by genie; FAST: the Gardner loop on the GPU; ULTRA: its held form")
-    ap.add_argument("--stm-hold-size", type=int, default=101, help="ULTRA: samples per hold block")
-    ap.add_argument("--stm-learn-frames", type=int, default=500, help="ULTRA: frames before the loop starts to hold (the learning phases' 150 + 150 + 200)")
+    add_timing_args(ap, learn_default=LEARN_FRAMES)
     ap.add_argument("--chn-max-freq-shift", type=float, default=None, help="the reference channel's frequency shift (cycles per sample) behind the delay tasks")
     ap.add_argument("--wl-phases", action="store_true", help="run the waiting and learning phases (the coarse-frequency loop on the GPU) before anything is counted")
     ap.add_argument("--json", default=None)
