@@ -102,6 +102,64 @@ def test_matrix_core_correlators_against_the_vector_kernel_and_fp64(O, Rx, monke
     a.close(); b.close()
 
 
+def _both_correlator_families(Rx, monkeypatch, modcod, F, calls):
+    """kernel -> per call (cor_SOF, cor_PLSC) complex, the two-task form on one handle per kernel family (the 64-sample memory carries over)"""
+    import fir_ref as R
+    out = {}
+    for kernel in ("mfma", "valu"):
+        if kernel == "valu":
+            monkeypatch.setenv("DVBS2HIP_SYNC", "valu")
+        else:
+            monkeypatch.delenv("DVBS2HIP_SYNC", raising=False)
+        rx = Rx(modcod, max_frames=F)
+        out[kernel] = []
+        for x in calls:
+            cs, cp = rx.sync_frame_synchronize1(x)
+            rx.sync_frame_synchronize2(x, cs, cp)
+            out[kernel].append((R.c_of(cs.reshape(-1)), R.c_of(cp.reshape(-1))))
+        rx.close()
+    monkeypatch.delenv("DVBS2HIP_SYNC", raising=False)
+    return out
+
+
+@pytest.mark.parametrize("modcod,F", [("32APSK-S_3/4", 5), ("QPSK-S_8/9", 1)])
+def test_both_correlations_against_fp64_with_the_oracle_chain_as_yardstick(O, Rx, monkeypatch, modcod, F):
+    """cor_SOF and cor_PLSC of both kernel families against the complex128 correlation (tests/fir_ref.py corr64), two calls.  The yardstick is the
+    oracle's fp32 chain on the same input: the kernels form d in fp32 too (perhaps contracted otherwise) and add in another order -- other
+    roundings, as many of them -- so each is held to twice the chain's max and rms error, per correlation and call.  A matrix-core kernel
+    without the third sample part is 2e-5 off, far outside (tests/test_fir_ref.py)."""
+    import fir_ref as R
+    stream, n = R.sync_stream(O, modcod, F)
+    ref = R.oracle_corr(O, n, stream.reshape(2 * F, -1))
+    got = _both_correlator_families(Rx, monkeypatch, modcod, F, stream)
+    for q, taps in enumerate(O.sync_frame_taps()):
+        for call in range(2):
+            zp = R.Z0 if call == 0 else R.c_of(stream[0].reshape(-1))[-64:]
+            c64 = R.corr64(stream[call].reshape(-1), taps, zp)
+            er = R.err_stats(ref[q][call * F * n:(call + 1) * F * n], c64)
+            for kernel in ("mfma", "valu"):
+                eg = R.err_stats(got[kernel][call][q], c64)
+                print("corr_fp64 %-13s %-4s call %d %-4s gpu %r | oracle chain %r" % (modcod, ("SOF", "PLSC")[q], call, kernel, eg, er))
+                assert eg.max <= 2 * er.max and eg.rms <= 2 * er.rms, (kernel, q, call, eg, er)
+
+
+@pytest.mark.parametrize("modcod,F", [("32APSK-S_3/4", 5), ("QPSK-S_8/9", 1)])
+def test_correlations_of_unit_samples_are_exact(O, Rx, monkeypatch, modcod, F):
+    """samples from {1, j, -1, -j}: every differential sample is one of them, exactly and with one bf16 part, the sums are whole numbers below 64:
+    both correlations of both families equal the complex128 ones -- the lane map, the taps' places in the band and the carry between calls
+    without a tolerance"""
+    import fir_ref as R
+    from dvbs2_amd import params
+    n = params.get_modcod(modcod).pl_frame
+    x = R.unit_stream(2 * F * n).reshape(2, F, 2 * n)
+    got = _both_correlator_families(Rx, monkeypatch, modcod, F, x)
+    for q, taps in enumerate(O.sync_frame_taps()):
+        for call in range(2):
+            c64 = R.corr64(x[call].reshape(-1), taps, R.Z0 if call == 0 else R.c_of(x[0].reshape(-1))[-64:])
+            for kernel in ("mfma", "valu"):
+                assert np.array_equal(got[kernel][call][q], c64), (kernel, q, call)
+
+
 def test_frame_synchronizer_at_size_locks_and_realigns_the_stream(O, Rx):
     """BASELINE-size call (611 normal frames = 20 M samples in ONE call: many workgroups per frame in the correlators, 25 whole chunks of 24
     frames + a partial one in the average, the delay line in lock) through size-independent properties: the delay settles on the stream's
