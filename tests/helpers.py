@@ -32,6 +32,16 @@ def make_pl_frames(O, modcod, F, ebn0_db, seed):
     return info, pl, cws, sigma
 
 
+def rot(O, pl_frame, f0, ph):
+    """a PL frame as the fine synchronizers see it: PL-descrambled, then turned by f0 cycles per sample from a phase of ph cycles"""
+    d = O.pl_scramble(pl_frame, scramble=False)
+    n = d.size // 2
+    c = (d[0::2] + 1j * d[1::2]) * np.exp(2j * np.pi * (f0 * np.arange(n) + ph))
+    x = np.empty(2 * n, np.float32)
+    x[0::2], x[1::2] = c.real, c.imag
+    return x
+
+
 def make_llrs(O, modcod, F, ebn0_db, seed):
     """BPSK-equivalent channel LLRs for LDPC-only tests (BASELINE config 2):
     y = (1-2c) + sigma n, LLR = 2 y / sigma^2.  -> info_ldpc[F,K], llr[F,N], cw[F,N]"""
