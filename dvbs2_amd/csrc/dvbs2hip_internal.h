@@ -270,6 +270,13 @@ struct TxKParams {
     int32_t K_bch, K_ldpc, N_ldpc, bps, itl_cols, itl_order, n_sym, pl_frame, enc_stride, n_frames;
 };
 hipError_t tx_launch(const TxKParams &p, hipStream_t s);
+// the TX tasks at the task boundary (k_tx_tasks.hip): int32 per bit, float pairs per symbol; the encoders take the tables and the B_TXBCH scratch (bch_cw) from p
+hipError_t tx_bch_encode_launch(const TxKParams &p, const int32_t *U_K, int32_t *X_N, hipStream_t s);
+hipError_t tx_ldpc_encode_launch(const TxKParams &p, const int32_t *U_K, int32_t *X_N, hipStream_t s);
+hipError_t tx_interleave_launch(const int32_t *nat, int32_t *itl, int N, int cols, int order, int F, hipStream_t s);
+hipError_t tx_modulate_launch(const int32_t *X, float *Y, const float *cstl, int bps, int N, int n_sym, int F, hipStream_t s);
+hipError_t tx_framer_launch(const float *X, float *Y, const float *plh, int n_sym, int pl_frame, int F, hipStream_t s);
+hipError_t tx_pl_scramble_launch(const float *X, float *Y, const uint8_t *seq, int pl_frame, int F, hipStream_t s);
 // generator polynomial of the t-error-correcting BCH code over GF(2^m): g[i] = coeff of x^i
 std::vector<uint8_t> bch_generator(const BchPlan &pl);
 

@@ -151,6 +151,20 @@ ABI = {
     "dvbs2hip_rx_bb": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_rx_bb_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_rx_bb_located_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_bb_scramble": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_bb_scramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_bch_encode": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_bch_encode_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_ldpc_encode": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_ldpc_encode_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_interleave": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_interleave_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_modulate": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_modulate_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_framer_generate": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_framer_generate_dev": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_pl_scramble": (C.c_int, [_vp, _vp, _vp, _i]),
+    "dvbs2hip_pl_scramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_tx_bb": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _i]),
     "dvbs2hip_tx_bb_dev": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _i]),
     "dvbs2hip_shape_filter": (C.c_int, [_vp, _vp, _vp, _i, _i]),

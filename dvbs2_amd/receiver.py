@@ -439,6 +439,62 @@ class Dvbs2Hip:
     def tx_bb_dev(self, info_in, seed, sigma, info_out, pl_frames, n_frames):
         self._chk(self.L.dvbs2hip_tx_bb_dev(self.h, _ptr(info_in), int(seed), _ptr(sigma), _ptr(info_out), _ptr(pl_frames), n_frames))
 
+    # ------------------------------------------------------------------ TX tasks: one method per codelet of the transmitter
+    def _tx_task(self, fn, X, n_in, t_in, n_out, t_out):
+        Xa, F = self._frames(X, n_in, t_in)
+        out = np.empty((F, n_out), dtype=t_out)
+        self._chk(fn(self.h, _ptr(Xa), _ptr(out), F))
+        return out
+
+    def bb_scramble(self, X_N1):
+        """Scrambler_BB::scramble: int32[F, K_bch] -> int32[F, K_bch]"""
+        return self._tx_task(self.L.dvbs2hip_bb_scramble, X_N1, self.K_bch, np.int32, self.K_bch, np.int32)
+
+    def bb_scramble_dev(self, X_N1, X_N2, n_frames):
+        self._chk(self.L.dvbs2hip_bb_scramble_dev(self.h, _ptr(X_N1), _ptr(X_N2), n_frames))
+
+    def bch_encode(self, U_K):
+        """Encoder_BCH_DVBS2::encode: int32[F, K_bch] -> int32[F, N_bch] (N_bch = K_ldpc), systematic"""
+        return self._tx_task(self.L.dvbs2hip_bch_encode, U_K, self.K_bch, np.int32, self.K_ldpc, np.int32)
+
+    def bch_encode_dev(self, U_K, X_N, n_frames):
+        self._chk(self.L.dvbs2hip_bch_encode_dev(self.h, _ptr(U_K), _ptr(X_N), n_frames))
+
+    def ldpc_encode(self, U_K):
+        """the LDPC encoder: int32[F, K_ldpc] -> int32[F, N_ldpc], systematic"""
+        return self._tx_task(self.L.dvbs2hip_ldpc_encode, U_K, self.K_ldpc, np.int32, self.N_ldpc, np.int32)
+
+    def ldpc_encode_dev(self, U_K, X_N, n_frames):
+        self._chk(self.L.dvbs2hip_ldpc_encode_dev(self.h, _ptr(U_K), _ptr(X_N), n_frames))
+
+    def interleave(self, nat):
+        """Interleaver::interleave: int32[F, N_ldpc] -> int32[F, N_ldpc]"""
+        return self._tx_task(self.L.dvbs2hip_interleave, nat, self.N_ldpc, np.int32, self.N_ldpc, np.int32)
+
+    def interleave_dev(self, nat, itl, n_frames):
+        self._chk(self.L.dvbs2hip_interleave_dev(self.h, _ptr(nat), _ptr(itl), n_frames))
+
+    def modulate(self, X_N1):
+        """Modem::modulate: int32[F, N_ldpc] -> f32[F, 2 * N_xfec]"""
+        return self._tx_task(self.L.dvbs2hip_modulate, X_N1, self.N_ldpc, np.int32, 2 * self.N_xfec, np.float32)
+
+    def modulate_dev(self, X_N1, X_N2, n_frames):
+        self._chk(self.L.dvbs2hip_modulate_dev(self.h, _ptr(X_N1), _ptr(X_N2), n_frames))
+
+    def framer_generate(self, Y_N1):
+        """Framer::generate: f32[F, 2 * N_xfec] -> f32[F, 2 * pl_frame]"""
+        return self._tx_task(self.L.dvbs2hip_framer_generate, Y_N1, 2 * self.N_xfec, np.float32, 2 * self.pl_frame, np.float32)
+
+    def framer_generate_dev(self, Y_N1, Y_N2, n_frames):
+        self._chk(self.L.dvbs2hip_framer_generate_dev(self.h, _ptr(Y_N1), _ptr(Y_N2), n_frames))
+
+    def pl_scramble(self, X_N1):
+        """Scrambler_PL::scramble: f32[F, 2 * pl_frame] -> f32[F, 2 * pl_frame]"""
+        return self._tx_task(self.L.dvbs2hip_pl_scramble, X_N1, 2 * self.pl_frame, np.float32, 2 * self.pl_frame, np.float32)
+
+    def pl_scramble_dev(self, X_N1, X_N2, n_frames):
+        self._chk(self.L.dvbs2hip_pl_scramble_dev(self.h, _ptr(X_N1), _ptr(X_N2), n_frames))
+
     # ------------------------------------------------------------------ N2: shaping filter, noise, perfect timing
     def shape_filter(self, X_N1, n_frames=1, osf=2):
         X = np.ascontiguousarray(X_N1, dtype=np.float32).ravel()

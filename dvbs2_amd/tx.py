@@ -2,6 +2,8 @@
 PL scramble -> shaping filter -> raw IQ file, every stage on the GPU (src/mains/TX/main.cpp of the reference; README.md:151-158).
 
   python -m dvbs2_amd.tx --rad-tx-file-path out_tx.bin -F 8 --src-type USER --src-path K_14232.src --mod-cod QPSK-S_8/9 --n-frames 64
+
+`--tx-tasks` makes the PL frames by the seven TX tasks of the C ABI, one call per task (TxTasks below), instead of the fused tx_bb: the same file.
 """
 from __future__ import annotations
 
@@ -29,7 +31,44 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sim-seed", type=int, default=0, dest="seed")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sim-stats", action="store_true", help="per-kernel-group device time at the end (the reference's --sim-stats)")
+    ap.add_argument("--tx-tasks", action="store_true", help="make the PL frames by the seven TX tasks, one C-ABI call per task in the reference's order, instead of the fused tx_bb "
+                    "(payload sources USER, USER_BIN and AZCW; same frames)")
     return ap
+
+
+class TxTasks:
+    """The PL frames of a batch by the seven tasks of the reference's TX mains, each a `_dev` call on the handle's stream:
+    BB scramble -> BCH encode -> LDPC encode -> interleave -> modulate -> frame -> PL scramble; the sockets in between stay on the device."""
+
+    def __init__(self, rx, n_frames, device=0):
+        import torch
+        self.torch, self.rx, self.F = torch, rx, n_frames
+        self.dev = torch.device("cuda", device)
+        bits = lambda n: torch.empty((n_frames, n), dtype=torch.int32, device=self.dev)
+        syms = lambda n: torch.empty((n_frames, 2 * n), dtype=torch.float32, device=self.dev)
+        self.scr, self.bch, self.cw, self.itl = bits(rx.K_bch), bits(rx.K_ldpc), bits(rx.N_ldpc), bits(rx.N_ldpc)
+        self.sym, self.plf, self.pl = syms(rx.N_xfec), syms(rx.pl_frame), syms(rx.pl_frame)
+
+    def run_dev(self, info):
+        """info: int32 device tensor [F, K_bch] -> the device tensor of the scrambled PL frames (valid once the handle's stream has got there)"""
+        rx, F = self.rx, self.F
+        rx.bb_scramble_dev(info.data_ptr(), self.scr.data_ptr(), F)
+        rx.bch_encode_dev(self.scr.data_ptr(), self.bch.data_ptr(), F)
+        rx.ldpc_encode_dev(self.bch.data_ptr(), self.cw.data_ptr(), F)
+        rx.interleave_dev(self.cw.data_ptr(), self.itl.data_ptr(), F)
+        rx.modulate_dev(self.itl.data_ptr(), self.sym.data_ptr(), F)
+        rx.framer_generate_dev(self.sym.data_ptr(), self.plf.data_ptr(), F)
+        rx.pl_scramble_dev(self.plf.data_ptr(), self.pl.data_ptr(), F)
+        return self.pl
+
+    def run(self, info):
+        """info: int32 array [F, K_bch] -> f32 array [F, 2 * pl_frame]"""
+        torch = self.torch
+        d_info = torch.from_numpy(info.reshape(self.F, self.rx.K_bch)).to(self.dev)
+        torch.cuda.current_stream(self.dev).synchronize()          # (the copy is asynchronous to the handle's stream)
+        pl = self.run_dev(d_info)
+        self.rx.synchronize()
+        return pl.cpu().numpy()
 
 
 def run(args, out=sys.stdout) -> int:
@@ -41,12 +80,15 @@ def run(args, out=sys.stdout) -> int:
         raise ValueError("one of --n-frames / --tx-time-limit is needed to end the transmission")
     if args.src_type in ("USER", "USER_BIN") and not args.src_path:
         raise ValueError("--src-type %s needs --src-path" % args.src_type)
+    if args.tx_tasks and args.src_type == "RAND":
+        raise ValueError("--tx-tasks needs a payload source (USER, USER_BIN or AZCW): the random source lives inside the fused tx_bb")
     F = args.n_frames_batch
     src = (SourceUser(args.src_path, mc.K_bch) if args.src_type == "USER" else SourceUserBinary(args.src_path, mc.K_bch, auto_reset=not args.src_no_loop) if args.src_type == "USER_BIN"
            else SourceAZCW(mc.K_bch) if args.src_type == "AZCW" else None)
     rx = Dvbs2Hip(mc.name, max_frames=F, device=args.device)
     if args.sim_stats:
         rx.timing_enable(True)
+    tasks = TxTasks(rx, F, args.device) if args.tx_tasks else None
     snd = RadioUserBinary(mc.pl_frame * args.osf, output_filename=args.rad_tx_file_path, n_frames=F)
     t0, frames, call = time.perf_counter(), 0, 0
     try:
@@ -55,7 +97,10 @@ def run(args, out=sys.stdout) -> int:
                 info = src.generate(F) if src else None
             except SourceDone:
                 break
-            _, pl = rx.tx_bb(F, info=info, seed=(args.seed << 32) + call)
+            if tasks:
+                pl = tasks.run(info)
+            else:
+                _, pl = rx.tx_bb(F, info=info, seed=(args.seed << 32) + call)
             snd.send(rx.shape_filter(pl, n_frames=F, osf=args.osf))        # the filter memory carries over from call to call
             frames += F
             call += 1

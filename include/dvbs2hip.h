@@ -345,6 +345,50 @@ int dvbs2hip_tx_bb(dvbs2hip_t *h, const int32_t *info_in, uint64_t seed, const f
 int dvbs2hip_tx_bb_dev(dvbs2hip_t *h, const int32_t *info_in, uint64_t seed, const float *sigma, int32_t *info_out,
                        float *pl_frames, int32_t n_frames);
 
+/* ------------------------------------------------------------------ TX tasks: one entry per codelet of the transmitter
+ * The seven tasks the reference's TX mains bind between the source and the shaping filter (src/mains/TX/main.cpp:70-78,
+ * TX_VAR/main.cpp:71-78, TX_RX_BB/main.cpp:75-81), sockets as there: one int32_t per bit (0 or 1; other input values are
+ * not defined, outputs are exactly 0 or 1), re/im interleaved floats per symbol.  Input and output sockets are distinct; the
+ * tasks keep no state between calls.  Chained in this order they compute what dvbs2hip_tx_bb computes without noise.
+ * _dev sockets may start at any multiple of the element size (4 bytes for bits, 8 for a complex symbol).
+ *
+ * replaces: Scrambler_BB<B>::scramble -> _scramble -- src/common/Module/Scrambler/Scrambler_BB/Scrambler_BB.hxx:51-72
+ * (the same XOR as dvbs2hip_bb_descramble).
+ *   X_N1, X_N2 : int32_t[n_frames * K_bch]                                            */
+int dvbs2hip_bb_scramble(dvbs2hip_t *h, const int32_t *X_N1, int32_t *X_N2, int32_t n_frames);
+int dvbs2hip_bb_scramble_dev(dvbs2hip_t *h, const int32_t *X_N1, int32_t *X_N2, int32_t n_frames);
+/* replaces: Encoder_BCH_DVBS2<B>::encode -> _encode -- src/common/Module/Encoder_BCH_DVBS2/Encoder_BCH_DVBS2.cpp:28-43.
+ * Systematic: X_N[0 .. K_bch) = U_K, then the N_bch - K_bch parity bits, coefficient of the highest power first.
+ *   U_K : int32_t[n_frames * K_bch]  ->  X_N : int32_t[n_frames * N_bch]   (N_bch = K_ldpc)       */
+int dvbs2hip_bch_encode(dvbs2hip_t *h, const int32_t *U_K, int32_t *X_N, int32_t n_frames);
+int dvbs2hip_bch_encode_dev(dvbs2hip_t *h, const int32_t *U_K, int32_t *X_N, int32_t n_frames);
+/* replaces: the LDPC encoder's encode (enc type "LDPC_DVBS2", built src/common/Factory/DVBS2/DVBS2.cpp:427; ETSI EN 302 307
+ * 5.3.2).  Systematic: X_N[0 .. K_ldpc) = U_K, then the parity bits p_0 .. p_{M-1} in natural order.
+ *   U_K : int32_t[n_frames * K_ldpc]  ->  X_N : int32_t[n_frames * N_ldpc]                       */
+int dvbs2hip_ldpc_encode(dvbs2hip_t *h, const int32_t *U_K, int32_t *X_N, int32_t n_frames);
+int dvbs2hip_ldpc_encode_dev(dvbs2hip_t *h, const int32_t *U_K, int32_t *X_N, int32_t n_frames);
+/* replaces: module::Interleaver<B,uint32_t>::interleave(nat, itl) -- the column/row interleaver of DVBS2.cpp:451-476:
+ * itl[i] = nat[lut[i]]; a copy when the MODCOD has none (itl_cols == 1).
+ *   nat, itl : int32_t[n_frames * N_ldpc]                                             */
+int dvbs2hip_interleave(dvbs2hip_t *h, const int32_t *nat, int32_t *itl, int32_t n_frames);
+int dvbs2hip_interleave_dev(dvbs2hip_t *h, const int32_t *nat, int32_t *itl, int32_t n_frames);
+/* replaces: module::Modem_generic<B,R,Q>::modulate(X_N1, X_N2) -- built DVBS2.cpp:478-488.  Symbol k takes bits
+ * k bps .. k bps + bps - 1, bit b with weight 1 << b, and is the handle's normalised constellation point of that index.
+ *   X_N1 : int32_t[n_frames * N_ldpc]  ->  X_N2 : float[n_frames * 2*N_xfec]          */
+int dvbs2hip_modulate(dvbs2hip_t *h, const int32_t *X_N1, float *X_N2, int32_t n_frames);
+int dvbs2hip_modulate_dev(dvbs2hip_t *h, const int32_t *X_N1, float *X_N2, int32_t n_frames);
+/* replaces: Framer<B>::generate -> _generate -- src/common/Module/Framer/Framer.hxx:232-293: the 90 PLHEADER symbols, then the
+ * data with a block of 36 pilots after every 16 slots.
+ *   Y_N1 : float[n_frames * 2*N_xfec]  ->  Y_N2 : float[n_frames * 2*pl_frame]        */
+int dvbs2hip_framer_generate(dvbs2hip_t *h, const float *Y_N1, float *Y_N2, int32_t n_frames);
+int dvbs2hip_framer_generate_dev(dvbs2hip_t *h, const float *Y_N1, float *Y_N2, int32_t n_frames);
+/* replaces: Scrambler_PL<D>::scramble -> __scramble(scr_flag = true)
+ * -- src/common/Module/Scrambler/Scrambler_PL/Scrambler_PL.hxx:46,61-78 (start_ix = 90): the header is copied, symbol
+ * i >= 90 is turned by R[i - 90] quarter turns (swaps and sign changes: no rounding).
+ *   X_N1, X_N2 : float[n_frames * 2*pl_frame]                                         */
+int dvbs2hip_pl_scramble(dvbs2hip_t *h, const float *X_N1, float *X_N2, int32_t n_frames);
+int dvbs2hip_pl_scramble_dev(dvbs2hip_t *h, const float *X_N1, float *X_N2, int32_t n_frames);
+
 /* ------------------------------------------------------------------ N2: TX shaping filter, channel noise, perfect timing
  * replaces: Filter_UPRRC_ccr_naive::filter -> Filter_UPFIR_ccr_naive::_filter
  * -- src/common/Module/Filter/Filter_UPFIR/Filter_UPFIR_ccr_naive.cpp:52-66 (polyphase bank of `fir_osf` FIRs built
