@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/dvbs2hip.h"
+#include "ldpc_layer_table.h"
 
 namespace dvbs2 {
 
@@ -78,9 +79,9 @@ struct LdpcKParams {
     int32_t inf_row;           // fast path: byte offset of the +inf row (padded layers) or -1
     uint32_t *cu_ctr;          // 8-wave workgroups: per-CU arrival counter (zeroed before the launch) or null
     struct {                   // k_ldpc_wg8.hip
-        const uint32_t *tab;   // [q][LDPC_FAST_STRIDE]: byte shift | byte offset of the bit-group row << 11 | LDS flag << 29; modes 4 / 5: then [q][NR] the idle waves' swaps (LDS position or 0xFF)
+        const uint32_t *tab;   // the layer tables, then the row-keeping waves' swaps (LdpcPlan::w8_tab; layout: ldpc_layer_table.h)
         const uint32_t *atab;  // per-lane address table (LdpcPlan::w8_atab) or null
-        const uint32_t *rows;  // bit-group of LDS row l (nl of them), then of global row l (ng), then where the q parity groups live; modes 4 / 5: then the bit-group in register slot k (NR)
+        const uint32_t *rows;  // the image's rows in storage order, the parity groups' places, the register slots' rows (LdpcPlan::w8_rows; sections: ldpc_layer_table.h)
         uint32_t st_base;      // byte offset of the packed c->v state in the workgroup's global slot
         uint32_t lds_junk;     // byte offset of the write-only LDS row (the +inf row of padded codes follows it)
         int32_t lds_bytes, pad;
@@ -143,9 +144,7 @@ constexpr int LDPC_FRAME_CTR = 4096;
 #endif                               // per CU: the 14 registers that carry the table do not exist there (23 / 19 / 8 spilled registers with suffix values every 3rd / 4th / 6th slot: QPSK-S 8/9
                                      // 9.63 -> 13.0 / 11.9 / 11.2 ms, docs/negative_results.md)
 constexpr int LDPC_AT_LANES = 384;      // lanes per row of the address table (6 waves; lanes 360 .. 383 hold the junk row / an offset that is dropped)
-constexpr int LDPC_FAST_STRIDE = 64;   // dwords per layer: 27 entries | prim mask | conflict info | conflict entries 0, 1 | slots with a duplicate edge | 16 conf entries | 16 conf meta
-                                       // (sum-product plans, at most LDPC_SPA_MAXC conflict entries: dwords LDPC_TANH_ORDER .. +4 = the slots in the ORACLE's edge order, 5 bits each, 6 per dword)
-constexpr int LDPC_TANH_ORDER = 56;
+// LDPC_FAST_STRIDE, LDPC_TANH_ORDER and every other number of the fast kernels' tables: ldpc_layer_table.h
 constexpr float LDPC_SPA_CAP = 16.6355324f;      // 2 atanh(1 - FLT_EPSILON): where the messages of AFF3CT's tanh-product rule stop (spa_rule 2 by construction, 3 by a clip)
 constexpr int LDPC_FAST_MAXC = 16;
 // modes 4 / 5 (k_ldpc_wg8.hip): bit-group rows parked in the registers of a workgroup's two idle waves (3 VGPRs per row and lane) and LDS slots per
@@ -235,7 +234,7 @@ struct FrontKParams {
 };
 size_t ldpc_lat_lds_bytes(const LdpcPlan &pl);                                    // k_ldpc_lat.hip: small batches of short frames, two lanes per check (0: not applicable)
 hipError_t ldpc_lat_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s);
-hipError_t frame_order_launch(const float *llr, float *metric, uint32_t *order, int F, int N, hipStream_t s);      // k_ldpc.hip: the work queue's order for launches with the stopping rule (noisiest frames first)
+hipError_t frame_order_launch(const float *llr, float *metric, uint32_t *order, int F, int N, hipStream_t s);      // k_ldpc_generic.hip: the work queue's order for launches with the stopping rule (noisiest frames first)
 hipError_t front_rx_launch(FrontKParams p, hipStream_t s);                     // a7+a6+a3+a4 fused, in = pl frames
 hipError_t demod_launch(FrontKParams p, bool deinterleave, hipStream_t s);     // a3 (+a4), in = xfec frames, sigma_in required
 hipError_t deinterleave_launch(const float *itl, float *nat, int N, int cols, int order, int F, hipStream_t s);

@@ -17,6 +17,7 @@
 //     work queue (frames handed out through a counter).
 // Same schedule and arithmetic as the oracle (bit-exact): tests/test_ldpc_gpu.py, tests/test_golden_gpu.py.
 #include "dvbs2hip_internal.h"
+#include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -133,8 +134,8 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
     };
     auto layer_barriers = [&](int r) {              // the barriers of one decoding layer, as the working waves take them
         const const_u32 T = tab + r * LDPC_FAST_STRIDE;
-        const uint32_t cinfo = T[28];
-        const int ncf = (int)(cinfo & 0xFFu);
+        const uint32_t cinfo = T[LT_CINFO];
+        const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
         bar_nowait();                               // the halves' partial minima are in the exchange area; every read of the layer precedes its writes
         if (SPA == 1) bar_nowait();                 // sum-product layer with the per-check scale: the halves' products are in the exchange area (the capped rule needs one exchange)
 #if C1_KEEP_LATE
@@ -143,8 +144,8 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
         if (ncf > 0) {
             bar_nowait();                           // the primary writes are in place
             uint32_t prev_lvl = 1u;
-            for (int i = (ncf > 1 && ((cinfo >> 21) & 3u) == 1u) ? 2 : 1; i < ncf; i++) {
-                const uint32_t lvl = T[48 + i] >> 8;
+            for (int i = (ncf > 1 && ((cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK) == 1u) ? 2 : 1; i < ncf; i++) {
+                const uint32_t lvl = T[LT_CONF_META + i] >> LT_META_LVL_SHIFT;
                 if (lvl != prev_lvl) { bar_nowait(); prev_lvl = lvl; }
             }
         }
@@ -160,12 +161,12 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
 #pragma unroll
         for (int k = 0; k < NRG; k++) {
             const uint32_t g = srow[k];
-            if (g != 0xFFFFFFFFu && (int)g >= p.n_info) {      // a parity group: element e is bit K + q e + (g - n_info)
+            if (g != ROWS_NONE && (int)g >= p.n_info) {      // a parity group: element e is bit K + q e + (g - n_info)
                 const float *Yg = Y + p.K + ((int)g - p.n_info);
                 R[k][0] = Yg[q * elc]; R[k][1] = Yg[q * (elc + LDPC_Z / 3)]; R[k][2] = Yg[q * (elc + 2 * (LDPC_Z / 3))];
                 continue;
             }
-            const float *Yg = Y + (g == 0xFFFFFFFFu ? 0u : g) * (uint32_t)LDPC_Z;
+            const float *Yg = Y + (g == ROWS_NONE ? 0u : g) * (uint32_t)LDPC_Z;
             R[k][0] = __builtin_nontemporal_load(&Yg[elc]); R[k][1] = __builtin_nontemporal_load(&Yg[elc + LDPC_Z / 3]); R[k][2] = __builtin_nontemporal_load(&Yg[elc + 2 * (LDPC_Z / 3)]);
         }
         __syncthreads();                            // the image is in place
@@ -270,7 +271,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
 #pragma unroll
                 for (int k = 0; k < PIO; k++) {
                     if (i0 + k < i_hi) {
-                        if ((i0 + k) * 64 + lane < cnt && prow[r] != 0xFFFFFFFFu) lst(prow[r] + (uint32_t)(tl0 + tl) * 4u, v[k]);      // (0xFFFFFFFF: that group starts in a register slot)
+                        if ((i0 + k) * 64 + lane < cnt && prow[r] != ROWS_NONE) lst(prow[r] + (uint32_t)(tl0 + tl) * 4u, v[k]);      // (0xFFFFFFFF: that group starts in a register slot)
                         tl += dq; r += dr;
                         if (r >= q) { r -= q; tl++; }
                     }
@@ -300,9 +301,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                 uint32_t E[NS];
 #pragma unroll
                 for (int j = 0; j < NS; j++) E[j] = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, J0 + j) : TE[J0 + j];
-                const uint32_t prim = (SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 27) : TE[27]) >> J0, cinfo = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 28) : TE[28],
-                               ce0 = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 29) : TE[29], ce1 = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 30) : TE[30];
-                const int ncf = (int)(cinfo & 0xFFu);
+                const uint32_t prim = (SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_PRIM) : TE[LT_PRIM]) >> J0, cinfo = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CINFO) : TE[LT_CINFO],
+                               ce0 = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF0) : TE[LT_CONF0], ce1 = SPA ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF1) : TE[LT_CONF1];
+                const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
                 const bool mask0 = HALF == 1 && (r == 0) && (t == 0);        // p_{c-1} of check 0 does not exist
                 if constexpr (SPA) {
                     // ================= sum-product layer, two lanes per check (round 5) =================
@@ -339,7 +340,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     float x[NS], u[NS], Bs[NB], od[LDPC_SPA_MAXC];
                     uint32_t t4s = t4;
                     uint32_t wk[C1_SPA_KEEPW ? NS : 1];
-                    auto woff = [&](int j, uint32_t tt) __attribute__((always_inline)) { const uint32_t d = tt - (E[j] & 0x7FFu); return min(d, d + (uint32_t)C1_ROW) + ((E[j] >> 11) & 0x3FFFFu); };
+                    auto woff = [&](int j, uint32_t tt) __attribute__((always_inline)) { const uint32_t d = tt - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK); };
                     float mn1 = INFINITY, mn2 = INFINITY, kap = 1.f, cln = 0.f, key = 0.f, Qown = 0.f;
                     uint32_t sx = 0u;
                     auto comb = [&](float a, float b) __attribute__((always_inline)) { return __builtin_fmaf(b, __builtin_fmaf(-kap, a, 1.f), a); };      // Q'_ab
@@ -480,13 +481,13 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     C1_MARK(3);
                     // duplicate edges: ordered delta updates, level by level, by half A's lanes (conflict entry i is slot i: what it adds is od[i] = new - old)
                     if (ncf > 0) {
-                        auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & 0x7FFu); return min(d, d + (uint32_t)C1_ROW) + ((e >> 11) & 0x3FFFFu); };
+                        auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
                         uint32_t prev_lvl = 0u;
 #pragma unroll
                         for (int i = 0; i < LDPC_SPA_MAXC; i++) {
                             if (i >= ncf) break;
-                            const uint32_t e = i == 0 ? ce0 : i == 1 ? ce1 : T[32 + i];
-                            const uint32_t lvl = i == 0 ? 1u : i == 1 ? (cinfo >> 21) & 3u : T[48 + i] >> 8;
+                            const uint32_t e = i == 0 ? ce0 : i == 1 ? ce1 : T[LT_CONF + i];
+                            const uint32_t lvl = i == 0 ? 1u : i == 1 ? (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK : T[LT_CONF_META + i] >> LT_META_LVL_SHIFT;
                             if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                             if (HALF == 0 && act) { const uint32_t a = addr_of(e); const float Lv = lld(a); lst(a, Lv + od[i]); }
                         }
@@ -506,8 +507,8 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     // ---- pass 1a: every posterior load of the half-check in flight before any use
 #pragma unroll
                     for (int j = 0; j < NS; j++) {
-                        const uint32_t d = t4 - (E[j] & 0x7FFu);
-                        const uint32_t base = (E[j] >> 11) & 0x3FFFFu;
+                        const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK);
+                        const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
                         w[j] = min(d, d + (uint32_t)C1_ROW) + base;
                         if (FWD && j == NS - 1 && r > 0) v[j] = pfw;         // p_{c-1}: handed over by layer r - 1
                         else v[j] = lld(w[j]);
@@ -608,9 +609,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                 C1_MARK(3);
                 // ---- duplicate edges of a bit-group inside this layer: ordered delta updates, level by level, by half A's lanes (conflict entry i is slot i)
                 if (ncf > 0) {
-                    auto addr_of = [&](uint32_t e) { const uint32_t d = t4 - (e & 0x7FFu); return min(d, d + (uint32_t)C1_ROW) + ((e >> 11) & 0x3FFFFu); };
+                    auto addr_of = [&](uint32_t e) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
                     auto delta_of = [&](uint32_t j) { return c1_unpack<NS>(cst1, cst2, pkn, j, SB) - c1_unpack<NS>(c1o, c2o, pko, j, SB); };
-                    const uint32_t j0 = (cinfo >> 8) & 31u, j1 = (cinfo >> 16) & 31u, lvl1 = (cinfo >> 21) & 3u;
+                    const uint32_t j0 = (cinfo >> LT_CINFO_SLOT0_SHIFT) & LT_SLOT_MASK, j1 = (cinfo >> LT_CINFO_SLOT1_SHIFT) & LT_SLOT_MASK, lvl1 = (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK;
                     const bool two = ncf > 1 && lvl1 == 1u;         // entry 1 commutes with entry 0 (another bit-group)
                     __syncthreads();                                // the primary writes of the layer are in place
                     if (HALF == 0 && act) {
@@ -622,8 +623,8 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     }
                     uint32_t prev_lvl = 1u;
                     for (int i = two ? 2 : 1; i < ncf; i++) {
-                        const uint32_t e = T[32 + i], meta = T[48 + i];
-                        const uint32_t j = meta & 31u, lvl = meta >> 8;
+                        const uint32_t e = T[LT_CONF + i], meta = T[LT_CONF_META + i];
+                        const uint32_t j = meta & LT_SLOT_MASK, lvl = meta >> LT_META_LVL_SHIFT;
                         if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                         if (HALF == 0 && act) {
                             const uint32_t a = addr_of(e);
@@ -658,8 +659,8 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
 #pragma unroll
                         for (int j = 0; j < DEG; j++) {
                             const uint32_t e = T[j];
-                            const uint32_t d = t4 - (e & 0x7FFu);
-                            Lv[j] = lld(min(d, d + (uint32_t)C1_ROW) + ((e >> 11) & 0x3FFFFu));
+                            const uint32_t d = t4 - (e & LT_SHIFT_MASK);
+                            Lv[j] = lld(min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK));
                         }
                         if (r == 0 && t == 0) Lv[DEG - 1] = 0.f;                               // absent edge
                         uint32_t x = 0u;
@@ -725,7 +726,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
 #pragma unroll
                 for (int k = 0; k < C1_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRT ? l0 + k : NRT - 1) * C1_ROW + t4) : 0.f;
 #pragma unroll
-                for (int k = 0; k < C1_IO; k++) if (l0 + k < NRT && srow[l0 + k] != 0xFFFFFFFFu) emit((int)srow[l0 + k], v[k]);
+                for (int k = 0; k < C1_IO; k++) if (l0 + k < NRT && srow[l0 + k] != ROWS_NONE) emit((int)srow[l0 + k], v[k]);
             }
         }
         if (first_wave && lane == 0) s_misc[19] = p.cu_ctr ? (int)(atomicAdd(&p.cu_ctr[LDPC_FRAME_CTR], 1u) + gridDim.x) : qp + (int)gridDim.x;

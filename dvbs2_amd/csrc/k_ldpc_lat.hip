@@ -15,6 +15,7 @@
 // Tables: the LDS-only plan of k_ldpc.hip as it is (w8_tab: slot entries = byte shift | byte offset of the bit-group row << 11, prim mask, conflict list).
 // Min-sum / normalised min-sum only; used by dvbs2hip_api.hip for calls of at most one frame per CU on codes whose image and state fit the LDS.
 #include "dvbs2hip_internal.h"
+#include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 
 namespace dvbs2 {
 
@@ -65,7 +66,7 @@ ldpc_lat_kernel(const LdpcKParams p)
         while (it < p.n_ite) {
             for (int r = 0; r < q; r++) {
                 const lat_const_u32 T = tab + r * LDPC_FAST_STRIDE;
-                const uint32_t prim = T[27], ncf = T[28] & 0xFFu;
+                const uint32_t prim = T[LT_PRIM], ncf = T[LT_CINFO] & LT_CINFO_NCF_MASK;
                 // ---- this half-check's slots: posterior loads, v->c = posterior - old c->v, local minima and signs
                 const uint32_t sa = st0 + (uint32_t)(r * LDPC_Z + (act ? t : 0)) * 12u;
                 const float c1o = *lat_f(sa), c2o = *lat_f(sa + 4u);
@@ -81,8 +82,8 @@ ldpc_lat_kernel(const LdpcKParams p)
                     const uint32_t e = part ? (has2 ? T[H + i < DEG ? H + i : 0] : 0u) : T[i];
                     const bool valid = act && (part == 0 || has2);
                     const uint32_t js = (uint32_t)(part ? H + i : i);
-                    const uint32_t d = t4 - (e & 0x7FFu);
-                    adr[i] = min(d, d + (uint32_t)LAT_ROW) + ((e >> 11) & 0x3FFFFu);
+                    const uint32_t d = t4 - (e & LT_SHIFT_MASK);
+                    adr[i] = min(d, d + (uint32_t)LAT_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK);
                     const bool absent = r == 0 && t == 0 && js == (uint32_t)(DEG - 1);  // p_{c-1} of check 0 does not exist
                     float v = valid ? *lat_f(adr[i]) : INFINITY;
                     const float mag = (idxo == js) ? c1o : c2o;
@@ -129,10 +130,10 @@ ldpc_lat_kernel(const LdpcKParams p)
                 if (ncf > 0) {
                     uint32_t prev = 0u;
                     for (uint32_t i = 0; i < ncf; i++) {
-                        const uint32_t lvl = T[48 + i] >> 8, e = T[32 + i];
+                        const uint32_t lvl = T[LT_CONF_META + i] >> LT_META_LVL_SHIFT, e = T[LT_CONF + i];
                         if (lvl != prev) { __syncthreads(); prev = lvl; }
                         if (act && part == 0) {
-                            const uint32_t d = t4 - (e & 0x7FFu), a = min(d, d + (uint32_t)LAT_ROW) + ((e >> 11) & 0x3FFFFu);
+                            const uint32_t d = t4 - (e & LT_SHIFT_MASK), a = min(d, d + (uint32_t)LAT_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK);
                             float dl = 0.f;
 #pragma unroll
                             for (int k = 0; k < (int)(sizeof(delta) / sizeof(delta[0])); k++) if ((uint32_t)k == i) dl = delta[k];
@@ -155,7 +156,7 @@ ldpc_lat_kernel(const LdpcKParams p)
                         const uint32_t e = part ? (has2 ? T[H + i < DEG ? H + i : 0] : 0u) : T[i];
                         const bool valid = act && (part == 0 || has2);
                         const uint32_t js = (uint32_t)(part ? H + i : i);
-                        const uint32_t d = t4 - (e & 0x7FFu), a = min(d, d + (uint32_t)LAT_ROW) + ((e >> 11) & 0x3FFFFu);
+                        const uint32_t d = t4 - (e & LT_SHIFT_MASK), a = min(d, d + (uint32_t)LAT_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK);
                         const bool absent = r == 0 && t == 0 && js == (uint32_t)(DEG - 1);
                         if (valid && !absent) xs ^= (*lat_f(a) < 0.f) ? SB : 0u;          // (the oracle's hard decision: L < 0, so -0 counts as 0)
                     }

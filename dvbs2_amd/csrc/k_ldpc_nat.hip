@@ -16,6 +16,7 @@
 // path (17 MB of state traffic per frame and decode, no reuse on chip) is HBM-bound and a 4096-frame batch
 // fills only 64 of the chip's 1024 SIMDs.  The QC-layer kernels are the throughput path.
 #include "dvbs2hip_internal.h"
+#include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include "ldpc_det.h"
 
 namespace dvbs2 {
@@ -83,10 +84,10 @@ ldpc_nat_kernel(const NatParams p)
     // row (byte offset) of slot j of check (r, t); NULL slots and the absent p_{c-1} of check 0 read +inf
     auto row_of = [&](const_u32 T, int j, int t, bool absent) -> uint32_t {
         const uint32_t e = T[2 * j], A = T[2 * j + 1];
-        int elem = t - (int)(e & 0xFFFFu);
+        int elem = t - (int)(e & NAT_T0_MASK);
         elem = elem < 0 ? elem + LDPC_Z : elem;
-        const uint32_t bit = A + (uint32_t)elem * ((e >> 16) & 1u ? (uint32_t)q : 1u);
-        return (((e >> 17) & 1u) || absent) ? inf_row : bit * NAT_ROW;
+        const uint32_t bit = A + (uint32_t)elem * ((e >> NAT_PARITY_BIT) & 1u ? (uint32_t)q : 1u);
+        return (((e >> NAT_NULL_BIT) & 1u) || absent) ? inf_row : bit * NAT_ROW;
     };
 
     bool live = f < p.F, ok = false;
@@ -202,10 +203,10 @@ ldpc_nat_spa_kernel(const NatParams p)
     auto gst = [&](uint32_t soff, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs, vo, soff, 0); };
     auto row_of = [&](const_u32 T, int j, int t, bool absent) -> uint32_t {
         const uint32_t e = T[2 * j], A = T[2 * j + 1];
-        int elem = t - (int)(e & 0xFFFFu);
+        int elem = t - (int)(e & NAT_T0_MASK);
         elem = elem < 0 ? elem + LDPC_Z : elem;
-        const uint32_t bit = A + (uint32_t)elem * ((e >> 16) & 1u ? (uint32_t)q : 1u);
-        return (((e >> 17) & 1u) || absent) ? inf_row : bit * NAT_ROW;
+        const uint32_t bit = A + (uint32_t)elem * ((e >> NAT_PARITY_BIT) & 1u ? (uint32_t)q : 1u);
+        return (((e >> NAT_NULL_BIT) & 1u) || absent) ? inf_row : bit * NAT_ROW;
     };
     bool live = f < p.F, ok = false;
     int it = 0, my_ite = 0;
@@ -352,11 +353,11 @@ ldpc_nat_part_kernel(const NatParams p)
     asm volatile("" : "+s"(SB));
     for (int i = lane; i < q * DEGP; i += 64) {
         const int r = i / DEGP, j = i - r * DEGP;
-        const uint32_t e = j < DEG ? p.tab[(size_t)(r * DEG + j) * 2] : (1u << 17), A = j < DEG ? p.tab[(size_t)(r * DEG + j) * 2 + 1] : 0u;
-        const bool null = ((e >> 17) & 1u) != 0u;
-        const uint32_t stride = null ? 0u : (((e >> 16) & 1u) ? (uint32_t)q : 1u) * RB;
+        const uint32_t e = j < DEG ? p.tab[(size_t)(r * DEG + j) * 2] : NAT_NULL, A = j < DEG ? p.tab[(size_t)(r * DEG + j) * 2 + 1] : 0u;
+        const bool null = ((e >> NAT_NULL_BIT) & 1u) != 0u;
+        const uint32_t stride = null ? 0u : (((e >> NAT_PARITY_BIT) & 1u) ? (uint32_t)q : 1u) * RB;
         s_tab[2 * i] = null ? inf_row : A * RB;
-        s_tab[2 * i + 1] = (null ? 0u : (e & 0xFFFFu)) | (stride << 16) | (null ? 0x80000000u : 0u);      // (stride < 2^15: q * RB <= 135 * 256)
+        s_tab[2 * i + 1] = (null ? 0u : (e & NAT_T0_MASK)) | (stride << 16) | (null ? 0x80000000u : 0u);      // (stride < 2^15: q * RB <= 135 * 256)
     }
     __syncthreads();
     auto gldv = [&](uint32_t voff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0)); };
@@ -561,10 +562,10 @@ ldpc_nat_ck_kernel(const NatParams p)
     asm volatile("" : "+s"(SB));
     for (int i = threadIdx.x; i < q * DEG; i += 64 * WV) {
         const uint32_t e = p.tab[(size_t)i * 2], A = p.tab[(size_t)i * 2 + 1];
-        const bool null = ((e >> 17) & 1u) != 0u;
-        const uint32_t stride = null ? 0u : (((e >> 16) & 1u) ? (uint32_t)q : 1u) * RB;
+        const bool null = ((e >> NAT_NULL_BIT) & 1u) != 0u;
+        const uint32_t stride = null ? 0u : (((e >> NAT_PARITY_BIT) & 1u) ? (uint32_t)q : 1u) * RB;
         s_tab[2 * i] = null ? inf_row : A * RB;
-        s_tab[2 * i + 1] = (null ? 0u : (e & 0xFFFFu)) | (stride << 16) | (null ? 0x80000000u : 0u);      // (stride < 2^15: q * RB <= 135 * 128)
+        s_tab[2 * i + 1] = (null ? 0u : (e & NAT_T0_MASK)) | (stride << 16) | (null ? 0x80000000u : 0u);      // (stride < 2^15: q * RB <= 135 * 128)
     }
     __syncthreads();
     auto gldv = [&](uint32_t voff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0)); };

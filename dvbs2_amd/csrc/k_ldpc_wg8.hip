@@ -28,6 +28,7 @@
 //  * VALU per edge: byte-addressed LDS (one add per access), sign/magnitude merges as single
 //    v_and_or / v_bitop3 with the sign mask in an SGPR, store redirection selected on the scalar unit.
 #include "dvbs2hip_internal.h"
+#include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -45,7 +46,7 @@ typedef const __attribute__((address_space(4))) uint32_t *const_u32;
 constexpr int W8_NL = 9;                    // MODE 3: LDS-resident slots per layer (the first ones)
 constexpr int W8_ROW = LDPC_Z * 4;          // bytes per bit-group row
 constexpr int W8_IO = 16;                  // independent loads per lane in flight during frame I/O
-constexpr uint32_t W8_OOB = 0x7FFFF000u;    // voffset beyond every workspace: the store is dropped
+constexpr uint32_t W8_OOB = ATAB_DROPPED;    // voffset beyond every workspace: the store is dropped
 __host__ __device__ __forceinline__ constexpr bool w8_parked(int mode) { return mode == 4 || mode == 5; }      // static hybrid with rows parked in the idle waves' registers
 __host__ __device__ __forceinline__ constexpr bool w8_hybrid(int mode) { return mode == 3 || w8_parked(mode); }
 // (forced: once the kernel had grown by the round-5 output loops the inliner left this one out of line -- 80 calls per layer, the launch 3.7 x as long)
@@ -248,14 +249,14 @@ __device__ __forceinline__ void w8_park_server(const LdpcKParams &p, lds_int *co
 #endif
     auto layer_barriers = [&](int r) __attribute__((always_inline)) {              // the barriers of one min-sum layer, as the working waves take them
         const const_u32 T = tab + r * LDPC_FAST_STRIDE;
-        const uint32_t cinfo = T[28];
-        const int ncf = (int)(cinfo & 0xFFu);
+        const uint32_t cinfo = T[LT_CINFO];
+        const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
         if (ncf > 0) {
             bar_inner();                            // every read of the layer precedes its writes
             bar_inner();                            // the primary writes are in place
             uint32_t prev_lvl = 1u;
-            for (int i = (ncf > 1 && ((cinfo >> 21) & 3u) == 1u) ? 2 : 1; i < ncf; i++) {
-                const uint32_t lvl = T[48 + i] >> 8;
+            for (int i = (ncf > 1 && ((cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK) == 1u) ? 2 : 1; i < ncf; i++) {
+                const uint32_t lvl = T[LT_CONF_META + i] >> LT_META_LVL_SHIFT;
                 if (lvl != prev_lvl) { bar_inner(); prev_lvl = lvl; }
             }
         }
@@ -271,7 +272,7 @@ __device__ __forceinline__ void w8_park_server(const LdpcKParams &p, lds_int *co
 #pragma unroll
         for (int k = 0; k < NR; k++) {
             const uint32_t g = srow[k];
-            const float *Yg = Y + (g == 0xFFFFFFFFu ? 0u : g) * (uint32_t)LDPC_Z;
+            const float *Yg = Y + (g == ROWS_NONE ? 0u : g) * (uint32_t)LDPC_Z;
             R[k][0] = __builtin_nontemporal_load(&Yg[elc]); R[k][1] = __builtin_nontemporal_load(&Yg[elc + LDPC_Z / 3]); R[k][2] = __builtin_nontemporal_load(&Yg[elc + 2 * (LDPC_Z / 3)]);
         }
         __syncthreads();                            // the image is in place
@@ -431,7 +432,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
     // Frames are handed out through a counter (the first one of every workgroup is its block index): with the syndrome early
     // stop frames take 1 .. n_ite iterations, and a fixed round-robin assignment left the workgroups with the slow frames running
     // alone at the end of the launch.
-    // (round 6) The queue can hand the frames out in an order of its own (LdpcKParams::order: the noisiest first, frame_order_launch in k_ldpc.hip) -- opt-in, measured a loss.
+    // (round 6) The queue can hand the frames out in an order of its own (LdpcKParams::order: the noisiest first, frame_order_launch in k_ldpc_generic.hip) -- opt-in, measured a loss.
     for (int qp = blockIdx.x; qp < p.n_frames; ) {
         const int f = p.order ? (int)__builtin_amdgcn_readfirstlane((int)p.order[qp]) : qp;
         // ---- channel LLRs -> posterior image, W8_IO independent loads per lane in flight; packed state := 0
@@ -505,8 +506,8 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                 for (int k = 0; k < PIO; k++) {
                     if ((i0 + k) * 64 + lio < cnt) {
-                        const uint32_t loc = prow[r], off = (loc & 0x7FFFFFFFu) + (uint32_t)(tl0 + tl) * 4u;
-                        if (loc >> 31) gst(off, 0u, v[k]); else lst(off, v[k]);
+                        const uint32_t loc = prow[r], off = (loc & ~ROWS_GLOBAL) + (uint32_t)(tl0 + tl) * 4u;
+                        if (loc >> ROWS_GLOBAL_BIT) gst(off, 0u, v[k]); else lst(off, v[k]);
                     }
                     tl += dq; r += dr;
                     if (r >= q) { r -= q; tl++; }
@@ -582,9 +583,9 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 uint32_t E[DEG];
 #pragma unroll
                 for (int j = 0; j < DEG; j++) E[j] = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, j) : TE[j];
-                const uint32_t prim = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 27) : TE[27], cinfo = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 28) : TE[28],
-                               ce0 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 29) : TE[29], ce1 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 30) : TE[30];
-                const int ncf = (int)(cinfo & 0xFFu);
+                const uint32_t prim = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_PRIM) : TE[LT_PRIM], cinfo = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CINFO) : TE[LT_CINFO],
+                               ce0 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF0) : TE[LT_CONF0], ce1 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF1) : TE[LT_CONF1];
+                const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
                 const bool mask0 = (r == 0) && (t == 0);        // p_{c-1} of check 0 does not exist
                 if (SPA) {
                     // ================= sum-product layer =================
@@ -600,19 +601,19 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     // on the way out and ~20 full-rate operations, against 2.8 boxplus x (2 exp + 2 log + 12) of the forward / backward form.
                     constexpr uint32_t mpitch = W8_ROW;      // message rows packed like the image's (a run-time pitch costs two scalar instructions per access; 1536-byte rows -- whole lines -- measured SLOWER, docs/negative_results.md)
                     const uint32_t mrow = st_base + (uint32_t)(r * DEG) * mpitch;       // messages of this layer: [slot][360 of mpitch / 4]
-                    const uint32_t dupmask = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, 31) : TE[31];
+                    const uint32_t dupmask = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_DUPMASK) : TE[LT_DUPMASK];
                     // the circulant offsets are formed twice, for the loads and again for the stores (an opaque copy of t4 keeps the compiler
                     // from holding 27 of them across the arithmetic: registers, not instructions, are what this layer is short of)
                     uint32_t t4s = t4, MAGM = 0x7FFFFFFFu;
                     asm volatile("" : "+s"(MAGM));                // the magnitude mask as an SGPR operand (VOP3 takes no literal)
-                    auto woff = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4 - (E[j] & 0x7FFu); return min(d, d + (uint32_t)W8_ROW); };
-                    auto woff_s = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4s - (E[j] & 0x7FFu); return min(d, d + (uint32_t)W8_ROW); };
+                    auto woff = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
+                    auto woff_s = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4s - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
                     // (round 5, LDS-only image) ... or read from the per-lane table: slot j's LDS address is one half of a register (a v_and with 0xFFFF or a shift by 16)
                     uint32_t M16 = 0xFFFFu;
                     asm volatile("" : "+v"(M16));                 // in a vector register: the plain two-register v_and_b32 issues every 2.07 cycles, with a literal 2.6, with an SGPR 4.25
                     auto a16 = [&](int j) __attribute__((always_inline)) -> uint32_t { const uint32_t wv = w16[AT16 ? j / 2 : 0]; return (j & 1) ? wv >> 16 : wv & M16; };
                     constexpr int KDS = ldpc_w8_kd(DEG);          // (plan contract, LDS-only image: from this slot on every slot is a primary edge)
-                    auto dup_slot = [&](int i) __attribute__((always_inline)) -> uint32_t { return i == 0 ? (cinfo >> 8) & 31u : i == 1 ? (cinfo >> 16) & 31u : T[48 + i] & 31u; };
+                    auto dup_slot = [&](int i) __attribute__((always_inline)) -> uint32_t { return i == 0 ? (cinfo >> LT_CINFO_SLOT0_SHIFT) & LT_SLOT_MASK : i == 1 ? (cinfo >> LT_CINFO_SLOT1_SHIFT) & LT_SLOT_MASK : T[LT_CONF_META + i] & LT_SLOT_MASK; };
                     // suffix values are kept for every BS-th slot only and rebuilt from there on the way forward (one or two steps off the
                     // critical path): the full array does not fit the 128-VGPR budget of two workgroups per CU beside x[] and u[]
                     constexpr int BS = DEG > 13 ? SPA_BS : 1, NB = (DEG + BS - 1) / BS;      // (the 11- and 13-slot codes have the registers for every suffix value)
@@ -635,7 +636,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                         for (int j = 0; j < DEG; j++) {
                             if (AT16) { x[j] = lld(a16(j)); continue; }
-                            const uint32_t base = (E[j] >> 11) & 0x3FFFFu, wj = woff(j);
+                            const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK, wj = woff(j);
                             if (FWD && j == DEG - 1 && r > 0) x[j] = pfw;                  // p_{c-1}: handed over by layer r - 1
                             else x[j] = w8_slot_lds(MODE, j) ? lld(wj + base) : gld(wj, base);
                         }
@@ -780,7 +781,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                                 // (redirected to the junk row in the other form) is left out -- those are the first slots only
                                 if (j >= KDS || pr) lst(a16(j), x[j] + nw);
                             } else {
-                            const uint32_t base = (E[j] >> 11) & 0x3FFFFu, wj = woff_s(j);
+                            const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK, wj = woff_s(j);
                             if (w8_slot_lds(MODE, j)) {
                                 uint32_t a = wj + (pr ? base : ljunk);
                                 if (j == DEG - 1 && mask0) a = ljunk;
@@ -843,12 +844,12 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                     for (int i = 0; i < LDPC_SPA_MAXC; i++) {
                         if (i >= ncf) break;
-                        const uint32_t e = i == 0 ? ce0 : i == 1 ? ce1 : T[32 + i];
-                        const uint32_t lvl = i == 0 ? 1u : i == 1 ? (cinfo >> 21) & 3u : T[48 + i] >> 8;
+                        const uint32_t e = i == 0 ? ce0 : i == 1 ? ce1 : T[LT_CONF + i];
+                        const uint32_t lvl = i == 0 ? 1u : i == 1 ? (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK : T[LT_CONF_META + i] >> LT_META_LVL_SHIFT;
                         if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                         if (act) {
-                            const uint32_t d = t4 - (e & 0x7FFu);
-                            const uint32_t off = min(d, d + (uint32_t)W8_ROW), base = (e >> 11) & 0x3FFFFu;
+                            const uint32_t d = t4 - (e & LT_SHIFT_MASK);
+                            const uint32_t off = min(d, d + (uint32_t)W8_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             if (MODE != 1) { const float Lv = lld(off + base); lst(off + base, Lv + od[i]); }
                             else { const float Lv = gld(off, base); gst(off, base, Lv + od[i]); }
                         }
@@ -894,7 +895,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
                     for (int j = 0; j < DEG; j++) {
-                        const uint32_t base = (E[j] >> 11) & 0x3FFFFu;
+                        const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
                         if (ATAB && (MODE == 0 || w8_slot_lds(MODE, j))) {
                             // (round 4) the address comes from the per-lane table (requested behind the previous layer's last store): an LDS slot's entry is the whole
                             // LDS address, a global slot's the rotated offset inside its row -- no vector instruction per slot (they were 21 % of the layer's vector issue
@@ -903,7 +904,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                             else v[j] = w8_slot_lds(MODE, j) ? lld(w[j]) : gld1(w[j], base);
                             continue;
                         }
-                        const uint32_t d = t4 - (E[j] & 0x7FFu);
+                        const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK);
                         w[j] = min(d, d + (uint32_t)W8_ROW);
                         if (FWD && j == DEG - 1) { if (r > 0) v[j] = pfw; else v[j] = gld1(w[j], base); }      // p_{c-1}: handed over by layer r - 1
                         else if (w8_slot_lds(MODE, j)) {
@@ -994,7 +995,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #endif
                         if (DREG && j < KDD) dold[j] = nw - dold[j];
                         const bool pr = ((prim >> j) & 1u) != 0u;                             // wave-uniform
-                        const uint32_t base = (E[j] >> 11) & 0x3FFFFu;
+                        const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
                         if (w8_slot_lds(MODE, j) && ATAB) {      // (hybrid images: every LDS slot is covered by the table's pieces)
                             // the table's address is where the value came from; a duplicate edge's plain store (redirected to the junk row without the table) is left out
                             uint32_t a = w[j];
@@ -1037,18 +1038,18 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 // ---- duplicate edges of a bit-group inside this layer: ordered delta updates, level by level.  The
                 //      first two (nearly always all of them, both of level 1) travel with the layer table.
                 if (ncf > 0) {
-                    auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & 0x7FFu); return min(d, d + (uint32_t)W8_ROW); };
+                    auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
                     auto delta_of = [&](uint32_t j) __attribute__((always_inline)) { return w8_unpack<DEG>(cst1, cst2, pkn, j, SB) - w8_unpack<DEG>(c1o, c2o, pko, j, SB); };
-                    const uint32_t j0 = (cinfo >> 8) & 31u, j1 = (cinfo >> 16) & 31u, lvl1 = (cinfo >> 21) & 3u;
+                    const uint32_t j0 = (cinfo >> LT_CINFO_SLOT0_SHIFT) & LT_SLOT_MASK, j1 = (cinfo >> LT_CINFO_SLOT1_SHIFT) & LT_SLOT_MASK, lvl1 = (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK;
                     const bool two = ncf > 1 && lvl1 == 1u;         // entry 1 commutes with entry 0 (another bit-group)
                     // (round 4, LDS-only image) addresses and deltas of the first two entries are ready BEFORE the barrier: behind it only load, add, store remain
                     // (the hybrid images keep round 3's order -- everything behind the barrier: hoisting it measured 1 % SLOWER there, 5.72 against 5.67 ms)
                     uint32_t o0 = 0, b0 = 0, o1 = 0, b1 = 0;
                     float d0 = 0.f, d1 = 0.f;
-                    if (DREG) { o0 = addr_of(ce0); b0 = (ce0 >> 11) & 0x3FFFFu; o1 = addr_of(ce1); b1 = (ce1 >> 11) & 0x3FFFFu; d0 = dold[0]; d1 = dold[KDD > 1 ? 1 : 0]; }
+                    if (DREG) { o0 = addr_of(ce0); b0 = (ce0 >> LT_BASE_SHIFT) & LT_BASE_MASK; o1 = addr_of(ce1); b1 = (ce1 >> LT_BASE_SHIFT) & LT_BASE_MASK; d0 = dold[0]; d1 = dold[KDD > 1 ? 1 : 0]; }
                     __syncthreads();                                // the primary writes of the layer are in place
                     if (act) {
-                        if (!DREG) { o0 = addr_of(ce0); b0 = (ce0 >> 11) & 0x3FFFFu; o1 = addr_of(ce1); b1 = (ce1 >> 11) & 0x3FFFFu; d0 = delta_of(j0); d1 = delta_of(j1); }
+                        if (!DREG) { o0 = addr_of(ce0); b0 = (ce0 >> LT_BASE_SHIFT) & LT_BASE_MASK; o1 = addr_of(ce1); b1 = (ce1 >> LT_BASE_SHIFT) & LT_BASE_MASK; d0 = delta_of(j0); d1 = delta_of(j1); }
                         float L0, L1 = 0.f;
                         if (MODE != 1) { L0 = lld(o0 + b0); if (two) L1 = lld(o1 + b1); }
                         else { L0 = gld(o0, b0); if (two) L1 = gld(o1, b1); }
@@ -1061,18 +1062,18 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                         for (int i = 1; i < KDD; i++) {
                             if (i < (two ? 2 : 1) || i >= ncf) continue;      // (no `break`: the loop has to unroll completely, dold[] lives in registers)
-                            const uint32_t e = T[32 + i], lvl = T[48 + i] >> 8;
-                            const uint32_t off = addr_of(e), base = (e >> 11) & 0x3FFFFu;
+                            const uint32_t e = T[LT_CONF + i], lvl = T[LT_CONF_META + i] >> LT_META_LVL_SHIFT;
+                            const uint32_t off = addr_of(e), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                             if (act) { const float Lv = lld(off + base); lst(off + base, Lv + dold[i]); }
                         }
                     } else
                     for (int i = two ? 2 : 1; i < ncf; i++) {
-                        const uint32_t e = T[32 + i], meta = T[48 + i];
-                        const uint32_t j = meta & 31u, lvl = meta >> 8;
+                        const uint32_t e = T[LT_CONF + i], meta = T[LT_CONF_META + i];
+                        const uint32_t j = meta & LT_SLOT_MASK, lvl = meta >> LT_META_LVL_SHIFT;
                         if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                         if (act) {
-                            const uint32_t off = addr_of(e), base = (e >> 11) & 0x3FFFFu;
+                            const uint32_t off = addr_of(e), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             if (MODE != 1) { const float Lv = lld(off + base); lst(off + base, Lv + delta_of(j)); }
                             else { const float Lv = gld(off, base); gst(off, base, Lv + delta_of(j)); }
                         }
@@ -1115,8 +1116,8 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                         for (int j = 0; j < DEG; j++) {
                             const uint32_t e = T[j];
-                            const uint32_t d = t4 - (e & 0x7FFu);
-                            const uint32_t wo = min(d, d + (uint32_t)W8_ROW), base = (e >> 11) & 0x3FFFFu;
+                            const uint32_t d = t4 - (e & LT_SHIFT_MASK);
+                            const uint32_t wo = min(d, d + (uint32_t)W8_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             Lv[j] = w8_slot_lds(MODE, j) ? lld(wo + base) : gld(wo, base);
                         }
                         if (r == 0 && t == 0) Lv[DEG - 1] = 0.f;                               // absent edge
@@ -1236,7 +1237,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                     for (int k = 0; k < W8_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRP ? l0 + k : NRP - 1) * W8_ROW + t4) : 0.f;
 #pragma unroll
-                    for (int k = 0; k < W8_IO; k++) if (l0 + k < NRP && srow[l0 + k] != 0xFFFFFFFFu) em((int)srow[l0 + k], v[k]);
+                    for (int k = 0; k < W8_IO; k++) if (l0 + k < NRP && srow[l0 + k] != ROWS_NONE) em((int)srow[l0 + k], v[k]);
                 }
             }
         };
@@ -1387,7 +1388,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     if (k > 0 && k % 8 == 0) __builtin_amdgcn_sched_barrier(0);
                     if (SYN) { emit_syn(k, v[k], l0 + k < ldone, r0, r1, pw, nw_c); continue; }
                     const uint32_t gk = grp(kind, l0 + k);
-                    if (kind == 2) { if (gk != 0xFFFFFFFFu) emit_plain((int)gk, v[k]); }      // (an empty register slot: the plan of the DVB-S2 codes leaves none)
+                    if (kind == 2) { if (gk != ROWS_NONE) emit_plain((int)gk, v[k]); }      // (an empty register slot: the plan of the DVB-S2 codes leaves none)
                     else emit_plain((int)gk, v[k]);
                 }
             };

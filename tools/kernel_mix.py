@@ -18,7 +18,12 @@ TRANS = ("v_exp_f32", "v_log_f32", "v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_si
 
 
 def disassemble(tu):
-    o = os.path.join(ROOT, "dvbs2_amd", "lib", tu + ".hip.o")
+    return disassemble_object(os.path.join(ROOT, "dvbs2_amd", "lib", tu + ".hip.o"))
+
+
+def disassemble_object(o):
+    if ".hip_fatbin" not in subprocess.run([LLVM + "/llvm-readelf", "-S", o], capture_output=True, text=True, check=True).stdout:
+        return ""          # host code alone (k_ldpc.hip: the LDPC plan): the object carries no code object
     with tempfile.TemporaryDirectory() as td:
         fb, co = os.path.join(td, "fb"), os.path.join(td, "co")
         subprocess.check_call([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, o], stderr=subprocess.DEVNULL)

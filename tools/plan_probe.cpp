@@ -2,14 +2,63 @@
 // static hybrid search chose -- LDS rows, slots per layer, whether the parity chain sits at the last two slots.
 //   hipcc -std=c++17 -I dvbs2_amd/csrc -I include tools/plan_probe.cpp -L dvbs2_amd/lib -ldvbs2hip -Wl,-rpath,$PWD/dvbs2_amd/lib -o tools/bin/plan_probe
 #include "dvbs2hip_internal.h"
+#include "ldpc_layer_table.h"
 #include "../include/dvbs2hip.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
+#include <cstring>
 using namespace dvbs2;
+
+// `plan_probe digest MODCOD SPA_RULE SMALL_BATCH LDS_LIMIT [--fields] [--bad-address]`: one line that pins the whole plan -- the error string, the scalars that choose the
+// kernel and size its memory in clear, and one FNV-1a-64 over every host field of LdpcPlan in declaration order (scalars as 64-bit values, vectors as length + contents;
+// the device pointers, grid_max and n_cus are not the plan's).  --fields: a line per field, to locate a difference between two builds.  --bad-address: the address table
+// with its first entry set to M (an error string's case).  tests/test_plan_digest.py compares the lines with tests/golden/ldpc_plan_digests.json.
+struct Fnv {
+    unsigned long long h = 0xcbf29ce484222325ull;
+    void bytes(const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; } }
+    void scalar(long long v) { bytes(&v, sizeof v); }
+};
+static int digest_main(int argc, char **argv)
+{
+    bool fields = false, bad = false;
+    std::vector<const char *> a;
+    for (int i = 2; i < argc; i++) { if (!strcmp(argv[i], "--fields")) fields = true; else if (!strcmp(argv[i], "--bad-address")) bad = true; else a.push_back(argv[i]); }
+    if (a.size() != 4) { std::fprintf(stderr, "usage: plan_probe digest MODCOD SPA_RULE SMALL_BATCH LDS_LIMIT [--fields] [--bad-address]\n"); return 2; }
+    dvbs2hip_cfg cfg;
+    if (dvbs2hip_cfg_from_modcod(a[0], &cfg)) { std::printf("unknown modcod\n"); return 1; }
+    std::vector<int32_t> addr(cfg.ldpc_addr, cfg.ldpc_addr + cfg.ldpc_row_ptr[cfg.ldpc_n_rows]);
+    if (bad) addr[0] = cfg.N_ldpc - cfg.K_ldpc;
+    LdpcPlan pl;
+    const std::string e = ldpc_build_plan(pl, cfg.N_ldpc, cfg.K_ldpc, cfg.ldpc_n_rows, cfg.ldpc_row_ptr, addr.data(), cfg.ldpc_lds_groups, (size_t)atol(a[3]), atoi(a[1]), atoi(a[2]) != 0);
+    Fnv all;
+    auto field = [&](const char *name, const void *p, size_t n, long long len) {
+        Fnv f;
+        if (len >= 0) { f.scalar(len); all.scalar(len); }
+        f.bytes(p, n); all.bytes(p, n);
+        if (fields) std::printf("  %-16s %016llx\n", name, f.h);
+    };
+#define SC(x) do { const long long v__ = (long long)pl.x; field(#x, &v__, sizeof v__, -1); } while (0)
+#define VE(x) field(#x, pl.x.data(), pl.x.size() * sizeof pl.x[0], (long long)pl.x.size())
+    SC(N); SC(K); SC(M); SC(q); SC(n_info); SC(n_groups); SC(E); SC(deg_max); SC(ent_stride); SC(lds_groups); SC(c2v_lds); SC(hybrid);
+    SC(lds_post_words); SC(glb_post_words); SC(gwork_words); SC(lds_bytes);
+    VE(entries); VE(layer_deg); VE(layer_lvl); VE(groups);
+    SC(fast); SC(spa); SC(spa_rule); SC(fast_deg); SC(fast_pad); SC(fast_inf_row); SC(fast_mode);
+    VE(nat_tab); VE(nat_haz);
+    SC(fast_cu1); SC(cu1_pairs); SC(fast_wg8); SC(w8_dups_in_lds);
+    VE(w8_tab); VE(w8_rows); VE(w8_atab);
+    SC(w8_st_base); SC(w8_lds_junk); SC(w8_lds_bytes); SC(w8_gwork_words); SC(w8_nl_info); SC(w8_nl); SC(w8_ng_info); SC(w8_ng); SC(w8_park_moves);
+#undef SC
+#undef VE
+    std::printf("digest: '%s' fast %d fast_deg %d fast_pad %d fast_mode %d fast_wg8 %d fast_cu1 %d w8_nl %d w8_ng %d w8_lds_bytes %d w8_gwork_words %d gwork_words %d lds_bytes %zu fnv %016llx\n",
+                e.c_str(), pl.fast, pl.fast_deg, pl.fast_pad, pl.fast_mode, pl.fast_wg8, pl.fast_cu1, pl.w8_nl, pl.w8_ng, pl.w8_lds_bytes, pl.w8_gwork_words, pl.gwork_words, pl.lds_bytes, all.h);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "digest")) return digest_main(argc, argv);
     dvbs2hip_cfg cfg;
     if (dvbs2hip_cfg_from_modcod(argc > 1 ? argv[1] : "QPSK-N_8/9", &cfg)) { std::printf("unknown modcod\n"); return 1; }
     LdpcPlan pl;
@@ -20,9 +69,9 @@ int main(int argc, char **argv)
         // the static hybrid's contract with the kernel: the first NL slots of every layer (and only those) are LDS accesses
         const int NL = pl.fast_mode == 3 ? 9 : ldpc_park_nl(pl.fast_mode);
         bool ok = true;
-        for (int r = 0; r < pl.q; r++) for (int j = 0; j < pl.fast_deg; j++) ok &= (((pl.w8_tab[(size_t)r * LDPC_FAST_STRIDE + j] >> 29) & 1u) != 0u) == (j < NL);
+        for (int r = 0; r < pl.q; r++) for (int j = 0; j < pl.fast_deg; j++) ok &= lt_is_lds(pl.w8_tab[(size_t)r * LDPC_FAST_STRIDE + j]) == (j < NL);
         int swaps = 0;
-        if (pl.fast_mode >= 4) for (size_t i = (size_t)pl.q * LDPC_FAST_STRIDE; i < (size_t)pl.q * LDPC_FAST_STRIDE + (size_t)pl.q * ldpc_park_nr(pl.fast_mode); i++) swaps += pl.w8_tab[i] != 0xFFu;
+        if (pl.fast_mode >= 4) for (size_t i = lt_swaps_at(pl.q); i < lt_swap_masks_at(pl.q, ldpc_park_nr(pl.fast_mode)); i++) swaps += pl.w8_tab[i] != LT_SWAP_NONE;
         std::printf("hybrid: %d LDS slots per layer %s | parked rows %d, row moves per iteration %d, swaps in the table %d\n", NL, ok ? "ok" : "BROKEN", pl.fast_mode >= 4 ? ldpc_park_nr(pl.fast_mode) : 0,
                     pl.w8_park_moves, swaps);
     }
@@ -39,7 +88,7 @@ int main(int argc, char **argv)
         std::vector<int> lds(pl.w8_rows.begin(), pl.w8_rows.begin() + P), reg;
         for (int k = 0; k < NRT; k++) reg.push_back((int)pl.w8_rows[(size_t)P + pl.w8_ng + q + k]);
         const std::vector<int> lds0 = lds, reg0 = reg;
-        const uint32_t *srv = &pl.w8_tab[(size_t)q * LDPC_FAST_STRIDE];
+        const uint32_t *srv = &pl.w8_tab[lt_swaps_at(q)];
         bool ok = pl.w8_ng == 0 && (int)pl.w8_lds_junk == P * LDPC_Z * 4;
         int swaps = 0, dupmax = 0, seen_rows = 0;
         std::vector<char> seen(pl.n_groups, 0);
@@ -49,18 +98,18 @@ int main(int argc, char **argv)
             const uint32_t *T = &pl.w8_tab[(size_t)r * LDPC_FAST_STRIDE];
             // slots 25 / 26 are p_c / p_{c-1}; every slot is an LDS access whose base is the position of a row; a slot's row must not be under way
             std::vector<int> used;
-            for (int j = 0; j < pl.fast_deg; j++) { const uint32_t base = (T[j] >> 11) & 0x3FFFFu; ok &= ((T[j] >> 29) & 1u) && base % (LDPC_Z * 4) == 0 && (int)(base / (LDPC_Z * 4)) < P; used.push_back(lds[base / (LDPC_Z * 4)]); }
+            for (int j = 0; j < pl.fast_deg; j++) { const uint32_t base = lt_base(T[j]); ok &= lt_is_lds(T[j]) && base % (LDPC_Z * 4) == 0 && (int)(base / (LDPC_Z * 4)) < P; used.push_back(lds[base / (LDPC_Z * 4)]); }
             ok &= used[pl.fast_deg - 2] == pl.n_info + r && used[pl.fast_deg - 1] == pl.n_info + (r + q - 1) % q;
-            const int ncf = (int)(T[28] & 0xFF);
+            const int ncf = (int)lt_ncf(T[LT_CINFO]);
             dupmax = std::max(dupmax, ncf);
-            for (int i = 0; i < ncf; i++) ok &= (int)(T[48 + i] & 31u) == i && i < LDPC_CU1_HA && T[32 + i] == T[i] && !((T[27] >> i) & 1u);       // conflict entry i is slot i, in half A, not primary
-            for (int j = ncf; j < pl.fast_deg; j++) ok &= ((T[27] >> j) & 1u) != 0u;                                                                // every other slot is primary
+            for (int i = 0; i < ncf; i++) ok &= (int)lt_meta_slot(T[LT_CONF_META + i]) == i && i < LDPC_CU1_HA && T[LT_CONF + i] == T[i] && !((T[LT_PRIM] >> i) & 1u);       // conflict entry i is slot i, in half A, not primary
+            for (int j = ncf; j < pl.fast_deg; j++) ok &= ((T[LT_PRIM] >> j) & 1u) != 0u;                                                                // every other slot is primary
             // the next layer's rows must already be in place when this layer's swaps run (a swap may take the whole layer), and a swapped row is used by neither
             std::vector<int> next;
             { const uint32_t *Tn = &pl.w8_tab[(size_t)((r + 1) % q) * LDPC_FAST_STRIDE]; (void)Tn; }
             for (int k = 0; k < NRT; k++) {
                 const uint32_t e = srv[(size_t)r * NRT + k];
-                if (e == 0xFFu) continue;
+                if (e == LT_SWAP_NONE) continue;
                 swaps++;
                 ok &= (int)e < P;
                 const int a = lds[e], b = reg[k];
@@ -71,7 +120,7 @@ int main(int argc, char **argv)
         ok &= lds == lds0 && reg == reg0 && seen_rows == pl.n_groups;
         for (int r = 0; r < q; r++) {      // where parity group r starts: its position, or 0xFFFFFFFF and then one of the register slots
             const uint32_t wh = pl.w8_rows[(size_t)P + r];
-            if (wh == 0xFFFFFFFFu) ok &= std::find(reg0.begin(), reg0.end(), pl.n_info + r) != reg0.end();
+            if (wh == ROWS_NONE) ok &= std::find(reg0.begin(), reg0.end(), pl.n_info + r) != reg0.end();
             else ok &= wh % (LDPC_Z * 4) == 0 && lds0[wh / (LDPC_Z * 4)] == pl.n_info + r;
         }
         std::printf("cu1: positions %d pairs %d swaps per iteration %d max duplicate edges per layer %d tables %s\n", P, pl.cu1_pairs, swaps, dupmax, ok ? "ok" : "BROKEN");
@@ -79,10 +128,10 @@ int main(int argc, char **argv)
     if (pl.fast_wg8) {
         for (int r = 0; r < pl.q; r++) {
             const uint32_t *T = &pl.w8_tab[(size_t)r * LDPC_FAST_STRIDE];
-            const int ncf = (int)(T[28] & 0xFF);
+            const int ncf = (int)lt_ncf(T[LT_CINFO]);
             std::printf("layer %2d: ncf %d :", r, ncf);
-            for (int i = 0; i < ncf; i++) std::printf(" (slot %u lvl %u shift %u)", T[48 + i] & 31u, T[48 + i] >> 8, (T[32 + i] & 0x7FFu) / 4);
-            std::printf("  prim %07x\n", T[27]);
+            for (int i = 0; i < ncf; i++) std::printf(" (slot %u lvl %u shift %u)", lt_meta_slot(T[LT_CONF_META + i]), lt_meta_lvl(T[LT_CONF_META + i]), lt_shift(T[LT_CONF + i]) / 4);
+            std::printf("  prim %07x\n", T[LT_PRIM]);
         }
     }
     return 0;

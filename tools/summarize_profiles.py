@@ -83,7 +83,7 @@ if pmc:
         try:
             import kernel_mix as KM
             kname = meta[0].replace("void ", "").split("(")[0].replace("dvbs2::", "")
-            mx = KM.mix("k_ldpc_wg8" if "wg8" in kname else "k_ldpc_cu1" if "cu1" in kname else "k_ldpc", kname)
+            mx = KM.mix("k_ldpc_wg8" if "wg8" in kname else "k_ldpc_cu1" if "cu1" in kname else "k_ldpc_generic", kname)
             cyc_per_valu, vop3_share = mx[0]["cycles_per_valu"], mx[0]["vop3_share"]
         except Exception as e:
             lines.append("(tools/kernel_mix.py failed: %s; every vector instruction priced at 3.97 cycles)" % e)
