@@ -3,7 +3,9 @@
 // api_sync.hip, api_acquire.hip and api_monitor.hip, the tables created here are built in api_tables.hip, what they all share is dvbs2hip_handle.h.
 // The arithmetic is in the k_*.hip files (docs/kernels.md).  No CPU fallback.
 #include "dvbs2hip_handle.h"
+#include "ldpc_dispatch.h"
 #include "dvbs2_tables_gen.h"
+#include <climits>
 #include <new>
 
 using namespace dvbs2;
@@ -86,7 +88,10 @@ static int create_init(dvbs2hip_t *h, const dvbs2hip_cfg *cfg)
         DEV_ALLOC_CHK(h, &lp.d_cu_ctr, (LDPC_CU_CTR_WORDS + LDPC_PROF_WORDS) * sizeof(uint32_t));
         HIPCHK(h, hipMemset(lp.d_cu_ctr, 0, LDPC_CU_CTR_WORDS * sizeof(uint32_t)));
     }
-    lp.grid_max = ldpc_blocks_per_cu(lp) * h->n_cus;
+    // the persistent grid and the tables of the fused chain are those of the kernel that large batches run on
+    const LdpcChoice big = ldpc_choose(lp, {DVBS2HIP_SCHED_QC, INT_MAX, h->n_cus, h->lat_lds_ok, false, false});
+    if (!big.error.empty()) return fail(h, DVBS2HIP_EUNSUPPORTED, big.error);
+    lp.grid_max = ldpc_blocks_per_cu(lp, big) * h->n_cus;
     lp.n_cus = h->n_cus;
     if (const char *ev = getenv("DVBS2HIP_LDPC_GRID_MAX")) { const int g = atoi(ev); if (g >= 1 && g < lp.grid_max) lp.grid_max = g; }   // scaling experiments
     if (lp.gwork_words > 0) DEV_ALLOC_CHK(h, &h->d_gwork, (size_t)lp.grid_max * lp.gwork_words * sizeof(float));
@@ -105,7 +110,7 @@ static int create_init(dvbs2hip_t *h, const dvbs2hip_cfg *cfg)
     const std::vector<uint8_t> g = bch_generator(h->bch);
     if ((int)g.size() - 1 != cfg->K_ldpc - cfg->K_bch || g.size() > 193) return fail(h, DVBS2HIP_EINVAL, "BCH generator degree does not match N_bch - K_bch");
     if ((r = upload(h, &h->d_bch_tab, bch_byte_table(g))) || (r = upload(h, &h->d_bch_shift, bch_shift_table(g, h->K_bch)))) return r;
-    if (lp.fast_wg8 && !lp.fast_cu1) {       // the LDPC kernel's BCH verification in the fused chain
+    if (big.family == LF_WG8) {       // the LDPC kernel's BCH verification in the fused chain
         LdpcSynTables syn;
         e = ldpc_syn_tables(*cfg, lp, g, prbs, syn);
         if (!e.empty()) return fail(h, DVBS2HIP_EINVAL, e);
@@ -220,25 +225,13 @@ int dvbs2hip_set_ldpc_schedule(dvbs2hip_t *h, int32_t schedule)
     return 0;
 }
 
-static bool ldpc_lat_ok(const dvbs2hip_t *h, int F);
+// the kernel of a call of F frames on this handle, as the handle stands
+static LdpcChoice ldpc_choice(const dvbs2hip_t *h, int F) { return ldpc_choose(h->ldpc, {h->ldpc_sched, F, h->n_cus, h->lat_lds_ok, h->early_stop != 0, h->d_syn_pos != nullptr}); }
+
 const char *dvbs2hip_ldpc_kernel_name(const dvbs2hip_t *h)
 {
     if (!h) return "";
-    if (h->ldpc_sched == DVBS2HIP_SCHED_NATURAL) {      // one lane per frame from 32768 frames on, a check's edges over 4 / 8 lanes below (k_ldpc_nat.hip: ldpc_nat_launch)
-        const std::string d = std::to_string(h->ldpc.fast_deg);
-        if (h->ldpc.spa) { const_cast<dvbs2hip_t *>(h)->ldpc_name = "ldpc_nat_spa_kernel<" + d + "," + (h->ldpc.spa_rule == 2 ? "2" : "1") + ">"; return h->ldpc_name.c_str(); }
-        const_cast<dvbs2hip_t *>(h)->ldpc_name = "ldpc_nat_kernel<" + d + "> / ldpc_nat_part_kernel<" + d + ",4|8> / ldpc_nat_ck_kernel<" + d + ",8|4,1|2|4> by batch size";
-        return h->ldpc_name.c_str();
-    }
-    const LdpcPlan &pl = h->ldpc;
-    char buf[96];
-    if (ldpc_lat_ok(h, h->max_frames)) snprintf(buf, sizeof buf, "ldpc_lat_kernel<%d>", pl.fast_deg);      // (every call of this handle is a small batch)
-    else if (!pl.fast) snprintf(buf, sizeof buf, "ldpc_layered_nms_kernel<%d,%s,%s>", pl.ent_stride, pl.hybrid ? "true" : "false", pl.c2v_lds ? "true" : "false");
-    else if (pl.fast_cu1 && pl.spa) snprintf(buf, sizeof buf, "ldpc_cu1_kernel<%d,%d>", pl.fast_deg, pl.spa_rule == 3 ? 3 : 1);
-    else if (pl.fast_cu1) snprintf(buf, sizeof buf, "ldpc_cu1_kernel<%d>", pl.fast_deg);
-    else if (pl.spa) snprintf(buf, sizeof buf, "ldpc_wg8_kernel<%d,%d,%d>", pl.fast_deg, pl.fast_mode, pl.spa_rule);
-    else snprintf(buf, sizeof buf, "ldpc_wg8_kernel<%d,%d>", pl.fast_deg, pl.fast_mode);
-    const_cast<dvbs2hip_t *>(h)->ldpc_name = buf;
+    const_cast<dvbs2hip_t *>(h)->ldpc_name = ldpc_choice_name(ldpc_choice(h, h->max_frames));      // (the small-batch kernel where every call of this handle is a small batch)
     return h->ldpc_name.c_str();
 }
 
@@ -324,27 +317,11 @@ int dvbs2hip_get_sizes(const dvbs2hip_t *h, dvbs2hip_sizes *o)
 }
 
 // ------------------------------------------------------------------ a1
-static bool env_is(const char *name, char c) { const char *e = getenv(name); return e && e[0] == c; }
-// the LDPC kernel can write the chain's output socket itself (descrambled info bits of a frame the BCH stage leaves alone)
-// (round 6) a call of at most one frame per CU on a code whose image and packed state fit the LDS can run on the two-lanes-per-check kernel (k_ldpc_lat.hip) -- OPT-IN,
-// DVBS2HIP_LDPC_LAT=1: bit-exact, and measured SLOWER than the lone workgroup of k_ldpc_wg8.hip (one 32APSK-S 3/4 frame: 210 against 177 us; QPSK-S 8/9: 178 against 141):
-// splitting a check over two lanes halves a wave's work per layer but not the SIMDs' -- the same vector instructions issue from twice the waves (docs/negative_results.md)
-static bool ldpc_lat_ok(const dvbs2hip_t *h, int F)
-{
-    const char *e = getenv("DVBS2HIP_LDPC_LAT");
-    const size_t lds = ldpc_lat_lds_bytes(h->ldpc);
-    return e && e[0] == '1' && h->ldpc_sched == DVBS2HIP_SCHED_QC && F <= h->n_cus && lds > 0 && lds <= 160 * 1024 - 512 && h->lat_lds_ok;
-}
-
-static bool ldpc_writes_info(const dvbs2hip_t *h) { return h->ldpc.fast_wg8 && h->ldpc_sched == DVBS2HIP_SCHED_QC && !getenv("DVBS2HIP_CHAIN_UNFUSED"); }
-
-// (round 5) ... and check the BCH remainder of what it outputs: the BCH stage then decodes the flagged frames only (DVBS2HIP_CHAIN_SYN=0: round 4's form, the BCH stage
-// forms the syndromes of every frame from the packed hard decisions)
-static bool ldpc_verifies_bch(const dvbs2hip_t *h) { const char *e = getenv("DVBS2HIP_CHAIN_SYN"); return ldpc_writes_info(h) && h->d_syn_pos && !h->ldpc.fast_cu1 && !(e && e[0] == '0'); }
-
-static int ldpc_dev(dvbs2hip_t *h, const float *Y, int8_t *CWD, int32_t *V, uint32_t *packed, float *post, int32_t *ites, int F, int32_t *info_out = nullptr,
+// ch: ldpc_choice(h, F).  info_out / bch_flag only where ch.writes_info / ch.writes_bch
+static int ldpc_dev(dvbs2hip_t *h, const LdpcChoice &ch, const float *Y, int8_t *CWD, int32_t *V, uint32_t *packed, float *post, int32_t *ites, int F, int32_t *info_out = nullptr,
                     uint8_t *bch_flag = nullptr, int8_t *cwd_bch = nullptr)
 {
+    if (!ch.error.empty()) return fail(h, DVBS2HIP_EUNSUPPORTED, ch.error);
     LdpcKParams p;
     memset(&p, 0, sizeof p);
     p.llr = Y; p.bits = V; p.packed = packed; p.cwd = CWD; p.post = post; p.ites = ites; p.gwork = h->d_gwork;
@@ -360,28 +337,20 @@ static int ldpc_dev(dvbs2hip_t *h, const float *Y, int8_t *CWD, int32_t *V, uint
             if (!pl.d_nat_tab && upload(h, &pl.d_nat_tab, pl.nat_tab)) { (void)dev_free(h, &pl.d_nat_tab); return DVBS2HIP_EHIP; }
             if (!pl.d_nat_haz && upload(h, &pl.d_nat_haz, pl.nat_haz)) { (void)dev_free(h, &pl.d_nat_haz); return DVBS2HIP_EHIP; }
         }
-        Timer tm(h, DVBS2HIP_K_LDPC);
-        HIPCHK(h, ldpc_nat_launch(pl, p, h->d_nat_work, h->stream));
-        return 0;
-    }
-    if (ldpc_lat_ok(h, F) && !info_out) {
-        Timer tm(h, DVBS2HIP_K_LDPC);
-        HIPCHK(h, ldpc_lat_launch(h->ldpc, p, h->stream));
-        return 0;
     }
     Timer tm(h, DVBS2HIP_K_LDPC);
     // (round 6, measured NEGATIVE and therefore opt-in: DVBS2HIP_LDPC_ORDER=1) with the stopping rule the work queue can hand out the noisiest frames first
     // (frame_order_launch).  Same-box A/B of the reference's configuration, 2 M frames per point: 8.30 / 13.33 / 18.05 Gb/s at 3.6 / 3.7 / 3.8 dB in index order against
     // 8.16 / 13.09 / 17.98 ordered (three clones: 22.5 -> 21.3 at 3.8 dB; QPSK-N: -4 %): the queue already balances the workgroups, the frames that run to the cap are not
     // what a launch waits for -- the two small kernels and the lost locality cost more than the order gives (docs/negative_results.md, round 6).
-    if (h->early_stop && h->ldpc.fast_wg8 && F >= (h->ldpc.fast_cu1 ? 2 : 4) * h->n_cus && env_is("DVBS2HIP_LDPC_ORDER", '1')) {
+    if (ch.takes_order) {
         void *dord;
         int r = ensure(h, B_ORDER, (size_t)F * 8, &dord);
         if (r) return r;
         HIPCHK(h, frame_order_launch(Y, (float *)dord + F, (uint32_t *)dord, F, h->N_ldpc, h->stream));
         p.order = (const uint32_t *)dord;
     }
-    HIPCHK(h, ldpc_launch(h->ldpc, p, h->stream));
+    HIPCHK(h, ldpc_launch(h->ldpc, ch, p, h->d_nat_work, h->stream));
     return 0;
 }
 
@@ -389,7 +358,7 @@ int dvbs2hip_ldpc_decode_siho_dev(dvbs2hip_t *h, const float *Y_N, int8_t *CWD, 
 {
     int r = check_frames(h, F); if (r) return r;
     if (!Y_N || !V_K) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
-    return ldpc_dev(h, Y_N, CWD, V_K, nullptr, nullptr, nullptr, F);
+    return ldpc_dev(h, ldpc_choice(h, F), Y_N, CWD, V_K, nullptr, nullptr, nullptr, F);
 }
 
 int dvbs2hip_ldpc_decode_siho_post(dvbs2hip_t *h, const float *Y_N, int8_t *CWD, int32_t *V_K, float *post, int32_t *ites, int32_t F)
@@ -400,7 +369,7 @@ int dvbs2hip_ldpc_decode_siho_post(dvbs2hip_t *h, const float *Y_N, int8_t *CWD,
     if (post) outs.push_back({post, B_AUX0, nin});          // (asked for or not staged at all: the decoder takes null for "not wanted")
     if (ites) outs.push_back({ites, B_AUX1, (size_t)F * 4});
     return host_call(h, F, !post && !ites, {{Y_N, B_IN, nin}}, outs, [&](void *const *i, void *const *o, int nf) {
-        return ldpc_dev(h, (const float *)i[0], (int8_t *)o[1], (int32_t *)o[0], nullptr, (float *)(post ? o[2] : nullptr), (int32_t *)(ites ? o[outs.size() - 1] : nullptr), nf);
+        return ldpc_dev(h, ldpc_choice(h, nf), (const float *)i[0], (int8_t *)o[1], (int32_t *)o[0], nullptr, (float *)(post ? o[2] : nullptr), (int32_t *)(ites ? o[outs.size() - 1] : nullptr), nf);
     });
 }
 
@@ -586,12 +555,13 @@ static int rx_bb_any_dev(dvbs2hip_t *h, const float *pl, const float *const *src
     // the LDPC kernel writes the descrambled info bits of every frame straight into the output socket (what the BCH stage outputs for a
     // frame it does not correct: nearly all of them behind a converged LDPC decoder); the BCH stage then only checks the syndromes of the
     // packed hard decisions and flips the bits it corrects -- its 4 K_bch output bytes per frame were 90 % of its time
-    const bool fused_out = ldpc_writes_info(h) && !ldpc_lat_ok(h, F);      // (the latency kernel of small batches writes the packed hard decisions only: the BCH stage does the rest)
+    const LdpcChoice ch = ldpc_choice(h, F);
+    const bool fused_out = ch.writes_info;
     // (round 5) ... and forms the frame's BCH remainder r(x) mod g(x) from the hard decisions it outputs: a frame whose remainder is zero is finished (information bits and
     // both CWD flags written by the LDPC kernel); the BCH stage rebuilds and decodes the flagged frames only
     void *dflag = nullptr;
-    if (fused_out && ldpc_verifies_bch(h) && (r = ensure(h, B_BCHFLAG, (size_t)F, &dflag))) return r;
-    if ((r = ldpc_dev(h, (const float *)dllr, cwd_l, nullptr, (uint32_t *)dpk, nullptr, nullptr, F, fused_out ? info : nullptr, (uint8_t *)dflag, cwd_b))) return r;
+    if (ch.writes_bch && (r = ensure(h, B_BCHFLAG, (size_t)F, &dflag))) return r;
+    if ((r = ldpc_dev(h, ch, (const float *)dllr, cwd_l, nullptr, (uint32_t *)dpk, nullptr, nullptr, F, fused_out ? info : nullptr, (uint8_t *)dflag, cwd_b))) return r;
     return bch_dev(h, nullptr, (const uint32_t *)dpk, cwd_b, info, true, F, fused_out, (const uint8_t *)dflag);
 }
 

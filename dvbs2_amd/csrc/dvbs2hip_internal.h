@@ -175,17 +175,13 @@ constexpr int LDPC_SYN_RED = 640;       // entries x^k mod g(x), k = 0 .. 639, o
 constexpr int LDPC_SPA_MAXC = 6;       // SPA: duplicate edges per layer whose old messages a lane keeps in registers (the DVB-S2 codes have at most 6)
 constexpr int NAT_AHEAD = 24;           // k_ldpc_nat.hip, lanes-per-frame form: checks whose loads are in flight ahead of the one being computed (8 lanes per frame; 12 with 4 lanes per frame)
 constexpr int NAT_HAZ_WINDOW = NAT_AHEAD + 1;
-hipError_t ldpc_nat_launch(const LdpcPlan &pl, const LdpcKParams &kp, float *work, hipStream_t s);
 size_t ldpc_nat_group_words(const LdpcPlan &pl);
 hipError_t ldpc_wg8_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s);
-hipError_t ldpc_cu1_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s);
-int ldpc_wg8_blocks_per_cu(const LdpcPlan &pl);
+int ldpc_wg8_blocks_per_cu(const LdpcPlan &pl);      // (choosing and launching a call's kernel: ldpc_dispatch.h)
 
 // builds the layer tables; returns empty string on success, else the error text
 std::string ldpc_build_plan(LdpcPlan &pl, int N, int K, int n_rows, const int32_t *row_ptr,
                             const int32_t *addr, int lds_groups_req, size_t lds_limit_bytes, int spa_rule = 0, bool small_batch = false);      // small_batch: the handle never sees more frames than CUs      // spa_rule: LdpcPlan::spa_rule
-hipError_t ldpc_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s);
-int ldpc_blocks_per_cu(const LdpcPlan &pl);
 
 // ---------------------------------------------------------------- BCH (a2)
 struct BchPlan {
@@ -232,8 +228,6 @@ struct FrontKParams {
     int32_t sep, sep_ax[2];
     float sep_g[2], sep_h[2];
 };
-size_t ldpc_lat_lds_bytes(const LdpcPlan &pl);                                    // k_ldpc_lat.hip: small batches of short frames, two lanes per check (0: not applicable)
-hipError_t ldpc_lat_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s);
 hipError_t frame_order_launch(const float *llr, float *metric, uint32_t *order, int F, int N, hipStream_t s);      // k_ldpc_generic.hip: the work queue's order for launches with the stopping rule (noisiest frames first)
 hipError_t front_rx_launch(FrontKParams p, hipStream_t s);                     // a7+a6+a3+a4 fused, in = pl frames
 hipError_t demod_launch(FrontKParams p, bool deinterleave, hipStream_t s);     // a3 (+a4), in = xfec frames, sigma_in required

@@ -16,7 +16,7 @@
 //   * Same layer tables as k_ldpc_wg8.hip (one dword per slot: byte shift | LDS byte offset of the row's position in THAT layer), same stopping rule, outputs and
 //     work queue (frames handed out through a counter).
 // Same schedule and arithmetic as the oracle (bit-exact): tests/test_ldpc_gpu.py, tests/test_golden_gpu.py.
-#include "dvbs2hip_internal.h"
+#include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include <cstdio>
 #include <cstdlib>
@@ -800,30 +800,16 @@ ldpc_cu1_kernel(const LdpcKParams p)
 #endif
 }
 
-hipError_t ldpc_cu1_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s)
+static_assert(C1_THREADS == LDPC_CU1_THREADS, "ldpc_dispatch.h describes this kernel's workgroup");
+template <int DEG, int SPA>
+static hipError_t cu1_inst(const LdpcPlan &pl, const LdpcKParams &p, hipStream_t s)
 {
-    p.cu_ctr = pl.d_cu_ctr;
-    p.w8.tab = pl.d_w8_tab; p.w8.rows = pl.d_w8_rows; p.w8.atab = nullptr;
-    p.w8.st_base = pl.w8_st_base; p.w8.lds_junk = pl.w8_lds_junk; p.w8.lds_bytes = pl.w8_lds_bytes; p.w8.pad = 0;
-    p.w8.nl_info = pl.w8_nl_info; p.w8.nl = pl.w8_nl; p.w8.ng_info = pl.w8_ng_info; p.w8.ng = pl.w8_ng;
-    p.spa_cap = pl.spa_rule == 3 ? LDPC_SPA_CAP : INFINITY;
-    p.N = pl.N; p.K = pl.K; p.M = pl.M; p.q = pl.q; p.n_info = pl.n_info; p.n_groups = pl.n_groups;
-    p.gwork_words = pl.w8_gwork_words;
-    if (pl.fast_deg != 27 || pl.cu1_pairs != 2 * ldpc_cu1_nrg()) return hipErrorInvalidValue;
-    auto kern = pl.spa_rule == 3 ? ldpc_cu1_kernel<27, 3> : pl.spa ? ldpc_cu1_kernel<27, 1> : ldpc_cu1_kernel<27, 0>;
-    static size_t configured_dev[3][64] = {{0}, {0}, {0}};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t &configured = configured_dev[pl.spa_rule == 3 ? 2 : pl.spa ? 1 : 0][dev & 63];
     const size_t lds = (size_t)pl.w8_lds_bytes;
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
+    hipError_t e = ldpc_dyn_lds<ldpc_cu1_kernel<DEG, SPA>>(lds);
+    if (e != hipSuccess) return e;
     const int grid = p.n_frames < pl.grid_max ? p.n_frames : pl.grid_max;
-    if (p.cu_ctr) { hipError_t e = hipMemsetAsync(p.cu_ctr, 0, LDPC_CU_CTR_WORDS * sizeof(uint32_t), s); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C1_THREADS), lds, s, p);
+    if (p.cu_ctr && (e = hipMemsetAsync(p.cu_ctr, 0, LDPC_CU_CTR_WORDS * sizeof(uint32_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL((ldpc_cu1_kernel<DEG, SPA>), dim3(grid), dim3(C1_THREADS), lds, s, p);
 #ifdef LDPC_PHASE_PROF
     {   // development aid: average ticks per phase over the working waves
         (void)hipStreamSynchronize(s);
@@ -851,6 +837,25 @@ hipError_t ldpc_cu1_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s)
     }
 #endif
     return hipGetLastError();
+}
+
+// every instantiation of the kernel, <DEG, SPA>
+static const struct Cu1Inst { int targ[2]; hipError_t (*launch)(const LdpcPlan &, const LdpcKParams &, hipStream_t); } cu1_insts[] = {{{27, 0}, cu1_inst<27, 0>}, {{27, 1}, cu1_inst<27, 1>}, {{27, 3}, cu1_inst<27, 3>}};
+static const Cu1Inst *cu1_find(const int *targ)
+{
+    for (const Cu1Inst &i : cu1_insts) if (i.targ[0] == targ[0] && i.targ[1] == targ[1]) return &i;
+    return nullptr;
+}
+bool ldpc_cu1_has(const int *targ) { return cu1_find(targ) != nullptr; }
+
+hipError_t ldpc_cu1_launch(const LdpcPlan &pl, const LdpcChoice &ch, LdpcKParams p, hipStream_t s)
+{
+    const Cu1Inst *i = cu1_find(ch.targ);
+    if (!i) return hipErrorInvalidValue;
+    ldpc_plan_params(pl, p);
+    p.cu_ctr = pl.d_cu_ctr; p.w8.atab = nullptr; p.w8.pad = 0;
+    p.gwork_words = pl.w8_gwork_words;
+    return i->launch(pl, p, s);
 }
 
 }  // namespace dvbs2

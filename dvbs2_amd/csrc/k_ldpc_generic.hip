@@ -2,8 +2,8 @@
 // lane t = check t of the layer; the schedule, the compressed check->variable state and the storage policy are described in k_ldpc.hip, whose plan builds this
 // kernel's tables (LdpcPlan::entries, groups, layer_lvl).  It is the fallback for codes the fast kernels reject -- check degree above 27 or more than 16
 // duplicate edges per layer -- and the subject of `DVBS2HIP_LDPC_PATH=generic` experiments; every DVB-S2 code shipped here runs on k_ldpc_wg8.hip or
-// k_ldpc_cu1.hip.  ldpc_launch / ldpc_blocks_per_cu dispatch between the three.  Behind it: the two small kernels of the work queue's opt-in frame order.
-#include "dvbs2hip_internal.h"
+// k_ldpc_cu1.hip.  ldpc_dispatch.hip chooses between the three.  Behind it: the two small kernels of the work queue's opt-in frame order.
+#include "ldpc_dispatch.h"
 
 namespace dvbs2 {
 
@@ -239,23 +239,14 @@ ldpc_layered_nms_kernel(const LdpcKParams p)
 template <int DEG, bool HYBRID, bool C2V_LDS>
 static hipError_t launch_inst(const LdpcPlan &pl, const LdpcKParams &p, hipStream_t s)
 {
-    auto kern = ldpc_layered_nms_kernel<DEG, HYBRID, C2V_LDS>;
-    static size_t configured_dev[64] = {0};
-    int dev__ = 0;
-    (void)hipGetDevice(&dev__);
-    size_t &configured = configured_dev[dev__ & 63];
-    if (pl.lds_bytes > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-        if (e != hipSuccess) return e;
-        configured = pl.lds_bytes;
-    }
+    const hipError_t e = ldpc_dyn_lds<ldpc_layered_nms_kernel<DEG, HYBRID, C2V_LDS>>(pl.lds_bytes);
+    if (e != hipSuccess) return e;
     const int grid = p.n_frames < pl.grid_max ? p.n_frames : pl.grid_max;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LDPC_THREADS), pl.lds_bytes, s, p);
+    hipLaunchKernelGGL((ldpc_layered_nms_kernel<DEG, HYBRID, C2V_LDS>), dim3(grid), dim3(LDPC_THREADS), pl.lds_bytes, s, p);
     return hipGetLastError();
 }
 
-// resident workgroups per CU for the instantiation the plan selects (persistent grid size)
+// resident workgroups per CU of an instantiation (persistent grid size)
 template <int DEG, bool HYBRID, bool C2V_LDS>
 static int occ_inst(const LdpcPlan &pl)
 {
@@ -265,31 +256,31 @@ static int occ_inst(const LdpcPlan &pl)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, LDPC_THREADS, pl.lds_bytes) != hipSuccess) nb = 1;
     return nb < 1 ? 1 : nb;
 }
-int ldpc_blocks_per_cu(const LdpcPlan &pl)
+// every instantiation of the kernel, <DEG, HYBRID, C2V_LDS>
+static_assert(LDPC_MAX_SLOTS == 27, "the table's second half is the LDPC_MAX_SLOTS form");
+static const struct GenericInst { int targ[3]; hipError_t (*launch)(const LdpcPlan &, const LdpcKParams &, hipStream_t); int (*occ)(const LdpcPlan &); } generic_insts[] = {
+    {{13, 0, 0}, launch_inst<13, false, false>, occ_inst<13, false, false>}, {{13, 0, 1}, launch_inst<13, false, true>, occ_inst<13, false, true>},
+    {{13, 1, 0}, launch_inst<13, true, false>, occ_inst<13, true, false>},   {{13, 1, 1}, launch_inst<13, true, true>, occ_inst<13, true, true>},
+    {{27, 0, 0}, launch_inst<27, false, false>, occ_inst<27, false, false>}, {{27, 0, 1}, launch_inst<27, false, true>, occ_inst<27, false, true>},
+    {{27, 1, 0}, launch_inst<27, true, false>, occ_inst<27, true, false>},   {{27, 1, 1}, launch_inst<27, true, true>, occ_inst<27, true, true>},
+};
+static const GenericInst *generic_find(const int *targ)
 {
-    if (pl.fast && pl.fast_cu1) return 1;
-    if (pl.fast && pl.fast_wg8) return ldpc_wg8_blocks_per_cu(pl);
-    const bool small = pl.ent_stride == 13;
-#define OCC(H, C) (small ? occ_inst<13, H, C>(pl) : occ_inst<LDPC_MAX_SLOTS, H, C>(pl))
-    if (pl.hybrid) return pl.c2v_lds ? OCC(true, true) : OCC(true, false);
-    return pl.c2v_lds ? OCC(false, true) : OCC(false, false);
-#undef OCC
+    for (const GenericInst &i : generic_insts) if (i.targ[0] == targ[0] && i.targ[1] == targ[1] && i.targ[2] == targ[2]) return &i;
+    return nullptr;
 }
+bool ldpc_generic_has(const int *targ) { return generic_find(targ) != nullptr; }
+int ldpc_generic_blocks_per_cu(const LdpcPlan &pl, const LdpcChoice &ch) { const GenericInst *i = generic_find(ch.targ); return i ? i->occ(pl) : 1; }
 
-hipError_t ldpc_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s)
+hipError_t ldpc_generic_launch(const LdpcPlan &pl, const LdpcChoice &ch, LdpcKParams p, hipStream_t s)
 {
-    if (pl.fast && pl.fast_cu1) return ldpc_cu1_launch(pl, p, s);
-    if (pl.fast && pl.fast_wg8) return ldpc_wg8_launch(pl, p, s);
+    const GenericInst *i = generic_find(ch.targ);
+    if (!i) return hipErrorInvalidValue;
+    ldpc_plan_params(pl, p);
     p.entries = pl.d_entries; p.layer_deg = pl.d_layer_deg; p.layer_lvl = pl.d_layer_lvl; p.groups = pl.d_groups;
-    p.N = pl.N; p.K = pl.K; p.M = pl.M; p.q = pl.q; p.n_info = pl.n_info; p.n_groups = pl.n_groups;
     p.ent_stride = pl.ent_stride; p.lds_post_words = pl.lds_post_words; p.glb_post_words = pl.glb_post_words;
     p.gwork_words = pl.gwork_words;
-    const bool small = pl.ent_stride == 13;
-#define DISPATCH(H, C)                                                      \
-    (small ? launch_inst<13, H, C>(pl, p, s) : launch_inst<LDPC_MAX_SLOTS, H, C>(pl, p, s))
-    if (pl.hybrid) return pl.c2v_lds ? DISPATCH(true, true) : DISPATCH(true, false);
-    return pl.c2v_lds ? DISPATCH(false, true) : DISPATCH(false, false);
-#undef DISPATCH
+    return i->launch(pl, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------------------

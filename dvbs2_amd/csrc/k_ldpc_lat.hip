@@ -14,7 +14,7 @@
 // value-equality rule of AFF3CT's min-sum, alpha applied to the two minima: posteriors are BIT-IDENTICAL (tests/test_ldpc_gpu.py).
 // Tables: the LDS-only plan of k_ldpc.hip as it is (w8_tab: slot entries = byte shift | byte offset of the bit-group row << 11, prim mask, conflict list).
 // Min-sum / normalised min-sum only; used by dvbs2hip_api.hip for calls of at most one frame per CU on codes whose image and state fit the LDS.
-#include "dvbs2hip_internal.h"
+#include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 
 namespace dvbs2 {
@@ -197,36 +197,32 @@ ldpc_lat_kernel(const LdpcKParams p)
     }
 }
 
-// the LDS bytes the kernel needs for this plan (image + junk + inf rows, packed state, one flag word), or 0 if the plan is not the LDS-only one
-size_t ldpc_lat_lds_bytes(const LdpcPlan &pl)
+static_assert(LAT_THREADS == LDPC_LAT_THREADS && LAT_ROW == LDPC_LAT_ROW, "ldpc_dispatch.h describes this kernel's workgroup and its LDS");
+template <int DEG>
+static hipError_t lat_inst(size_t lds, int grid, const LdpcKParams &p, hipStream_t s)
 {
-    if (!pl.fast || !pl.fast_wg8 || pl.fast_mode != 0 || pl.spa) return 0;
-    return (size_t)(pl.n_groups + 2) * LAT_ROW + (size_t)pl.M * 12 + 16;
+    const hipError_t e = ldpc_dyn_lds<ldpc_lat_kernel<DEG>>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ldpc_lat_kernel<DEG>, dim3(grid), dim3(LAT_THREADS), lds, s, p);
+    return hipGetLastError();
 }
 
-hipError_t ldpc_lat_launch(const LdpcPlan &pl, LdpcKParams p, hipStream_t s)
+// every instantiation of the kernel, <DEG>
+static const struct LatInst { int deg; hipError_t (*launch)(size_t, int, const LdpcKParams &, hipStream_t); } lat_insts[] = {{27, lat_inst<27>}, {13, lat_inst<13>}, {11, lat_inst<11>}};
+static const LatInst *lat_find(const int *targ)
 {
-    p.w8.tab = pl.d_w8_tab;
-    p.w8.lds_junk = (uint32_t)(pl.n_groups * LAT_ROW);
-    p.N = pl.N; p.K = pl.K; p.M = pl.M; p.q = pl.q; p.n_info = pl.n_info; p.n_groups = pl.n_groups;
-    const size_t lds = ldpc_lat_lds_bytes(pl);
-    if (!lds || (uint32_t)pl.w8_lds_junk != p.w8.lds_junk) return hipErrorInvalidValue;      // (the plan's image has the rows in bit-group order: the tables' offsets assume it)
-    const int grid = p.n_frames < pl.n_cus ? p.n_frames : pl.n_cus;
-#define LAT_CASE(D) \
-    if (pl.fast_deg == D) { \
-        static size_t configured[64] = {0}; \
-        int dev = 0; (void)hipGetDevice(&dev); \
-        if (lds > configured[dev & 63]) { \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ldpc_lat_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e; \
-            configured[dev & 63] = lds; \
-        } \
-        hipLaunchKernelGGL(ldpc_lat_kernel<D>, dim3(grid), dim3(LAT_THREADS), lds, s, p); \
-        return hipGetLastError(); \
-    }
-    LAT_CASE(27) LAT_CASE(13) LAT_CASE(11)
-#undef LAT_CASE
-    return hipErrorInvalidValue;
+    for (const LatInst &i : lat_insts) if (i.deg == targ[0]) return &i;
+    return nullptr;
+}
+bool ldpc_lat_has(const int *targ) { return lat_find(targ) != nullptr; }
+
+// (ldpc_choose has held the plan against what the kernel assumes: the LDS-only min-sum image with its rows in bit-group order, ch.lds_bytes of LDS)
+hipError_t ldpc_lat_launch(const LdpcPlan &pl, const LdpcChoice &ch, LdpcKParams p, hipStream_t s)
+{
+    const LatInst *i = lat_find(ch.targ);
+    if (!i) return hipErrorInvalidValue;
+    ldpc_plan_params(pl, p);
+    return i->launch(ch.lds_bytes, p.n_frames < pl.n_cus ? p.n_frames : pl.n_cus, p, s);
 }
 
 }  // namespace dvbs2

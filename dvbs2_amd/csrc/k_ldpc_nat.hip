@@ -15,7 +15,7 @@
 // It is a validation and large-batch mode, selected with dvbs2hip_set_ldpc_schedule(.., NATURAL): the data
 // path (17 MB of state traffic per frame and decode, no reuse on chip) is HBM-bound and a 4096-frame batch
 // fills only 64 of the chip's 1024 SIMDs.  The QC-layer kernels are the throughput path.
-#include "dvbs2hip_internal.h"
+#include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include "ldpc_det.h"
 
@@ -761,6 +761,8 @@ nat_store_g_kernel(const NatParams p, int G)
     }
 }
 
+// The launchers of the four forms (ldpc_choose picks one by the batch size, the hazard planes and DVBS2HIP_NAT_PARTS): the frames of a group transposed into the workspace, the
+// decoder, the results transposed back.
 template <int DEG, int CK, int WV>
 static hipError_t nat_ck_launch(const LdpcPlan &pl, NatParams p, hipStream_t s)
 {
@@ -773,74 +775,59 @@ static hipError_t nat_ck_launch(const LdpcPlan &pl, NatParams p, hipStream_t s)
     return hipGetLastError();
 }
 
-template <int DEG, int PARTS>
+template <int DEG, int PARTS, int AHEAD>      // AHEAD > 1: the second hazard plane is empty and M divides, loads run AHEAD checks ahead
 static hipError_t nat_part_launch(const LdpcPlan &pl, NatParams p, hipStream_t s)
 {
-    bool clean = true;      // the second hazard plane is empty: loads may run NAT_AHEAD checks ahead
-    for (size_t i = pl.nat_haz.size() / 2; i < pl.nat_haz.size(); i++) clean &= pl.nat_haz[i] == 0u;
     constexpr int G = 64 / PARTS, SPP = (DEG + PARTS - 1) / PARTS;
     p.grp_words = (uint32_t)((size_t)(pl.N + 2 + 3 * pl.M) * G);
     const int groups = (p.F + G - 1) / G, tiles = (pl.N + 63) / 64;
     hipLaunchKernelGGL(nat_load_g_kernel, dim3(tiles, groups), dim3(256), 0, s, p, G);
-    constexpr int AH = PARTS == 8 ? NAT_AHEAD : NAT_AHEAD / 2;
-    if (clean && pl.M % AH == 0) hipLaunchKernelGGL((ldpc_nat_part_kernel<DEG, PARTS, AH>), dim3(groups), dim3(64), (size_t)pl.q * SPP * PARTS * 8, s, p);
-    else hipLaunchKernelGGL((ldpc_nat_part_kernel<DEG, PARTS, 1>), dim3(groups), dim3(64), (size_t)pl.q * SPP * PARTS * 8, s, p);
+    hipLaunchKernelGGL((ldpc_nat_part_kernel<DEG, PARTS, AHEAD>), dim3(groups), dim3(64), (size_t)pl.q * SPP * PARTS * 8, s, p);
     hipLaunchKernelGGL(nat_store_g_kernel, dim3(tiles, groups), dim3(256), 0, s, p, G);
     return hipGetLastError();
 }
 
-hipError_t ldpc_nat_launch(const LdpcPlan &pl, const LdpcKParams &kp, float *work, hipStream_t s)
+template <int DEG, int RULE>      // one lane per frame: min-sum (RULE 0, ldpc_nat_kernel) or sum-product in the reference's sweep order (ldpc_nat_spa_kernel)
+static hipError_t nat_lane_launch(const LdpcPlan &pl, NatParams p, hipStream_t s)
 {
+    p.grp_words = (uint32_t)ldpc_nat_group_words(pl);
+    const int groups = (p.F + 63) / 64, tiles = (pl.N + 63) / 64;
+    hipLaunchKernelGGL(nat_load_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
+    if constexpr (RULE == 0) hipLaunchKernelGGL(ldpc_nat_kernel<DEG>, dim3(groups), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((ldpc_nat_spa_kernel<DEG, RULE>), dim3(groups), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(nat_store_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// every instantiation of the four kernels: ldpc_nat_kernel<DEG>, ldpc_nat_spa_kernel<DEG, RULE>, ldpc_nat_part_kernel<DEG, PARTS, AHEAD>, ldpc_nat_ck_kernel<DEG, CK, WV>
+static_assert(NAT_AHEAD == 24, "the part kernels' table spells NAT_AHEAD and NAT_AHEAD / 2 out");
+struct NatInst { LdpcFamily family; int targ[3]; hipError_t (*launch)(const LdpcPlan &, NatParams, hipStream_t); };
+template <int DEG>
+static constexpr NatInst nat_insts[13] = {
+    {LF_NAT_LANE, {DEG, 0, 0}, nat_lane_launch<DEG, 0>}, {LF_NAT_SPA, {DEG, 1, 0}, nat_lane_launch<DEG, 1>}, {LF_NAT_SPA, {DEG, 2, 0}, nat_lane_launch<DEG, 2>},
+    {LF_NAT_PART, {DEG, 4, 12}, nat_part_launch<DEG, 4, 12>}, {LF_NAT_PART, {DEG, 4, 1}, nat_part_launch<DEG, 4, 1>},
+    {LF_NAT_PART, {DEG, 8, 24}, nat_part_launch<DEG, 8, 24>}, {LF_NAT_PART, {DEG, 8, 1}, nat_part_launch<DEG, 8, 1>},
+    {LF_NAT_CK, {DEG, 8, 4}, nat_ck_launch<DEG, 8, 4>}, {LF_NAT_CK, {DEG, 8, 2}, nat_ck_launch<DEG, 8, 2>}, {LF_NAT_CK, {DEG, 8, 1}, nat_ck_launch<DEG, 8, 1>},
+    {LF_NAT_CK, {DEG, 4, 4}, nat_ck_launch<DEG, 4, 4>}, {LF_NAT_CK, {DEG, 4, 2}, nat_ck_launch<DEG, 4, 2>}, {LF_NAT_CK, {DEG, 4, 1}, nat_ck_launch<DEG, 4, 1>},
+};
+static const NatInst *nat_find(LdpcFamily family, const int *targ)
+{
+    const NatInst *insts = targ[0] == 27 ? nat_insts<27> : targ[0] == 13 ? nat_insts<13> : targ[0] == 11 ? nat_insts<11> : nullptr;
+    for (int i = 0; insts && i < 13; i++) if (insts[i].family == family && insts[i].targ[1] == targ[1] && insts[i].targ[2] == targ[2]) return &insts[i];
+    return nullptr;
+}
+bool ldpc_nat_has(LdpcFamily family, const int *targ) { return nat_find(family, targ) != nullptr; }
+
+hipError_t ldpc_nat_launch(const LdpcPlan &pl, const LdpcChoice &ch, const LdpcKParams &kp, float *work, hipStream_t s)
+{
+    const NatInst *i = nat_find(ch.family, ch.targ);
+    if (!i) return hipErrorInvalidValue;
     NatParams p;
     p.llr = kp.llr; p.work = work; p.tab = pl.d_nat_tab; p.haz = pl.d_nat_haz;
     p.bits = kp.bits; p.packed = kp.packed; p.cwd = kp.cwd; p.post = kp.post; p.ites = kp.ites;
     p.N = pl.N; p.K = pl.K; p.M = pl.M; p.q = pl.q; p.F = kp.n_frames; p.n_ite = kp.n_ite; p.early_stop = kp.early_stop; p.alpha = kp.alpha;
-    if (pl.spa) {      // sum-product in the reference's sweep order: one lane per frame (ldpc_nat_spa_kernel)
-        p.spa_cap = pl.spa_rule == 3 ? LDPC_SPA_CAP : INFINITY;
-        p.grp_words = (uint32_t)ldpc_nat_group_words(pl);
-        const int groups = (kp.n_frames + 63) / 64, tiles = (pl.N + 63) / 64;
-        hipLaunchKernelGGL(nat_load_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
-#define NAT_SPA_CASE(D) \
-        if (pl.fast_deg == D) { if (pl.spa_rule == 2) hipLaunchKernelGGL((ldpc_nat_spa_kernel<D, 2>), dim3(groups), dim3(64), 0, s, p); else hipLaunchKernelGGL((ldpc_nat_spa_kernel<D, 1>), dim3(groups), dim3(64), 0, s, p); }
-        NAT_SPA_CASE(27) NAT_SPA_CASE(13) NAT_SPA_CASE(11)
-#undef NAT_SPA_CASE
-        hipLaunchKernelGGL(nat_store_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
-    // Form by the size of the batch.  Codes whose second hazard plane is empty and whose check count divides by eight (every DVB-S2 code of the library) run CONSECUTIVE CHECKS
-    // side by side (ldpc_nat_ck_kernel).  (round 5) While the batch gives every CU at most ONE workgroup of 16 frames (4096 frames on 256 CUs: the BASELINE batch): 8 checks x 8
-    // frames per wave, TWO waves per workgroup -- the sweep's step time follows the number of cache lines the waves of a CU touch per group of checks (every slot of every check
-    // is one line access per wave whatever the row holds), and rows of 32 frames (the two forms below) put four waves on half the CUs at this size: 4096 normal frames 35.3 -> 24.9-26.8
-    // ms = 115 -> 153-165 k frames/s, 1024 frames 31.4 -> 19.3 ms; with two such workgroups on a CU the time doubles (6144 frames: 47.5 against 36.5 ms), so from there on
-    // 4 checks x 16 frames, two waves per workgroup = rows of 32 frames (8192 frames: 217 k; 16384+: 245-260 k; one lane per frame reached 171 k at 32768).  Any other code: one lane per
-    // frame when that alone gives every SIMD a wave, else a check's edges over 4 or 8 lanes.  DVBS2HIP_NAT_PARTS = 1 | 4 | 8 (those forms), 88 | 44 | 82 | 81 | 41 | 48 (side by side) overrides.
-    bool clean = pl.M % 8 == 0;
-    for (size_t i = pl.nat_haz.size() / 2; i < pl.nat_haz.size(); i++) clean &= pl.nat_haz[i] == 0u;
-    int parts = clean ? (kp.n_frames <= 8 * pl.n_cus ? 81 : kp.n_frames <= 16 * pl.n_cus ? 82 : kp.n_frames >= 3072 ? 44 : 88)      // (one wave per CU while that holds the batch: 2048 normal frames 20.9 -> 19.4 ms)
-                     : kp.n_frames >= 32768 ? 1 : kp.n_frames > 6144 ? 4 : 8;
-    if (const char *ev = getenv("DVBS2HIP_NAT_PARTS")) { const int v = atoi(ev); if (v == 1 || v == 4 || v == 8 || ((v == 88 || v == 44 || v == 82 || v == 81 || v == 48 || v == 41) && clean)) parts = v; }
-    // (two digits: checks side by side, waves per workgroup -- 88 and 44 are the forms above, whose rows hold 32 frames; 82 = <8, 2> and 41 = <4, 1>: rows of 16 frames, twice the workgroups; 81 = <8, 1>: rows of 8; 48 = <4, 4>: rows of 64)
-#define NAT_CK_CASE(code, CKv, WVv) \
-    if (parts == code) { \
-        if (pl.fast_deg == 27) return nat_ck_launch<27, CKv, WVv>(pl, p, s); \
-        if (pl.fast_deg == 13) return nat_ck_launch<13, CKv, WVv>(pl, p, s); \
-        return nat_ck_launch<11, CKv, WVv>(pl, p, s); \
-    }
-    NAT_CK_CASE(88, 8, 4) NAT_CK_CASE(44, 4, 2) NAT_CK_CASE(82, 8, 2) NAT_CK_CASE(81, 8, 1) NAT_CK_CASE(48, 4, 4) NAT_CK_CASE(41, 4, 1)
-#undef NAT_CK_CASE
-    if (parts > 1) {
-        if (pl.fast_deg == 27) return parts == 4 ? nat_part_launch<27, 4>(pl, p, s) : nat_part_launch<27, 8>(pl, p, s);
-        if (pl.fast_deg == 13) return parts == 4 ? nat_part_launch<13, 4>(pl, p, s) : nat_part_launch<13, 8>(pl, p, s);
-        return parts == 4 ? nat_part_launch<11, 4>(pl, p, s) : nat_part_launch<11, 8>(pl, p, s);
-    }
-    p.grp_words = (uint32_t)ldpc_nat_group_words(pl);
-    const int groups = (kp.n_frames + 63) / 64, tiles = (pl.N + 63) / 64;
-    hipLaunchKernelGGL(nat_load_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
-    if (pl.fast_deg == 27) hipLaunchKernelGGL(ldpc_nat_kernel<27>, dim3(groups), dim3(64), 0, s, p);
-    else if (pl.fast_deg == 13) hipLaunchKernelGGL(ldpc_nat_kernel<13>, dim3(groups), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(ldpc_nat_kernel<11>, dim3(groups), dim3(64), 0, s, p);
-    hipLaunchKernelGGL(nat_store_kernel, dim3(tiles, groups), dim3(256), 0, s, p);
-    return hipGetLastError();
+    p.spa_cap = pl.spa_rule == 3 ? LDPC_SPA_CAP : INFINITY;
+    return i->launch(pl, p, s);
 }
 
 size_t ldpc_nat_group_words(const LdpcPlan &pl) { return (size_t)(pl.N + 2 + (pl.spa ? pl.fast_deg : 3) * pl.M) * 64; }      // (sum-product: one fp32 message per edge slot)

@@ -1,7 +1,7 @@
 // Development aid (CPU, no GPU needed): builds the LDPC plan of a MODCOD exactly as dvbs2hip_create does and prints what the
 // static hybrid search chose -- LDS rows, slots per layer, whether the parity chain sits at the last two slots.
 //   hipcc -std=c++17 -I dvbs2_amd/csrc -I include tools/plan_probe.cpp -L dvbs2_amd/lib -ldvbs2hip -Wl,-rpath,$PWD/dvbs2_amd/lib -o tools/bin/plan_probe
-#include "dvbs2hip_internal.h"
+#include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"
 #include "../include/dvbs2hip.h"
 #include <cstdio>
@@ -56,9 +56,68 @@ static int digest_main(int argc, char **argv)
     return 0;
 }
 
+// `plan_probe choice MODCOD SPA_RULE SMALL_BATCH LDS_LIMIT N_CUS SCHEDULE:F .. [--bad-address] [--junk-row] [--deg D] [--mode M] [--rule R]`: a line per SCHEDULE:F with the kernel ldpc_choose
+// (ldpc_dispatch.h) picks for a call of F frames on that plan (SCHEDULE: qc | natural; early stop on, the fused chain's tables present, a 160 KiB LDS; the DVBS2HIP_* variables as the environment has them) --
+// the instantiation as the code object names it, what it writes, its shape, the name the API reports, the error text.  The options doctor the plan first: the junk row one row
+// further, another slot count, image mode or sum-product rule.  `plan_probe insts`: every instantiation the families' tables hold.  tests/test_ldpc_dispatch.py reads both.
+static std::string symbol(LdpcFamily f, const int *t)
+{
+    std::string s = std::string(ldpc_family(f).kernel) + "<" + std::to_string(t[0]);
+    for (int i = 1; i < ldpc_family(f).n_targ; i++) s += ", " + (f == LF_GENERIC ? std::string(t[i] ? "true" : "false") : std::to_string(t[i]));
+    return s + ">";
+}
+static int choice_main(int argc, char **argv)
+{
+    std::vector<const char *> a;
+    int junk_rows = 0, deg = -1, mode = -1, rule = -1;
+    bool bad = false;
+    for (int i = 2; i < argc; i++) {
+        if (!strcmp(argv[i], "--junk-row")) junk_rows = 1;
+        else if (!strcmp(argv[i], "--bad-address")) bad = true;
+        else if (!strcmp(argv[i], "--deg") && i + 1 < argc) deg = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--mode") && i + 1 < argc) mode = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--rule") && i + 1 < argc) rule = atoi(argv[++i]);
+        else a.push_back(argv[i]);
+    }
+    if (a.size() < 6) { std::fprintf(stderr, "usage: plan_probe choice MODCOD SPA_RULE SMALL_BATCH LDS_LIMIT N_CUS qc|natural:F .. [--junk-row] [--deg D] [--mode M] [--rule R]\n"); return 2; }
+    dvbs2hip_cfg cfg;
+    if (dvbs2hip_cfg_from_modcod(a[0], &cfg)) { std::printf("unknown modcod\n"); return 1; }
+    std::vector<int32_t> addr(cfg.ldpc_addr, cfg.ldpc_addr + cfg.ldpc_row_ptr[cfg.ldpc_n_rows]);
+    if (bad) addr[0] = cfg.N_ldpc - cfg.K_ldpc;
+    LdpcPlan pl;
+    const std::string e = ldpc_build_plan(pl, cfg.N_ldpc, cfg.K_ldpc, cfg.ldpc_n_rows, cfg.ldpc_row_ptr, addr.data(), cfg.ldpc_lds_groups, (size_t)atol(a[3]), atoi(a[1]), atoi(a[2]) != 0);
+    if (!e.empty()) { std::printf("plan: '%s'\n", e.c_str()); return 0; }      // (no plan, no choice: dvbs2hip_create fails with this text)
+    pl.w8_lds_junk += (uint32_t)(junk_rows * LDPC_LAT_ROW);
+    if (deg >= 0) pl.fast_deg = deg;
+    if (mode >= 0) pl.fast_mode = mode;
+    if (rule >= 0) { pl.spa_rule = rule; pl.spa = rule != 0; }
+    for (size_t k = 5; k < a.size(); k++) {
+        const char *colon = strchr(a[k], ':');
+        if (!colon) { std::fprintf(stderr, "'%s' is not SCHEDULE:F\n", a[k]); return 2; }
+        const LdpcChoice ch = ldpc_choose(pl, {a[k][0] == 'n' ? DVBS2HIP_SCHED_NATURAL : DVBS2HIP_SCHED_QC, atoi(colon + 1), atoi(a[4]), true, true, true});
+        std::printf("choice %s: %s | info %d bch %d order %d | block %d lds %zu per_cu %d | name '%s' | error '%s'\n", a[k], symbol(ch.family, ch.targ).c_str(), ch.writes_info, ch.writes_bch,
+                    ch.takes_order, ch.block, ch.lds_bytes, ch.blocks_per_cu, ldpc_choice_name(ch).c_str(), ch.error.c_str());
+    }
+    return 0;
+}
+static int insts_main()
+{
+    for (int f = 0; f < LF_COUNT; f++)
+        for (int x = 0; x < 32; x++) for (int y = 0; y < 32; y++) for (int z = 0; z < 32; z++) {
+            const int t[3] = {x, y, z};
+            const LdpcFamily fam = (LdpcFamily)f;
+            const int n = ldpc_family(fam).n_targ;
+            if ((n < 3 && z) || (n < 2 && y)) continue;
+            if (ldpc_has(fam, t)) std::printf("%s\n", symbol(fam, t).c_str());
+        }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1 && !strcmp(argv[1], "digest")) return digest_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "choice")) return choice_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "insts")) return insts_main();
     dvbs2hip_cfg cfg;
     if (dvbs2hip_cfg_from_modcod(argc > 1 ? argv[1] : "QPSK-N_8/9", &cfg)) { std::printf("unknown modcod\n"); return 1; }
     LdpcPlan pl;
