@@ -425,19 +425,25 @@ int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, con
     if (!DEL || !X_N1 || !MU || !FRQ || !PHS || !Y_N1 || !B_N1) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     auto &T = h->stm;
     auto &C = h->sfc;
+    const bool started_over = C.hist_stale || (int)C.hs.size() != T.S;            // (sfc_dev clears the loop's own memories then)
     if ((r = stm_begin(h, F, "synchronize")) || (r = sfc_dev(h))) return r;
     float pg, ig;
     sfc_gains(C.pll_sps, C.damping, C.nbw, pg, ig);
-    // one stream: the matched filter's memory is the block-wise filter's own (the last 80 input samples, oldest first), so dvbs2hip_filter* carry on from the loop and back
-    const bool shared = T.S == 1;
-    const float *hin = shared ? h->d_hist[h->hist_cur] : C.hist[C.hist_cur];
-    float *hout = shared ? h->d_hist[h->hist_cur ^ 1] : C.hist[C.hist_cur ^ 1];
+    // the matched filter's memory is the block-wise filter's own (the last 80 input samples per stream, oldest first) when the two stream counts agree, so dvbs2hip_filter*
+    // carry on from the loop and back: one stream on d_hist, S streams (dvbs2hip_set_streams) on bw.hist.  Otherwise the loop keeps a memory per stream of its own.
+    const bool shared = T.S == 1 && h->bw.S == 1, shared_s = T.S > 1 && h->bw.S == T.S;
+    if (shared_s) {
+        if ((r = bw_hist_ready(h))) return r;
+        if (started_over) HIPCHK(h, hipMemsetAsync(h->bw.hist[h->bw.hist_cur], 0, SMF_HIST_BYTES * (size_t)T.S, h->stream));
+    }
+    const float *hin = shared ? h->d_hist[h->hist_cur] : shared_s ? h->bw.hist[h->bw.hist_cur] : C.hist[C.hist_cur];
+    float *hout = shared ? h->d_hist[h->hist_cur ^ 1] : shared_s ? h->bw.hist[h->bw.hist_cur ^ 1] : C.hist[C.hist_cur ^ 1];
     Timer tm(h, DVBS2HIP_K_MISC);
     HIPCHK(h, stepmf_launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt[T.c_cur], T.st[T.st_cur], T.st[T.st_cur ^ 1], C.cf[C.cf_cur], C.cf[C.cf_cur ^ 1], hin, hout, h->d_taps_rev,
                             C.pil, C.n_p, T.S, F / T.S, stm_frame_cplx(h), h->pl_frame, T.kp, T.ki, pg, ig, (float)h->fir_osf, h->stream));
     T.st_cur ^= 1;
     C.cf_cur ^= 1;
-    if (shared) h->hist_cur ^= 1; else C.hist_cur ^= 1;
+    if (shared) h->hist_cur ^= 1; else if (shared_s) h->bw.hist_cur ^= 1; else C.hist_cur ^= 1;
     C.where = C.DEV;
     return 0;
 }
@@ -458,6 +464,7 @@ int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h)                         // Synchr
     if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
     int r = dvbs2hip_sync_coarse_reset(h); if (r) return r;
     if (h->stm.S == 1) { if (h->fir_T > 1 && h->d_hist[h->hist_cur]) HIPCHK(h, hipMemsetAsync(h->d_hist[h->hist_cur], 0, sizeof(float) * 2 * (size_t)(h->fir_T - 1), h->stream)); }
+    else if (h->bw.S == h->stm.S && h->bw.hist[h->bw.hist_cur] && h->bw.hist_n >= h->bw.S) HIPCHK(h, hipMemsetAsync(h->bw.hist[h->bw.hist_cur], 0, SMF_HIST_BYTES * (size_t)h->bw.S, h->stream));
     else if (h->sfc.hist[h->sfc.hist_cur]) HIPCHK(h, hipMemsetAsync(h->sfc.hist[h->sfc.hist_cur], 0, SMF_HIST_BYTES * (size_t)h->sfc.n_alloc, h->stream));
     h->stm.act = false;
     return stm_alloc(h, h->stm.S);

@@ -46,45 +46,78 @@ static const uint16_t *sfm_frag(dvbs2hip_t *h)
     return e && !strcmp(e, "valu") ? nullptr : h->sfm.frag;
 }
 
+// every stream the state holds (S.n_alloc of them, side by side: dvbs2hip_set_streams)
 static int sfm_state_reset(dvbs2hip_t *h, bool all)
 {
     const int n = h->pl_frame;
     auto &S = h->sfm;
-    const float one[2] = {1.f, 0.f};                                               // reg_channel = (1, 0), .cpp:19 / :309
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(h, hipMemsetAsync(S.xh[i], 0, sizeof(float) * 2 * 64, h->stream));
-        HIPCHK(h, hipMemsetAsync(S.buff2[i], 0, sizeof(float) * (size_t)S.nbuff2, h->stream));
-        const int st[2] = {0, 1};                                                  // head2 = 0, first_time = true
-        HIPCHK(h, hipMemcpyAsync(S.st[i], st, sizeof st, hipMemcpyHostToDevice, h->stream));
-        if (all) HIPCHK(h, hipMemsetAsync(S.sofh[i], 0, sizeof(float) * 2 * 64, h->stream));
+    const size_t ns = (size_t)S.n_alloc;
+    std::vector<float> xh0(ns * 2 * 64, 0.f);
+    std::vector<int> st0(ns * SYNC_ST_STRIDE, 0);
+    for (size_t s = 0; s < ns; s++) {
+        xh0[s * 128 + 2 * 63] = 1.f;                                               // reg_channel = (1, 0), .cpp:19 / :309
+        st0[s * SYNC_ST_STRIDE + 1] = 1;                                           // head2 = 0, first_time = true
     }
-    HIPCHK(h, hipMemcpyAsync(S.xh[S.xh_cur] + 2 * 63, one, sizeof one, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(S.cv, 0, sizeof(float) * (size_t)n, h->stream));
-    if (all) { HIPCHK(h, hipMemsetAsync(S.yprev[S.yp_cur], 0, sizeof(float) * 2 * (size_t)n, h->stream)); HIPCHK(h, hipMemsetAsync(S.metric, 0, sizeof(float), h->stream)); }
-    HIPCHK(h, hipStreamSynchronize(h->stream));                                    // `one` / `st` live on this stack
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(h, hipMemsetAsync(S.xh[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
+        HIPCHK(h, hipMemsetAsync(S.buff2[i], 0, sizeof(float) * (size_t)S.nbuff2 * ns, h->stream));
+        HIPCHK(h, hipMemcpyAsync(S.st[i], st0.data(), sizeof(int) * st0.size(), hipMemcpyHostToDevice, h->stream));
+        if (all) HIPCHK(h, hipMemsetAsync(S.sofh[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(S.xh[S.xh_cur], xh0.data(), sizeof(float) * xh0.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(S.cv, 0, sizeof(float) * (size_t)n * ns, h->stream));
+    if (all) { HIPCHK(h, hipMemsetAsync(S.yprev[S.yp_cur], 0, sizeof(float) * 2 * (size_t)n * ns, h->stream)); HIPCHK(h, hipMemsetAsync(S.metric, 0, sizeof(float) * ns, h->stream)); }
+    HIPCHK(h, hipStreamSynchronize(h->stream));                                    // `xh0` / `st0` live on this stack
     return 0;
+}
+
+// the per-stream state for ns streams, side by side: a complete set or nothing (a failure leaves the handle with what it had)
+static int sfm_alloc_streams(dvbs2hip_t *h, int ns)
+{
+    auto &S = h->sfm;
+    const int n = h->pl_frame;
+    const size_t z = (size_t)ns;
+    float *xh[2] = {}, *sofh[2] = {}, *buff2[2] = {}, *yprev[2] = {}, *cv = nullptr, *metric = nullptr;
+    int *st[2] = {};
+    const char *what = "hipMalloc of the frame synchronizer's per-stream state failed";
+    int r = 0;
+    for (int i = 0; i < 2 && !r; i++)
+        if ((r = dev_alloc(h, &xh[i], sizeof(float) * 2 * 64 * z, what)) || (r = dev_alloc(h, &sofh[i], sizeof(float) * 2 * 64 * z, what)) ||
+            (r = dev_alloc(h, &buff2[i], sizeof(float) * (size_t)S.nbuff2 * z, what)) || (r = dev_alloc(h, &st[i], sizeof(int) * SYNC_ST_STRIDE * z, what)) ||
+            (r = dev_alloc(h, &yprev[i], sizeof(float) * 2 * (size_t)n * z, what))) break;
+    if (!r && !(r = dev_alloc(h, &cv, sizeof(float) * (size_t)n * z, what))) r = dev_alloc(h, &metric, sizeof(float) * z, what);
+    if (r) {
+        for (int i = 0; i < 2; i++) { (void)dev_free(h, &xh[i]); (void)dev_free(h, &sofh[i]); (void)dev_free(h, &buff2[i]); (void)dev_free(h, &st[i]); (void)dev_free(h, &yprev[i]); }
+        (void)dev_free(h, &cv); (void)dev_free(h, &metric);
+        return r;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 2; i++) {
+        (void)dev_free(h, &S.xh[i]); (void)dev_free(h, &S.sofh[i]); (void)dev_free(h, &S.buff2[i]); (void)dev_free(h, &S.st[i]); (void)dev_free(h, &S.yprev[i]);
+        S.xh[i] = xh[i]; S.sofh[i] = sofh[i]; S.buff2[i] = buff2[i]; S.st[i] = st[i]; S.yprev[i] = yprev[i];
+    }
+    (void)dev_free(h, &S.cv); (void)dev_free(h, &S.metric);
+    S.cv = cv; S.metric = metric;
+    S.n_alloc = ns;
+    S.xh_cur = S.sofh_cur = S.od_cur = S.yp_cur = 0;
+    return sfm_state_reset(h, true);
 }
 
 static int sfm_ready(dvbs2hip_t *h)
 {
     auto &S = h->sfm;
-    if (S.ready) return 0;
+    if (S.ready && S.n_alloc >= h->bw.S) return 0;
+    if (h->capturing && S.ready) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first call after dvbs2hip_set_streams allocates the streams' state");
     const int n = h->pl_frame;
     S.nbuff2 = 4 * (n + 1);                                                        // Variable_delay_cc_naive(N, N/2, N/2): buff2(4 (max_delay + 1))
-    for (int i = 0; i < 2; i++) {
-        DEV_ALLOC_CHK(h, &S.xh[i], sizeof(float) * 2 * 64);
-        DEV_ALLOC_CHK(h, &S.sofh[i], sizeof(float) * 2 * 64);
-        DEV_ALLOC_CHK(h, &S.buff2[i], sizeof(float) * (size_t)S.nbuff2);
-        DEV_ALLOC_CHK(h, &S.st[i], sizeof(int) * 4);
+    if (!S.keys)
+        DEV_ALLOC_CHK(h, &S.keys, sizeof(unsigned long long) * (size_t)h->max_frames * (size_t)((n + 63) / 64) + sizeof(float) * 2 * (size_t)((h->max_frames + SYNC_SUB - 1) / SYNC_SUB) * (size_t)n);      // (+ the segments' {A, B} of the average over frames: k_sync.hip)
+    if (!S.frag) {
+        const std::vector<uint16_t> fr = sync_frag_default();
+        DEV_ALLOC_CHK(h, &S.frag, fr.size() * sizeof(uint16_t));
+        HIPCHK(h, hipMemcpy(S.frag, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
-    DEV_ALLOC_CHK(h, &S.cv, sizeof(float) * (size_t)n);
-    for (int i = 0; i < 2; i++) DEV_ALLOC_CHK(h, &S.yprev[i], sizeof(float) * 2 * (size_t)n);
-    DEV_ALLOC_CHK(h, &S.keys, sizeof(unsigned long long) * (size_t)h->max_frames * (size_t)((n + 63) / 64) + sizeof(float) * 2 * (size_t)((h->max_frames + SYNC_SUB - 1) / SYNC_SUB) * (size_t)n);      // (+ the segments' {A, B} of the average over frames: k_sync.hip)
-    DEV_ALLOC_CHK(h, &S.metric, sizeof(float));
-    const std::vector<uint16_t> fr = sync_frag_default();
-    DEV_ALLOC_CHK(h, &S.frag, fr.size() * sizeof(uint16_t));
-    HIPCHK(h, hipMemcpy(S.frag, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    int r = sfm_state_reset(h, true);
+    int r = sfm_alloc_streams(h, h->bw.S);                                        // (it leaves every stream in the reset state)
     if (r) return r;
     S.ready = true;
     return 0;
@@ -107,12 +140,15 @@ int dvbs2hip_sync_frame_reset(dvbs2hip_t *h)
 
 int dvbs2hip_sync_frame_synchronize1_dev(dvbs2hip_t *h, const float *X_N1, float *cor_SOF, float *cor_PLSC, int32_t F)
 {
-    int r = check_frames(h, F); if (r) return r;
+    int r = bw_check(h, F); if (r) return r;
     if (!X_N1 || !cor_SOF || !cor_PLSC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     if ((r = sfm_ready(h))) return r;
     auto &S = h->sfm;
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, sync_corr_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * F, h->stream));
+    if (h->bw.S > 1)      // every stream from its own 64-sample memory
+        HIPCHK(h, sync_corr_streams_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * (F / h->bw.S), h->bw.S, h->stream));
+    else
+        HIPCHK(h, sync_corr_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * F, h->stream));
     S.xh_cur ^= 1;
     return 0;
 }
@@ -120,7 +156,9 @@ int dvbs2hip_sync_frame_synchronize1_dev(dvbs2hip_t *h, const float *X_N1, float
 // synchronize2, or (cor_SOF == cor_PLSC == null) the whole one-task synchronize with the correlators fused into the metric
 static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, const float *cor_PLSC, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F, const float **SRC = nullptr)
 {
-    int r = check_frames(h, F); if (r) return r;
+    int r = bw_check(h, F); if (r) return r;
+    const int NS = h->bw.S, Fs = F / NS;                                           // streams of the call, frames per stream
+    if (SRC && NS > 1) return fail(h, DVBS2HIP_EUNSUPPORTED, "the located form of the frame synchronizer is one stream per handle: with dvbs2hip_set_streams(S > 1) use dvbs2hip_sync_frame_synchronize_dev");
     int32_t *delay = DEL;
     const bool fused = !cor_SOF && !cor_PLSC;
     if (!X_N1 || (!fused && (!cor_SOF || !cor_PLSC)) || !delay || (!Y_N2 && !SRC)) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
@@ -134,6 +172,20 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
     Timer tm(h, DVBS2HIP_K_MISC);
     if (TRI) met = TRI;
     const SyncTail tail{S.keys, delay, (float *)met, FLG, S.trigger, (int32_t *)dtab, S.metric, reinterpret_cast<float *>(S.keys + (size_t)h->max_frames * (size_t)((n + 63) / 64))};
+    if (NS > 1) {      // every stream on its own state; frame 0 of a stream continues from that stream's previous call
+        if (fused) {
+            HIPCHK(h, sync_corr_metric_streams_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], S.cv, (float *)corr, tail,
+                                                      n, Fs, NS, S.alpha, S.vec_width, h->stream));
+            S.xh_cur ^= 1;
+        } else
+            HIPCHK(h, sync_metric_streams_launch(cor_SOF, S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], cor_PLSC, S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
+        S.sofh_cur ^= 1;
+        HIPCHK(h, sync_vdelay_streams_launch(X_N1, S.yprev[S.yp_cur], S.yprev[S.yp_cur ^ 1], Y_N2, S.buff2[S.od_cur], S.buff2[S.od_cur ^ 1], S.st[S.od_cur], S.st[S.od_cur ^ 1],
+                                             (const int32_t *)dtab, n, S.nbuff2, Fs, NS, h->stream));
+        S.od_cur ^= 1;
+        S.yp_cur ^= 1;
+        return 0;
+    }
     if (fused) {
         HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], S.cv, (float *)corr, tail,
                                           n, F, S.alpha, S.vec_width, h->stream));
@@ -181,6 +233,7 @@ int dvbs2hip_sync_frame_synchronize_dev(dvbs2hip_t *h, const float *X_N1, int32_
 int dvbs2hip_sync_frame_locate_dev(dvbs2hip_t *h, const float *X_N1, int32_t *DEL, int32_t *FLG, float *TRI, const float **SRC, int32_t F)
 {
     if (h && !SRC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if (h && h->bw.S > 1) return fail(h, DVBS2HIP_EUNSUPPORTED, "the located form of the frame synchronizer is one stream per handle: with dvbs2hip_set_streams(S > 1) use dvbs2hip_sync_frame_synchronize_dev");
     return sfm_sync2(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, nullptr, F, SRC);
 }
 
@@ -219,11 +272,19 @@ int dvbs2hip_sync_frame_synchronize(dvbs2hip_t *h, const float *X_N1, int32_t *D
 // ------------------------------------------------------------------ N4: fine frequency / phase synchronizers (sockets X_N1, FRQ, PHS, Y_N2)
 static int sff_call(dvbs2hip_t *h, bool lr, bool host, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t F)
 {
-    int r = check_frames(h, F); if (r) return r;
+    int r = lr ? bw_check(h, F) : check_frames(h, F); if (r) return r;
     if (!X_N1 || !Y_N2) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     const int n = h->pl_frame;
     if (n <= 1530) return fail(h, DVBS2HIP_EUNSUPPORTED, "the PL frame holds no pilot block");
-    if (lr && !h->d_lr_R) { DEV_ALLOC_CHK(h, &h->d_lr_R, 2 * sizeof(float)); HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float), h->stream)); }
+    const int NS = lr ? h->bw.S : 1;
+    if (lr && h->lr_n < NS) {      // the damped autocorrelation of every stream, zero (a larger stream count comes through dvbs2hip_set_streams, which has cleared the old ones)
+        if (h->capturing && h->d_lr_R) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first L&R call after dvbs2hip_set_streams allocates the streams' state");
+        float *R = nullptr;
+        if ((r = dev_alloc(h, &R, 2 * sizeof(float) * (size_t)NS, "hipMalloc of L&R's per-stream state failed"))) return r;
+        if (h->d_lr_R) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)dev_free(h, &h->d_lr_R); }
+        h->d_lr_R = R; h->lr_n = NS;
+        HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float) * (size_t)NS, h->stream));
+    }
     if (lr && !h->lr_err_host) {
         HIPCHK(h, hipHostMalloc((void **)&h->lr_err_host, dvbs2hip_handle::LR_SLOTS * sizeof(uint32_t), hipHostMallocMapped));
         for (int i = 0; i < dvbs2hip_handle::LR_SLOTS; i++) h->lr_err_host[i] = 0u;
@@ -242,9 +303,10 @@ static int sff_call(dvbs2hip_t *h, bool lr, bool host, const float *X_N1, float 
     if ((r = ensure(h, lr ? B_LR_TMP0 + slot : B_SFF_TMP, sizeof(float) * 4 * (size_t)F, &tmp))) return r;
     auto launch = [&](const float *x, float *frq, float *phs, float *y) {
         Timer tm(h, DVBS2HIP_K_MISC);
-        if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, h->lr_alpha, h->lr_err_dev + slot, h->stream));
+        if (lr && NS > 1) HIPCHK(h, sff_lr_streams_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, NS, h->lr_alpha, h->stream));      // three kernels: no waiting workgroup, nothing to look at later
+        else if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, h->lr_alpha, h->lr_err_dev + slot, h->stream));
         else HIPCHK(h, sff_fp_launch(x, y, (float *)tmp, frq, phs, n, F, h->stream));
-        if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host; }
+        if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host && NS == 1; }
         return 0;
     };
     if (!host) return launch(X_N1, FRQ, PHS, Y_N2);
@@ -283,7 +345,21 @@ int dvbs2hip_sync_lr_timeouts(dvbs2hip_t *h, int32_t *n)
 int dvbs2hip_sync_lr_reset(dvbs2hip_t *h)          // Synchronizer_Luise_Reggiannini_DVBS2_aib::_reset, .cpp:170-176
 {
     int r = enter(h); if (r) return r;
-    if (h->d_lr_R) HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float), h->stream));
+    if (h->d_lr_R) HIPCHK(h, hipMemsetAsync(h->d_lr_R, 0, 2 * sizeof(float) * (size_t)h->lr_n, h->stream));      // every stream's
+    return 0;
+}
+
+// S streams per call in every receive task that keeps a memory: the timing tasks' count (stm.S) and the block-wise tasks' (bw.S); every stream of all of them starts over
+int dvbs2hip_set_streams(dvbs2hip_t *h, int32_t S)
+{
+    int r = enter(h); if (r) return r;
+    if (S < 1 || S > h->max_frames || S > 65535) return fail(h, DVBS2HIP_EINVAL, "'S' has to be in [1, min(max_frames, 65535)] ('S' = " + std::to_string(S) + ").");
+    if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
+    if ((r = lr_check_all(h))) return r;                                           // (one-launch L&R calls not looked at yet belong to the old count)
+    if ((r = dvbs2hip_sync_timing_set_streams(h, S))) return r;
+    h->bw.S = S;                                                                   // (the per-stream state of the new count is allocated by the first call that needs it)
+    if ((r = dvbs2hip_filter_reset(h)) || (r = dvbs2hip_sync_lr_reset(h))) return r;
+    if (h->sfm.ready && (r = sfm_state_reset(h, true))) return r;                  // as a new handle: the SOF delay, the previous output frame and the last metric too
     return 0;
 }
 
@@ -292,10 +368,10 @@ int dvbs2hip_sync_frame_get_metric(dvbs2hip_t *h, float *max_corr, int32_t *pack
     if (!h || !max_corr || !packet_flag) return DVBS2HIP_EINVAL;
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, DVBS2HIP_EHIP, "hipSetDevice failed");
     int r = sfm_ready(h); if (r) return r;
-    float m = 0.f;
-    HIPCHK(h, hipMemcpyAsync(&m, h->sfm.metric, sizeof m, hipMemcpyDeviceToHost, h->stream));
+    std::vector<float> m((size_t)h->bw.S, 0.f);                                    // one entry per stream (dvbs2hip_set_streams)
+    HIPCHK(h, hipMemcpyAsync(m.data(), h->sfm.metric, sizeof(float) * m.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    *max_corr = m; *packet_flag = m > h->sfm.trigger ? 1 : 0;                      // _get_metric / _get_packet_flag, .hpp:59-60
+    for (size_t s = 0; s < m.size(); s++) { max_corr[s] = m[s]; packet_flag[s] = m[s] > h->sfm.trigger ? 1 : 0; }      // _get_metric / _get_packet_flag, .hpp:59-60
     return 0;
 }
 

@@ -575,6 +575,7 @@ int dvbs2hip_rx_bb_dev(dvbs2hip_t *h, const float *pl, const float *sigma, int32
 int dvbs2hip_rx_bb_located_dev(dvbs2hip_t *h, const float *const *SRC, const float *sigma, int32_t *info, int8_t *cwd_l, int8_t *cwd_b, int32_t F)
 {
     if (h && !SRC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if (h && h->bw.S > 1) return fail(h, DVBS2HIP_EUNSUPPORTED, "the located form is one stream per handle: with dvbs2hip_set_streams(S > 1) use dvbs2hip_rx_bb_dev on the synchronizer's Y_N2");
     return rx_bb_any_dev(h, nullptr, SRC, sigma, info, cwd_l, cwd_b, F);
 }
 

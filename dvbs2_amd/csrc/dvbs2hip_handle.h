@@ -79,6 +79,7 @@ struct dvbs2hip_handle {
         float *metric = nullptr;               // max_corr of the last frame
         uint16_t *frag = nullptr;              // band fragments of the two correlators for the matrix cores (k_sync_mfma.hip)
         int xh_cur = 0, sofh_cur = 0, od_cur = 0, yp_cur = 0;
+        int n_alloc = 0;                       // streams the state above holds, side by side (dvbs2hip_set_streams; 1 without it)
     } sfm;
     // L&R fine frequency synchronizer (N4): damped autocorrelation R_l, alpha (factory default 0.999)
     // host sockets the integrator has pinned (dvbs2hip_host_register): base address -> bytes; copy streams + events of
@@ -91,7 +92,8 @@ struct dvbs2hip_handle {
     float sep_g[2] = {0.f, 0.f}, sep_h[2] = {0.f, 0.f};
     int fir_kernel = DVBS2HIP_FIR_AUTO;
     float *d_nat_work = nullptr;       // natural-order LDPC: frame-interleaved image + state, ceil(max_frames / 64) groups
-    float *d_lr_R = nullptr;
+    float *d_lr_R = nullptr;           // 2 floats per stream, lr_n streams
+    int lr_n = 0;
     float lr_alpha = 0.999f;
     int lr_timeouts = 0;               // launches whose rotation had to be repeated (dvbs2hip_sync_lr_timeouts)
     // L&R, recurrence and rotation in one launch (k_sync.hip, sff_lr_fused_kernel): the error word a rotating workgroup sets when it gives up waiting for the
@@ -155,6 +157,14 @@ struct dvbs2hip_handle {
         float fs_omega = 0.f;                                   // the frequency shift: Multiplier_sine_ccc_naive's omega and sample counter
         uint32_t fs_n = 0;
     } chn;
+    // dvbs2hip_set_streams: streams per call in the block-wise tasks that keep a memory (matched filter, frame synchronizer, L&R); the timing tasks' count is stm.S, and
+    // dvbs2hip_sync_timing_set_streams sets that one alone.  S > 1: the matched filter's memory per stream, (fir_T - 1) complex samples each, side by side in a ping-pong pair
+    // of its own (S = 1 stays on d_hist); the coarse-frequency loop runs on it too when stm.S == S (api_acquire.hip)
+    struct {
+        int S = 1;
+        float *hist[2] = {nullptr, nullptr};
+        int hist_n = 0, hist_cur = 0;                           // streams hist[] holds
+    } bw;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[DVBS2HIP_K_COUNT];
     std::string err;
@@ -245,6 +255,15 @@ inline int check_frames(dvbs2hip_t *h, int n_frames)
     if (n_frames < 1 || n_frames > h->max_frames)
         return fail(h, DVBS2HIP_EINVAL, "'n_frames' has to be in [1, max_frames] ('n_frames' = " + std::to_string(n_frames) +
                                             ", 'max_frames' = " + std::to_string(h->max_frames) + ").");
+    return 0;
+}
+
+// the block-wise tasks with a memory: stream s = frames [s F/S, (s+1) F/S) of a call (dvbs2hip_set_streams)
+inline int bw_check(dvbs2hip_t *h, int n_frames)
+{
+    int r = check_frames(h, n_frames); if (r) return r;
+    if (n_frames % h->bw.S)
+        return fail(h, DVBS2HIP_EINVAL, "'n_frames' has to be a multiple of the stream count ('n_frames' = " + std::to_string(n_frames) + ", streams = " + std::to_string(h->bw.S) + ").");
     return 0;
 }
 
@@ -377,6 +396,7 @@ int host_wrap(dvbs2hip_t *h, const Tin *in, size_t nin_el, Tout *out, size_t nou
 
 // ---- defined in one translation unit, used from another
 int lr_check_all(dvbs2hip_t *h);                                                   // api_sync.hip
+int bw_hist_ready(dvbs2hip_t *h);                                                  // api_filter.hip: bw.hist for bw.S streams (allocated and cleared on first use)
 // api_tables.hip: what dvbs2hip_create uploads (pl_sequence: the coarse loop's pilots too)
 struct TxEncTable { std::vector<uint32_t> tab; std::vector<int32_t> deg; int stride = 0; };
 struct LdpcSynTables { std::vector<uint32_t> pos, prbs_s; int words = 0, rows = 0; };

@@ -28,11 +28,14 @@ constexpr int FIR_TMAX = 257;
 
 __host__ __device__ __forceinline__ int fir_pad(int s) { return s + (s >> 3); }
 
-template <int TS>   // TS > 0: compile-time tap count (fully unrolled); TS == 0: run-time T
+// MS (dvbs2hip_set_streams, S > 1 streams per call): workgroup (b, s) is workgroup b of a one-stream call on stream s alone -- n_total samples at x + s n_total, its own
+// memory at hist_in + s (T - 1).  Every stream starts at a tile boundary of its own, so its sums are the one-stream call's, operation for operation.
+template <int TS, bool MS = false>   // TS > 0: compile-time tap count (fully unrolled); TS == 0: run-time T
 __global__ void __launch_bounds__(FIR_THREADS)
 fir_ccr_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const float2 *__restrict__ hist_in,
                const float *__restrict__ taps_rev, int Trt, long long n_total)
 {
+    if (MS) { const size_t s = blockIdx.y; x += s * (size_t)n_total; y += s * (size_t)n_total; hist_in += s * (size_t)((TS > 0 ? TS : Trt) - 1); }
     extern __shared__ float2 tile[];             // fir_pad(FIR_TILE + T - 1) samples
     const int T = TS > 0 ? TS : Trt;
     const int H = T - 1;
@@ -86,6 +89,7 @@ fir_ccr_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const float
     }
 }
 
+
 // new history = last H samples of (old history ++ x)
 __global__ void fir_hist_kernel(const float2 *x, const float2 *hist_in, float2 *hist_out, int H, long long n_total)
 {
@@ -93,6 +97,14 @@ __global__ void fir_hist_kernel(const float2 *x, const float2 *hist_in, float2 *
     if (i >= H) return;
     const long long gi = n_total - H + i;
     hist_out[i] = gi >= 0 ? x[gi] : hist_in[H + gi];
+}
+__global__ void fir_hist_streams_kernel(const float2 *x, const float2 *hist_in, float2 *hist_out, int H, long long n_per)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H) return;
+    const size_t s = blockIdx.y;
+    const long long gi = n_per - H + i;
+    hist_out[s * H + i] = gi >= 0 ? x[s * (size_t)n_per + gi] : hist_in[s * H + H + gi];
 }
 
 // afrag != nullptr: the matrix-core form (k_fir_mfma.hip) when it applies (T <= 81, 16-byte aligned sockets);
@@ -120,6 +132,29 @@ hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *his
     return hipGetLastError();
 }
 
+// S streams of n_per samples each, memories of T - 1 samples per stream side by side; the kernel family is chosen once for the call, from the sockets and the per-stream
+// length (the matrix-core form loads 16 bytes at a time: every stream has to start on such a boundary)
+hipError_t fir_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag,
+                              int T, long long n_per, int S, hipStream_t s)
+{
+    if (T < 1 || T > FIR_TMAX || S < 1 || S > 65535 || n_per < 1) return hipErrorInvalidValue;
+    const int H = T - 1;
+    static const bool force_valu = [] { const char *e = getenv("DVBS2HIP_FIR"); return e && e[0] == 'v'; }();
+    if (afrag && !force_valu && fir_mfma_usable(x, y, T, n_per) && n_per % 2 == 0)
+        return fir_mfma_streams_launch(x, y, hist_in, hist_out, afrag, T, n_per, S, s);
+    const size_t lds = sizeof(float2) * (size_t)(fir_pad(FIR_TILE + H) + 1);
+    const unsigned grid = (unsigned)((n_per + FIR_TILE - 1) / FIR_TILE);
+    const float2 *x2 = reinterpret_cast<const float2 *>(x);
+    float2 *y2 = reinterpret_cast<float2 *>(y);
+    const float2 *h2 = reinterpret_cast<const float2 *>(hist_in);
+    if (T == 81) hipLaunchKernelGGL((fir_ccr_kernel<81, true>), dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
+    else         hipLaunchKernelGGL((fir_ccr_kernel<0, true>), dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (H > 0)
+        hipLaunchKernelGGL(fir_hist_streams_kernel, dim3((H + 63) / 64, S), dim3(64), 0, s, x2, h2, reinterpret_cast<float2 *>(hist_out), H, n_per);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------- N2: TX shaping filter (polyphase up-sampling FIR)
 // Replaces Filter_UPRRC_ccr_naive / Filter_UPFIR_ccr_naive::_filter

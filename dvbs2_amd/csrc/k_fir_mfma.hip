@@ -100,11 +100,16 @@ __device__ __forceinline__ float2 fm_fetch_edge(const float2 *__restrict__ x, co
 // NPH = 1: the matched filter.  NPH = 2: the TX shaping filter (Filter_UPFIR_ccr_naive, osf = 2) -- two polyphase branches
 // of at most 81 taps over the SAME staged samples, branch ph in the band fragments afrag[ph]; output 2 i + ph of input i,
 // so a lane stores (re, im) of both branches as one 16-byte piece and 16 lanes a 256-byte run.  n_total counts INPUT samples.
-template <int NPH>
-__global__ void __launch_bounds__(FM_THREADS) __attribute__((amdgpu_waves_per_eu(NPH == 1 ? 4 : 3, NPH == 1 ? 4 : 3)))
+// NPHS = NPH, or NPH + FM_STREAMS (dvbs2hip_set_streams, S > 1 streams per call; the matched filter only): row s of the grid is then a one-stream launch on stream s
+// alone -- n_total samples (an even number: the 16-byte loads) at x + s n_total, the memories of T - 1 samples side by side.
+constexpr int FM_STREAMS = 4;
+template <int NPHS>
+__global__ void __launch_bounds__(FM_THREADS) __attribute__((amdgpu_waves_per_eu((NPHS & 3) == 1 ? 4 : 3, (NPHS & 3) == 1 ? 4 : 3)))
 fir_mfma_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const float2 *__restrict__ hist_in, float2 *__restrict__ hist_out,
                 const uint4 *__restrict__ afrag, int T, long long n_total, int tiles_per_wg)
 {
+    constexpr int NPH = NPHS & 3;
+    if (NPHS & FM_STREAMS) { const size_t s = blockIdx.y; x += s * (size_t)n_total; y += s * (size_t)n_total; hist_in += s * (size_t)(T - 1); hist_out += s * (size_t)(T - 1); }
     __shared__ __attribute__((aligned(16))) uint16_t lds[3 * 2 * FM_PLANE];      // [part][re | im][sample]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int H = T - 1;
@@ -210,6 +215,7 @@ fir_mfma_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const floa
     }
 }
 
+
 static inline uint16_t bf16_rne(float v)
 {
     uint32_t u; std::memcpy(&u, &v, 4);
@@ -256,6 +262,18 @@ hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float
     const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
     hipLaunchKernelGGL(fir_mfma_kernel<1>, dim3(grid), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
                        reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T, n_total,
+                       tiles_per_wg);
+    return hipGetLastError();
+}
+
+// the tiles of a stream are dealt to its workgroups as in a one-stream call of n_per samples
+hipError_t fir_mfma_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s)
+{
+    const long long n_tiles = (n_per + FM_TILE - 1) / FM_TILE;
+    const int tiles_per_wg = n_tiles >= 4096 ? 4 : (int)((n_tiles + 1023) / 1024);
+    const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
+    hipLaunchKernelGGL(fir_mfma_kernel<1 + FM_STREAMS>, dim3(grid, S), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
+                       reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T, n_per,
                        tiles_per_wg);
     return hipGetLastError();
 }

@@ -32,10 +32,14 @@ __device__ __forceinline__ int sy_pad(int i) { return i + (i >> 2); }     // one
 // Each lane forms SY_R consecutive outputs from one pass over the 63 + SY_R differential samples they share (a value is read
 // from LDS once and used by up to SY_R x 2 taps; one output per lane read 89 values per output and was LDS-bound), every
 // output accumulating oldest sample first like Filter_FIR_ccr.cpp:68-142.
+// MS (dvbs2hip_set_streams, S > 1 streams per call): row s of the grid is the one-stream launch on stream s alone, n_total samples at x + s n_total, its 64-sample memory
+// at xh + 64 s -- the halo of a stream's first block comes from that stream's memory, never from the stream before it.  MS = false is the one-stream kernel as it was.
+template <bool MS>
 __global__ void __launch_bounds__(SY_THREADS)
 sync_corr_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, float2 *__restrict__ cor_sof, float2 *__restrict__ cor_plsc,
                  long long n_total)
 {
+    if (MS) { const size_t o = (size_t)blockIdx.y * (size_t)n_total; x += o; xh += (size_t)blockIdx.y * SY_H; cor_sof += o; cor_plsc += o; }
     __shared__ float2 xs[SY_T + SY_H];                               // xs[k] = x[blk0 - 64 + k]
     __shared__ float2 ds[SY_T + SY_H + (SY_T + SY_H) / 4 + 4];       // ds[pad(k)] = d[blk0 - 63 + k] = x[blk0 - 64 + k] conj(x[blk0 - 63 + k])
     const long long blk0 = (long long)blockIdx.x * SY_T;
@@ -85,10 +89,12 @@ sync_corr_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, fl
 // delayed cor_SOF from the handle's history (sofh), the last 64 cor_SOF values of the stream go to sofh_out.
 typedef float sy_f2 __attribute__((ext_vector_type(2)));
 constexpr int SY_HX = 96;                     // samples of x before the block: 64 (SOF halo) + 24 (its taps) + 1 (differential), rounded up
+template <bool MS>      // MS: as sync_corr_kernel, the cor_SOF memories at sofh + 64 s too
 __global__ void __launch_bounds__(SY_THREADS)
 sync_corr_m_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, const float2 *__restrict__ sofh, float2 *__restrict__ sofh_out,
                    float *__restrict__ corr, long long n_total)
 {
+    if (MS) { const size_t s = blockIdx.y, o = s * (size_t)n_total; x += o; xh += s * SY_H; sofh += s * 64; sofh_out += s * 64; corr += o; }
     __shared__ float2 xs[SY_T + SY_HX];                              // xs[k] = x[blk0 - 96 + k]
     __shared__ float2 ds[SY_T + SY_HX + (SY_T + SY_HX) / 4 + 4];     // ds[pad(k)] = d[blk0 - 95 + k]
     __shared__ float2 sof_s[SY_T + 64];                              // sof_s[k] = cor_SOF[blk0 - 64 + k]
@@ -171,6 +177,15 @@ __global__ void sync_hist_kernel(const float2 *x, const float2 *hist_in, float2 
     const long long gi = n_total - H + i;
     hist_out[i] = gi >= 0 ? x[gi] : hist_in[H + gi];
 }
+// ... of every stream (grid y), the memories side by side
+__global__ void sync_hist_streams_kernel(const float2 *x, const float2 *hist_in, float2 *hist_out, int H, long long n_per)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H) return;
+    const size_t s = blockIdx.y;
+    const long long gi = n_per - H + i;
+    hist_out[s * H + i] = gi >= 0 ? x[s * (size_t)n_per + gi] : hist_in[s * H + H + gi];
+}
 
 // ---- _synchronize2, first half (:236-267, :278-285).  The instantaneous metric m[f][i] = max(|plsc + sof|, |sof - plsc|) of
 // every sample is independent work (sync_m_kernel, one lane per sample of the batch); the average over frames
@@ -186,6 +201,19 @@ __global__ void sync_m_kernel(const float2 *__restrict__ cor_sof, const float2 *
     const float sr = p.x + s.x, si = p.y + s.y, dr = s.x - p.x, di = s.y - p.y;
     const float a2s = fmaf(sr, sr, si * si), a2d = fmaf(dr, dr, di * di);
     corr[g] = sqrtf(fmaxf(a2s, a2d));
+}
+// stream s (grid y): the delayed cor_SOF of its first 64 samples is that stream's memory
+__global__ void sync_m_streams_kernel(const float2 *__restrict__ cor_sof, const float2 *__restrict__ sofh, const float2 *__restrict__ cor_plsc,
+                                      float *__restrict__ corr, long long n_per)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_per) return;
+    const size_t s = blockIdx.y, o = s * (size_t)n_per;
+    const float2 sv = g >= 64 ? cor_sof[o + g - 64] : sofh[s * 64 + g];
+    const float2 p = cor_plsc[o + g];
+    const float sr = p.x + sv.x, si = p.y + sv.y, dr = sv.x - p.x, di = sv.y - p.y;
+    const float a2s = fmaf(sr, sr, si * si), a2d = fmaf(dr, dr, di * di);
+    corr[o + g] = sqrtf(fmaxf(a2s, a2d));
 }
 
 // four wave-wide maxima side by side (the row_shr / row_bcast ladder of gfx9, the four registers interleaved so that no step waits for the
@@ -538,10 +566,14 @@ sync_metric_argmax_kernel(float *__restrict__ cv, const float *__restrict__ corr
 // per frame (one wave each): the maximum of the workgroups' keys -> delay (:296), TRI = get_metric() (Synchronizer_frame.hxx:181),
 // FLG = get_packet_flag() (.hpp:60); the delay line's table D[f] = 2 ((n - delay[f]) % n) (set_delay((cplx_in_sz - delay) % cplx_in_sz), :298);
 // max_corr of the last frame into the handle's state
+// MS (S > 1 streams per call): workgroup (f, s) is frame f of stream s, F frames per stream; the per-frame sockets and the keys are stream-major (frame s F + f of the
+// call), last_metric per stream
+template <bool MS>
 __global__ void __launch_bounds__(64)
 sync_finalize_kernel(const unsigned long long *__restrict__ keys, int nwg, int32_t *__restrict__ delay, float *__restrict__ metric, int32_t *__restrict__ flag,
                      float trigger, int32_t *__restrict__ Dtab, float *__restrict__ last_metric, int n, int n_sof, int n_plsc, int F)
 {
+    if (MS) { const size_t s = blockIdx.y, o = s * (size_t)F; keys += o * (size_t)nwg; delay += o; metric += o; if (flag) flag += o; Dtab += o; last_metric += s; }
     const int f = blockIdx.x;
     unsigned long long k = 0ull;
     for (int g = threadIdx.x; g < nwg; g += 64) { const unsigned long long v = keys[(size_t)f * nwg + g]; k = v > k ? v : k; }
@@ -557,6 +589,43 @@ sync_finalize_kernel(const unsigned long long *__restrict__ keys, int nwg, int32
     if (flag) flag[f] = bv > trigger ? 1 : 0;
     if (f == F - 1) *last_metric = bv;
     Dtab[f] = 2 * ((n - d) % n);
+}
+
+// ---- the average over frames and the arg max of every frame when the call carries S > 1 streams: the streams supply the parallelism, so this is the plain walk.  One wave
+// per (stream, 64 positions) goes through its stream's Fs frames in order with the position's average in a register -- read from cv once, written back once; no other lane
+// of the launch touches that element -- and leaves, per frame, the key of its 64 positions for sync_finalize_kernel<true>.  The recurrence is the single walk's of the
+// kernels above: c = al c + om m with each product and the sum rounded once; positions past the last full vector are not averaged (al = 0, om = 1).  A frame's key is
+// (value bits << 32) | ~index, the wave's maximum of it the largest value and among equal values the first position; no value above 0 gives key 0.
+constexpr int SYS_UF = 8;       // frames whose loads are in flight together
+__global__ void __launch_bounds__(64)
+sync_average_argmax_streams_kernel(float *__restrict__ cv, const float *__restrict__ corr, unsigned long long *__restrict__ keys, int n, int Fs, float alpha, int end_vec)
+{
+    const int lane = threadIdx.x, i = blockIdx.x * 64 + lane;
+    const size_t s = blockIdx.y;
+    const bool act = i < n;
+    const int il = act ? i : n - 1;
+    cv += s * (size_t)n;
+    const float *p = corr + s * (size_t)Fs * (size_t)n + il;
+    unsigned long long *kq = keys + s * (size_t)Fs * gridDim.x + blockIdx.x;
+    float c = act ? cv[il] : 0.f;
+    const float al = il < end_vec ? alpha : 0.f, om = !act ? 0.f : il < end_vec ? 1.0f - alpha : 1.f;      // (lanes past the last position carry 0)
+    const unsigned long long inv = 0xffffffffu - (uint32_t)i;
+    for (int f0 = 0; f0 < Fs; f0 += SYS_UF) {
+        float m[SYS_UF];
+#pragma unroll
+        for (int u = 0; u < SYS_UF; u++) m[u] = __builtin_nontemporal_load(p + (size_t)(f0 + u < Fs ? f0 + u : Fs - 1) * (size_t)n);
+#pragma unroll
+        for (int u = 0; u < SYS_UF; u++) {
+            if (f0 + u >= Fs) break;                                   // (uniform)
+            c = al * c + om * m[u];
+            const uint32_t b = __float_as_uint(c);
+            unsigned long long k = b != 0u ? ((unsigned long long)b << 32) | inv : 0ull;
+#pragma unroll
+            for (int sft = 32; sft > 0; sft >>= 1) { const unsigned long long o = __shfl_xor(k, sft); k = o > k ? o : k; }
+            if (lane == 0) kq[(size_t)(f0 + u) * gridDim.x] = k;
+        }
+    }
+    if (act) cv[i] = c;
 }
 
 // ---- Variable_delay_cc_naive::_filter (Variable_delay_cc_naive.cpp:56-79), the whole batch in ONE launch.
@@ -578,6 +647,7 @@ __device__ __forceinline__ int vd_D(const int32_t *Dtab, int f, int) { return Dt
 // walks run once per complex sample and move 8 bytes).  The walks only compute WHERE a sample comes from (they read nothing but the
 // small table of delays); the loads themselves are issued afterwards, several per lane at once -- one dependent load per lane was
 // latency-bound at 1.6 TB/s.  A null source stands for the zero of first_time.
+template <bool MS>      // (MS: the S-stream launch has copies of its own of the two walks, so that the one-stream kernel's stay as they were compiled for their one caller)
 __device__ __noinline__ const float *vd_buff(const float *__restrict__ X, const float *__restrict__ buff0, const int32_t *__restrict__ delay_f,
                                                 int g, int k, int n)
 {
@@ -589,6 +659,7 @@ __device__ __noinline__ const float *vd_buff(const float *__restrict__ X, const 
     return &buff0[k];
 }
 
+template <bool MS>
 __device__ __noinline__ const float *vd_source(const float *__restrict__ X, const float *__restrict__ yprev0, const float *__restrict__ buff0,
                                            const int *__restrict__ st0, const int32_t *__restrict__ delay_f, int f, int j, int n, int nbuff2)
 {
@@ -600,7 +671,7 @@ __device__ __noinline__ const float *vd_source(const float *__restrict__ X, cons
         int end_buff = start_buff + D;
         end_buff = end_buff > nbuff2 ? nbuff2 : end_buff;
         end_buff = (end_buff - start_buff > N - start_Y) ? end_buff - ((end_buff - start_buff) - (N - start_Y)) : end_buff;
-        if (j >= start_Y && j < start_Y + (end_buff - start_buff)) return vd_buff(X, buff0, delay_f, f - 1, start_buff + j - start_Y, n);
+        if (j >= start_Y && j < start_Y + (end_buff - start_buff)) return vd_buff<MS>(X, buff0, delay_f, f - 1, start_buff + j - start_Y, n);
         if (j < start_Y) { if (first) return nullptr; j = N - start_Y + j; }
         if (--f < 0) return &yprev0[j];                     // the output buffer as the previous call left it
     }
@@ -622,6 +693,7 @@ __device__ __forceinline__ VdU vd_uniform(const int *__restrict__ st0, const int
     u.len = end_buff - u.start_buff;
     return u;
 }
+template <bool MS>
 __device__ __forceinline__ const float *vd_source_fast(const VdU &u, const float *__restrict__ X, const float *__restrict__ yprev0, const float *__restrict__ buff0,
                                                        const int *__restrict__ st0, const int32_t *__restrict__ Dtab, int f, int j, int n, int nbuff2)
 {
@@ -631,7 +703,7 @@ __device__ __forceinline__ const float *vd_source_fast(const VdU &u, const float
         const int k = u.start_buff + j - u.start_Y;
         if (k < u.head2) return &X[(size_t)(f - 1) * N + N - u.head2 + k];
     }
-    return vd_source(X, yprev0, buff0, st0, Dtab, f, j, n, nbuff2);
+    return vd_source<MS>(X, yprev0, buff0, st0, Dtab, f, j, n, nbuff2);
 }
 
 constexpr int VD_SPL = 2;        // PAIRS of complex samples per lane, their loads in flight together
@@ -639,10 +711,19 @@ typedef float vd_f4 __attribute__((ext_vector_type(4), aligned(4)));     // a pa
 // blockIdx.y < F: output frame blockIdx.y; blockIdx.y == F: the delay line and {head2, first_time} after the last frame.
 // A lane resolves two neighbouring complex samples; almost always they are neighbours at the source too (in lock a whole output frame is ONE
 // run of the input stream, X[f N - D ...)), and the pair then moves as 16 bytes.
+// MS (S > 1 streams per call, grid z; list is null): slice s is the one-stream launch on stream s alone -- its F frames, its delay line, {head2, first_time} and previous
+// output frame (the state arrays hold the streams side by side: nbuff2 floats, SYNC_ST_STRIDE ints, 2 n floats each), its rows of the delay table.  Frame 0 of a stream
+// continues from that stream's previous call.
+template <bool MS>
 __global__ void sync_vdelay_batch_kernel(const float *__restrict__ X, const float *__restrict__ yprev0, float *__restrict__ yprev_new, float *__restrict__ Y,
                                          const float *__restrict__ buff_old, float *__restrict__ buff_new, const int *__restrict__ st_old,
                                          int *__restrict__ st_new, const int32_t *__restrict__ delay_f, int n, int nbuff2, int F, const int32_t *__restrict__ list)
 {
+    if (MS) {
+        const size_t s = blockIdx.z, o = s * (size_t)F * 2 * (size_t)n;
+        X += o; Y += o; yprev0 += s * 2 * (size_t)n; yprev_new += s * 2 * (size_t)n; buff_old += s * (size_t)nbuff2; buff_new += s * (size_t)nbuff2;
+        st_old += s * SYNC_ST_STRIDE; st_new += s * SYNC_ST_STRIDE; delay_f += s * (size_t)F;
+    }
     const int N = 2 * n;
     __shared__ int red[256];
     // located form (sync_locate_kernel): `list` = {count, frames to materialize .. (F = the state row among them)}; row y of the grid takes entries y, y + gridDim.y, ..
@@ -668,11 +749,11 @@ __global__ void sync_vdelay_batch_kernel(const float *__restrict__ X, const floa
         const int j = 4 * ((bx * VD_SPL + i) * (int)blockDim.x + (int)threadIdx.x);      // first float of a pair of complex samples
         jj[i] = j; sa[i] = nullptr; sb[i] = nullptr;
         if (f < F) {
-            if (j < lim) sa[i] = vd_source_fast(u, X, yprev0, buff_old, st_old, delay_f, f, j, n, nbuff2);
-            if (j + 2 < lim) sb[i] = vd_source_fast(u, X, yprev0, buff_old, st_old, delay_f, f, j + 2, n, nbuff2);
+            if (j < lim) sa[i] = vd_source_fast<MS>(u, X, yprev0, buff_old, st_old, delay_f, f, j, n, nbuff2);
+            if (j + 2 < lim) sb[i] = vd_source_fast<MS>(u, X, yprev0, buff_old, st_old, delay_f, f, j + 2, n, nbuff2);
         } else {                                                      // buff2 after the last frame: its first D entries are that frame's tail
-            if (j < lim) sa[i] = j < u.D ? &X[(size_t)(F - 1) * N + N - u.D + j] : j < dmax ? vd_buff(X, buff_old, delay_f, F - 2, j, n) : &buff_old[j];
-            if (j + 2 < lim) sb[i] = j + 2 < u.D ? &X[(size_t)(F - 1) * N + N - u.D + j + 2] : j + 2 < dmax ? vd_buff(X, buff_old, delay_f, F - 2, j + 2, n) : &buff_old[j + 2];
+            if (j < lim) sa[i] = j < u.D ? &X[(size_t)(F - 1) * N + N - u.D + j] : j < dmax ? vd_buff<MS>(X, buff_old, delay_f, F - 2, j, n) : &buff_old[j];
+            if (j + 2 < lim) sb[i] = j + 2 < u.D ? &X[(size_t)(F - 1) * N + N - u.D + j + 2] : j + 2 < dmax ? vd_buff<MS>(X, buff_old, delay_f, F - 2, j + 2, n) : &buff_old[j + 2];
         }
     }
     vd_f4 v[VD_SPL];
@@ -768,10 +849,13 @@ __device__ __forceinline__ void sff_lr_chain(float2 *sh, float &r0, float &r1, f
 // Two waves: wave 0 stages 64 frames in LDS (the next 64 already on their way from memory) and its lane 0 runs the recurrence over them;
 // wave 1 forms the estimates of the batch before (atan2 and the double-precision scaling, one frame per lane) meanwhile -- one LDS-only
 // barrier per batch, two batch buffers.
+// MS (S > 1 streams per call): one workgroup per stream, over that stream's F frames (tR + s F, fr + s F) and its own damped autocorrelation R_l + 2 s
+template <bool MS>
 __global__ void __launch_bounds__(128)
 sff_lr_iir_kernel(const float2 *__restrict__ tR, float *__restrict__ R_l, float2 *__restrict__ fr, float *__restrict__ FRQ,
                   float *__restrict__ PHS, int F, float alpha)
 {
+    if (MS) { const size_t s = blockIdx.x, o = s * (size_t)F; tR += o; R_l += 2 * s; fr += o; if (FRQ) FRQ += o; if (PHS) PHS += o; }
     __shared__ float2 sh[2][64];
     const int lane = threadIdx.x & 63, nb = (F + 63) / 64;
     if (threadIdx.x < 64) {
@@ -1048,9 +1132,20 @@ static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, fl
 {
     float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
     hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, (float2 *)nullptr, n);
-    hipLaunchKernelGGL(sff_lr_iir_kernel, dim3(1), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F, alpha);
+    hipLaunchKernelGGL(sff_lr_iir_kernel<false>, dim3(1), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F, alpha);
     const long long tot = (long long)n * F;
     sff_rotate_launch<0>(X, Y, fr, n, tot, s);
+    return hipGetLastError();
+}
+
+// S > 1 streams per call: always the three kernels (the one-launch form's waiting workgroups rely on workgroup 0 being placed first: one assumption per launch, not
+// multiplied by the streams) -- the pilots per frame, the recurrence as one workgroup per stream, the rotation per frame
+hipError_t sff_lr_streams_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s)
+{
+    float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
+    hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, (float2 *)nullptr, n);
+    hipLaunchKernelGGL(sff_lr_iir_kernel<true>, dim3(S), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F / S, alpha);
+    sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, s);
     return hipGetLastError();
 }
 
@@ -1070,7 +1165,7 @@ hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, c
     // frag: the correlators on the matrix cores (k_sync_mfma.hip, which also leaves the next call's memory in xh_out); null = the fp32 vector kernel
     if (sync_mfma_usable(x, frag)) return sync_corr_mfma_launch(x, xh_in, xh_out, frag, cor_sof, cor_plsc, n_total, s);
     const unsigned grid = (unsigned)((n_total + SY_T - 1) / SY_T);
-    hipLaunchKernelGGL(sync_corr_kernel, dim3(grid), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+    hipLaunchKernelGGL(sync_corr_kernel<false>, dim3(grid), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                        reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_total);
     hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                        reinterpret_cast<float2 *>(xh_out), SY_H, n_total);
@@ -1095,7 +1190,7 @@ static void sync_average_argmax(float *cv, float *corr, int n, int F, float alph
         hipLaunchKernelGGL(sync_metric_argmax_kernel<96>, dim3(nwg, S), dim3(64 * (SYM_NC + 12)), 0, s, cv, corr, t.keys, n, F, alpha, end_vec, (const float *)t.seg, seg_F);
     }
     else hipLaunchKernelGGL(sync_metric_argmax4_kernel, dim3(nwg), dim3(256), 0, s, cv, corr, t.keys, n, F, alpha, end_vec);
-    hipLaunchKernelGGL(sync_finalize_kernel, dim3(F), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, F);
+    hipLaunchKernelGGL(sync_finalize_kernel<false>, dim3(F), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, F);
 }
 
 // the one-task form: correlators + instantaneous metric fused (nothing but m leaves the chip), then the average / arg max as above
@@ -1105,7 +1200,7 @@ hipError_t sync_corr_metric_launch(const float *x, const float *xh_in, float *xh
     const long long tot = (long long)n * F;
     if (sync_mfma_usable(x, frag)) (void)sync_corr_m_mfma_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, tot, s);
     else {
-        hipLaunchKernelGGL(sync_corr_m_kernel, dim3((unsigned)((tot + SY_T - 1) / SY_T)), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
+        hipLaunchKernelGGL(sync_corr_m_kernel<false>, dim3((unsigned)((tot + SY_T - 1) / SY_T)), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
                            reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, tot);
         hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                            reinterpret_cast<float2 *>(xh_out), SY_H, tot);
@@ -1123,6 +1218,60 @@ hipError_t sync_metric_launch(const float *cor_sof, const float *sofh_in, float 
     hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
                        reinterpret_cast<float2 *>(sofh_out), 64, tot);
     sync_average_argmax(cv, corr, n, F, alpha, vec_width, t, s);
+    return hipGetLastError();
+}
+
+// ---- S > 1 streams per call (dvbs2hip_set_streams): stream s = frames [s Fs, (s + 1) Fs) of every socket; all state is laid out stream after stream
+hipError_t sync_corr_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
+{
+    if (sync_mfma_usable(x, frag) && n_per % 2 == 0) return sync_corr_mfma_streams_launch(x, xh_in, xh_out, frag, nullptr, nullptr, nullptr, cor_sof, cor_plsc, n_per, S, s);
+    hipLaunchKernelGGL(sync_corr_kernel<true>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
+                       reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
+    hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                       reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
+    return hipGetLastError();
+}
+
+static void sync_average_argmax_streams(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
+{
+    const int end_vec = (n / vec_width) * vec_width, nwg = (n + 63) / 64;
+    hipLaunchKernelGGL(sync_average_argmax_streams_kernel, dim3(nwg, S), dim3(64), 0, s, cv, (const float *)corr, t.keys, n, Fs, alpha, end_vec);
+    hipLaunchKernelGGL(sync_finalize_kernel<true>, dim3(Fs, S), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, Fs);
+}
+
+hipError_t sync_corr_metric_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
+                                           const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
+{
+    const long long n_per = (long long)n * Fs;
+    if (sync_mfma_usable(x, frag) && n_per % 2 == 0) (void)sync_corr_mfma_streams_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, nullptr, nullptr, n_per, S, s);
+    else {
+        hipLaunchKernelGGL(sync_corr_m_kernel<true>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
+                           reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, n_per);
+        hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                           reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
+    }
+    sync_average_argmax_streams(cv, corr, n, Fs, S, alpha, vec_width, t, s);
+    return hipGetLastError();
+}
+
+hipError_t sync_metric_streams_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
+                                      const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
+{
+    const long long n_per = (long long)n * Fs;
+    hipLaunchKernelGGL(sync_m_streams_kernel, dim3((unsigned)((n_per + 255) / 256), S), dim3(256), 0, s, reinterpret_cast<const float2 *>(cor_sof),
+                       reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<const float2 *>(cor_plsc), corr, n_per);
+    hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
+                       reinterpret_cast<float2 *>(sofh_out), 64, n_per);
+    sync_average_argmax_streams(cv, corr, n, Fs, S, alpha, vec_width, t, s);
+    return hipGetLastError();
+}
+
+hipError_t sync_vdelay_streams_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
+                                      const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s)
+{
+    const int tot = ((nbuff2 > 2 * n ? nbuff2 : 2 * n) + 3) / 4;     // pairs of complex samples
+    const int gx = (tot + 256 * VD_SPL - 1) / (256 * VD_SPL);
+    hipLaunchKernelGGL(sync_vdelay_batch_kernel<true>, dim3(gx, Fs + 1, S), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, Fs, (const int32_t *)nullptr);
     return hipGetLastError();
 }
 
@@ -1161,10 +1310,10 @@ hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_n
         hipLaunchKernelGGL(sync_locate_kernel, dim3(1), dim3(1024), 0, s, X, Y, Dtab, n, nbuff2, F, list, src);
         // rows of the grid share the list's entries: in lock three of them have work (first frame, last frame, state row), while the synchronizer acquires all do
         const int gy = F + 1 < 64 ? F + 1 : 64;
-        hipLaunchKernelGGL(sync_vdelay_batch_kernel, dim3(gx, gy), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)list);
+        hipLaunchKernelGGL(sync_vdelay_batch_kernel<false>, dim3(gx, gy), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)list);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(sync_vdelay_batch_kernel, dim3(gx, F + 1), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)nullptr);
+    hipLaunchKernelGGL(sync_vdelay_batch_kernel<false>, dim3(gx, F + 1), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)nullptr);
     return hipGetLastError();
 }
 

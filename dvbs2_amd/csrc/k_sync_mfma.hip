@@ -172,9 +172,9 @@ __device__ __forceinline__ void sm_body(uint16_t *lds, const float2 *__restrict_
 // frag: [PLSC | SOF][K step][lane] band fragments (host-made, 6 KB, L2-resident)
 // (26 KB of LDS leave six workgroups per CU; the register allocator is told so, or it settles for 104 registers = four)
 template <bool FUSED>
-__global__ void __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
-sync_corr_mfma_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, float2 *__restrict__ xh_out, const uint4 *__restrict__ frag, const float2 *__restrict__ sofh,
-                      float2 *__restrict__ sofh_out, float *__restrict__ corr, float2 *__restrict__ cor_sof, float2 *__restrict__ cor_plsc, long long n_total)
+__device__ __forceinline__ void
+sync_corr_mfma_wg(const float2 *__restrict__ x, const float2 *__restrict__ xh, float2 *__restrict__ xh_out, const uint4 *__restrict__ frag, const float2 *__restrict__ sofh,
+                  float2 *__restrict__ sofh_out, float *__restrict__ corr, float2 *__restrict__ cor_sof, float2 *__restrict__ cor_plsc, long long n_total)
 {
     __shared__ __attribute__((aligned(16))) uint16_t lds[6 * SM_PLANE];
     const long long blk0 = (long long)blockIdx.x * SM_TILE;
@@ -185,6 +185,24 @@ sync_corr_mfma_kernel(const float2 *__restrict__ x, const float2 *__restrict__ x
     }
     if (blk0 >= SM_HALO + 1 && blk0 + SM_TILE + 2 <= n_total - 64) sm_body<FUSED, false>(lds, x, xh, frag, sofh, sofh_out, corr, cor_sof, cor_plsc, n_total, blk0);
     else sm_body<FUSED, true>(lds, x, xh, frag, sofh, sofh_out, corr, cor_sof, cor_plsc, n_total, blk0);
+}
+template <bool FUSED>
+__global__ void __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
+sync_corr_mfma_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, float2 *__restrict__ xh_out, const uint4 *__restrict__ frag, const float2 *__restrict__ sofh,
+                      float2 *__restrict__ sofh_out, float *__restrict__ corr, float2 *__restrict__ cor_sof, float2 *__restrict__ cor_plsc, long long n_total)
+{
+    sync_corr_mfma_wg<FUSED>(x, xh, xh_out, frag, sofh, sofh_out, corr, cor_sof, cor_plsc, n_total);
+}
+// S streams per call (dvbs2hip_set_streams): row s of the grid is the one-stream launch on stream s alone -- n_per samples (an even number: the 16-byte loads) at
+// x + s n_per, its memories at xh + 64 s and sofh + 64 s.  The halo of a stream's first tile is that stream's memory.
+template <bool FUSED>
+__global__ void __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
+sync_corr_mfma_streams_kernel(const float2 *__restrict__ x, const float2 *__restrict__ xh, float2 *__restrict__ xh_out, const uint4 *__restrict__ frag, const float2 *__restrict__ sofh,
+                              float2 *__restrict__ sofh_out, float *__restrict__ corr, float2 *__restrict__ cor_sof, float2 *__restrict__ cor_plsc, long long n_per)
+{
+    const size_t s = blockIdx.y, o = s * (size_t)n_per;
+    if (FUSED) sync_corr_mfma_wg<true>(x + o, xh + s * SM_H, xh_out + s * SM_H, frag, sofh + s * 64, sofh_out + s * 64, corr + o, nullptr, nullptr, n_per);
+    else sync_corr_mfma_wg<false>(x + o, xh + s * SM_H, xh_out + s * SM_H, frag, nullptr, nullptr, nullptr, cor_sof + o, cor_plsc + o, n_per);
 }
 
 static inline uint16_t sm_bf16_of(float v) { uint32_t u; std::memcpy(&u, &v, 4); return (uint16_t)(u >> 16); }     // +-1 and 0: exact
@@ -226,6 +244,22 @@ hipError_t sync_corr_m_mfma_launch(const float *x, const float *xh_in, float *xh
     hipLaunchKernelGGL(sync_corr_mfma_kernel<true>, dim3(grid), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                        reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, nullptr, nullptr,
                        n_total);
+    return hipGetLastError();
+}
+
+// S streams: corr != null is the one-task form (sofh_in / sofh_out its memories), else both correlations go to their sockets
+hipError_t sync_corr_mfma_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
+                                         float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
+{
+    const dim3 grid((unsigned)((n_per + SM_TILE - 1) / SM_TILE), S);
+    if (corr)
+        hipLaunchKernelGGL(sync_corr_mfma_streams_kernel<true>, grid, dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                           reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr,
+                           (float2 *)nullptr, (float2 *)nullptr, n_per);
+    else
+        hipLaunchKernelGGL(sync_corr_mfma_streams_kernel<false>, grid, dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                           reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), (const float2 *)nullptr, (float2 *)nullptr, (float *)nullptr,
+                           reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
     return hipGetLastError();
 }
 

@@ -113,6 +113,7 @@ ABI = {
     "dvbs2hip_sync_timing_set_params": (C.c_int, [_vp, _f, _f, _f]),
     "dvbs2hip_sync_timing_get_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "dvbs2hip_sync_timing_set_streams": (C.c_int, [_vp, _i]),
+    "dvbs2hip_set_streams": (C.c_int, [_vp, _i]),
     "dvbs2hip_sync_timing_reset": (C.c_int, [_vp]),
     "dvbs2hip_sync_timing_set_type": (C.c_int, [_vp, _i, _i]),
     "dvbs2hip_sync_timing_set_act": (C.c_int, [_vp, _i]),

@@ -242,6 +242,12 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_sync_timing_set_streams(self.h, int(S)))
         self.stm_streams = int(S)
 
+    def set_streams(self, S):
+        """S independent streams per call in every receive task that keeps a memory (timing, step_mf, coarse shift, matched filter, frame synchronizer, L&R): stream s =
+        frames [s F/S, (s+1) F/S); clears every stream's state"""
+        self._chk(self.L.dvbs2hip_set_streams(self.h, int(S)))
+        self.stm_streams = self.streams = int(S)
+
     def sync_timing_reset(self):
         self._chk(self.L.dvbs2hip_sync_timing_reset(self.h))
 
@@ -574,6 +580,11 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_rx_bb_located_dev(self.h, SRC, _ptr(sigma), _ptr(info), _ptr(cwd_ldpc), _ptr(cwd_bch), n_frames))
 
     def sync_frame_metric(self):
+        S = getattr(self, "streams", 1)
+        if S > 1:                                             # set_streams: one entry per stream
+            m, fl = np.empty(S, np.float32), np.empty(S, np.int32)
+            self._chk(self.L.dvbs2hip_sync_frame_get_metric(self.h, m.ctypes.data_as(C.POINTER(C.c_float)), fl.ctypes.data_as(C.POINTER(C.c_int32))))
+            return m, fl.astype(bool)
         m, fl = C.c_float(), C.c_int32()
         self._chk(self.L.dvbs2hip_sync_frame_get_metric(self.h, C.byref(m), C.byref(fl)))
         return m.value, bool(fl.value)

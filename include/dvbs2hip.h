@@ -200,6 +200,10 @@ int dvbs2hip_demodulate_deinterleave_dev(dvbs2hip_t *h, const float *CP, const f
  * Filter_FIR_ccr.hpp:39-52), bound RX/main_sched.cpp:199-201.  The n_frames frames of
  * one call are consecutive in time; the last (n_taps-1) complex samples are kept in the
  * handle between calls (Filter_FIR_ccr.cpp:80-83); dvbs2hip_filter_reset zeroes them.
+ * After dvbs2hip_set_streams(h, S > 1) the call carries S streams (stream s = frames
+ * [s F/S, (s+1) F/S), n_frames a multiple of S), each with a memory of its own, and stream s
+ * is filtered exactly as a one-stream call on its frames alone; dvbs2hip_filter_reset zeroes
+ * every stream's memory.  filter / filter1 follow it; filter2 has no memory and does not.
  *   X_N1, Y_N2 : float[n_frames * 2 * n_cplx]                                        */
 int dvbs2hip_filter(dvbs2hip_t *h, const float *X_N1, float *Y_N2, int32_t n_cplx, int32_t n_frames);
 int dvbs2hip_filter_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N2, int32_t n_cplx, int32_t n_frames);
@@ -425,6 +429,22 @@ int dvbs2hip_extract_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx
 int dvbs2hip_sync_timing_set_params(dvbs2hip_t *h, float damping, float nbw, float detector_gain);
 int dvbs2hip_sync_timing_get_gains(dvbs2hip_t *h, float *proportional, float *integrator);
 int dvbs2hip_sync_timing_set_streams(dvbs2hip_t *h, int32_t S);
+/* S independent streams per call in every receive task that keeps a memory: stream s = frames [s F/S, (s+1) F/S) of a call.
+ * = dvbs2hip_sync_timing_set_streams(h, S) (timing, step_mf, coarse shift: as above) AND the block-wise matched filter (dvbs2hip_filter / filter1), the frame synchronizer
+ * (synchronize1 / synchronize2 / synchronize) and L&R (dvbs2hip_sync_lr_synchronize), which dvbs2hip_sync_timing_set_streams alone leaves at one stream: the handle keeps
+ * two counts, this entry sets both.  The default is 1, and a handle that never calls it behaves in every entry as it did before the entry existed.  S < 1 or S > max_frames
+ * (or > 65535): DVBS2HIP_EINVAL; an open capture: DVBS2HIP_EINVAL.  It clears every stream's state of all the tasks it governs, also when S does not change (S = 1: the
+ * resets of the timing tasks, the matched filter, the frame synchronizer -- with the SOF delay, the previous output frame and the last metric, as a new handle -- and L&R).
+ * In the three block-wise tasks n_frames must be a multiple of S (else DVBS2HIP_EINVAL); unlike the timing tasks F/S may change from call to call.  Per stream the
+ * operations are those of a one-stream handle fed that stream's frames in the same calls: same results, bit for bit (L&R: those of its three-kernel form, DVBS2HIP_LR=unfused).
+ * Per-stream state is allocated by the first call that needs it (inside a capture: run the sequence once before); a failed allocation returns DVBS2HIP_ENOMEM and leaves
+ * the handle with the state it had.  dvbs2hip_sync_frame_get_metric writes S entries per output; dvbs2hip_sync_frame_reset, dvbs2hip_sync_lr_reset and
+ * dvbs2hip_filter_reset clear all streams.  With S > 1 L&R always runs as three kernels (pilots, one workgroup per stream for the recurrence, rotation): no workgroup
+ * waits for another, and dvbs2hip_sync_lr_timeouts keeps counting one-launch calls only.
+ * What stays one stream per handle: the located form (dvbs2hip_sync_frame_locate_dev and dvbs2hip_rx_bb_located_dev return DVBS2HIP_EUNSUPPORTED while S > 1: "one run of
+ * the input stream" is an argument about one stream), the task sequences above the C ABI (RxSequence, acquire) and the host/ modules, and the TX / channel side:
+ * filter2 (no memory), shape_filter, channel_delay, channel_freq_shift, add_noise.  Every stateless receive task takes the frames of S streams in one call anyway. */
+int dvbs2hip_set_streams(dvbs2hip_t *h, int32_t S);
 int dvbs2hip_sync_timing_reset(dvbs2hip_t *h);
 int dvbs2hip_sync_timing_synchronize(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t n_frames);
 int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *Y_N1, int32_t *B_N1, float *MU, int32_t n_frames);
@@ -477,7 +497,9 @@ int dvbs2hip_channel_freq_shift_dev(dvbs2hip_t *h, const float *X, float *Y, int
  * State is shared with the block-wise tasks, as the reference's modules share theirs: the loop runs on the timing synchronizer's per-stream state (so that
  * dvbs2hip_sync_timing_synchronize / _extract carry on from it), on the coarse synchronizer's frequency and sample counter (so that dvbs2hip_sync_coarse_synchronize carries
  * on with the learned frequency and a continuous phase; with S streams that state is per stream, and set_freq sets all of them) and, with one stream, on the matched
- * filter's memory (dvbs2hip_filter / filter1 carry on from it and back; with S > 1 the loop keeps a memory per stream of its own, as the block-wise filter is one stream).
+ * filter's memory (dvbs2hip_filter / filter1 carry on from it and back).  With S > 1 the same holds per stream when the block-wise filter runs on the same S streams
+ * (dvbs2hip_set_streams: every stream's last 80 samples cross the switch between the loop and dvbs2hip_filter*, in both directions); after dvbs2hip_sync_timing_set_streams
+ * alone the block-wise filter is one stream and the loop keeps a memory per stream of its own.
  * set_pll = set_PLL_coeffs(pll_sps, damping, nbw) (.cpp:94-113; defaults 1, sqrt(0.5), 1e-4); get_gains: the proportional and integrator gains that follow;
  * get_freq: per stream (float[S] each) estimated_freq and the nu in use (floored to six decimals, = -estimated_freq).  step_mf_reset = Synchronizer_step_mf_cc::reset: the coarse
  * synchronizer, the matched filter's memory and the timing synchronizer.  dvbs2hip_sync_coarse_reset also clears the PLL.
@@ -501,7 +523,8 @@ int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h);
  *   synchronize2 (:222-299)  cor_SOF delayed by 64, correlation metric, alpha-average, arg max -> delay,
  *                            variable output delay (Filter/Variable_delay/Variable_delay_cc_naive.cpp:56-79)
  *   synchronize  (:46-128)   both in one task
- * A call carries n_frames PL frames that are consecutive in time and behaves as n_frames calls of the
+ * A call carries n_frames PL frames that are consecutive in time -- after dvbs2hip_set_streams(h, S > 1): S streams of
+ * n_frames / S consecutive frames each, every stream with a state of its own -- and behaves per stream as that many calls of the
  * reference task with its n_frames = 1 (the reference's delay line re-reads its own output socket, so
  * its multi-frame form depends on what the socket held before; that case is not reproduced).  State
  * (correlator memories, reg_channel, corr_vec, delay lines, previous output frame) lives in the handle.
@@ -509,7 +532,7 @@ int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h);
  *   NULL): int32_t[n_frames]; TRI (metric, may be NULL): float[n_frames] -- the sockets of Synchronizer_frame.hxx:40-81
  * set_params: alpha / trigger (defaults 0.9 / 30) and vec_width = mipp::N<float>() of the reference build
  * (default 8 = AVX2): the samples past the last full vector of a frame are not alpha-averaged (:284-285).
- * get_metric: _get_metric / _get_packet_flag (.hpp:59-60) after the last frame processed.            */
+ * get_metric: _get_metric / _get_packet_flag (.hpp:59-60) after the last frame processed; with S streams, S entries each (float[S], int32_t[S]). */
 int dvbs2hip_sync_frame_set_params(dvbs2hip_t *h, float alpha, float trigger, int32_t vec_width);
 int dvbs2hip_sync_frame_reset(dvbs2hip_t *h);
 int dvbs2hip_sync_frame_synchronize1(dvbs2hip_t *h, const float *X_N1, float *cor_SOF, float *cor_PLSC, int32_t n_frames);
