@@ -286,7 +286,7 @@ tx_mod_kernel(const TxKParams p)
         if (i0 >= p.pl_frame) continue;
         const bool two = i0 + 1 < p.pl_frame;
         float2 y0 = tx_symbol<BPS, ITL>(p, cs, cw, i0, n_pil), y1 = two ? tx_symbol<BPS, ITL>(p, cs, cw, i0 + 1, n_pil) : make_float2(0.f, 0.f);
-        if (p.sigma) {
+        if (sg != 0.f) {                                             // (sigma = 0 is the noiseless frame bit for bit: adding 0 * n would turn a -0 of the constellation into +0)
             const uint4 r = philox4x32(make_uint4((uint32_t)pr, (uint32_t)f, 1u, 0u), make_uint2(p.seed_lo, p.seed_hi));
             // Box-Muller on the hardware units: v_log_f32, v_sqrt_f32, and v_sin_f32 / v_cos_f32, which take their argument in
             // revolutions (u2 itself) -- the accurate libm forms cost ~10x the instructions and the noise needs none of it
@@ -309,11 +309,13 @@ __global__ void awgn_kernel(const float2 *x, float2 *y, const float *sigma, uint
     const int f = blockIdx.y;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pairs) return;
+    const float sg = sigma[f];
+    const float2 v = x[(size_t)f * n_pairs + i];
+    if (sg == 0.f) { y[(size_t)f * n_pairs + i] = v; return; }          // the frame itself, bit for bit (v + 0 * n would turn -0 into +0)
     const uint4 r = philox4x32(make_uint4((uint32_t)i, (uint32_t)f, 2u, (uint32_t)(i >> 32)), make_uint2(seed_lo, seed_hi));
     const float u1 = ((float)r.x + 1.0f) * 2.3283064365386963e-10f, u2 = (float)r.y * 2.3283064365386963e-10f;
-    const float rad = sigma[f] * __builtin_amdgcn_sqrtf(-2.0f * hw_log(u1));
+    const float rad = sg * __builtin_amdgcn_sqrtf(-2.0f * hw_log(u1));
     const float sn = __builtin_amdgcn_sinf(u2), cn = __builtin_amdgcn_cosf(u2);
-    const float2 v = x[(size_t)f * n_pairs + i];
     y[(size_t)f * n_pairs + i] = make_float2(v.x + rad * cn, v.y + rad * sn);
 }
 hipError_t awgn_launch(const float *x, float *y, const float *sigma, unsigned long long seed, long long n_pairs, int F, hipStream_t s)
