@@ -39,19 +39,19 @@ static int stm_alloc(dvbs2hip_t *h, int S)
     const int n_alloc = std::max(T.n_alloc, S);                         // (streams the buffers hold once every allocation below has succeeded)
     if (T.n_alloc < S) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &T.st[i])); HIPCHK(h, dev_free(h, &T.ccnt[i])); HIPCHK(h, dev_free(h, &T.carry[i])); }
+        for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &T.st.p[i])); HIPCHK(h, dev_free(h, &T.ccnt.p[i])); HIPCHK(h, dev_free(h, &T.carry.p[i])); }
         T.cap = 0;
         T.n_alloc = 0;
         const char *what = "hipMalloc of the timing synchronizer's state failed";
         for (int i = 0; i < 2; i++)
-            if ((r = dev_alloc(h, &T.st[i], sizeof(StmState) * (size_t)S, what)) || (r = dev_alloc(h, &T.ccnt[i], sizeof(int32_t) * (size_t)S, what))) return r;
+            if ((r = dev_alloc(h, &T.st.p[i], sizeof(StmState) * (size_t)S, what)) || (r = dev_alloc(h, &T.ccnt.p[i], sizeof(int32_t) * (size_t)S, what))) return r;
     }
     if (!T.uf && (r = dev_alloc(h, &T.uf, sizeof(int32_t) * (size_t)h->max_frames, "hipMalloc of the timing synchronizer's underflow counters failed"))) return r;
     T.n_alloc = n_alloc;
-    T.st_cur = T.c_cur = 0;
+    T.st.cur = T.carry.cur = T.ccnt.cur = 0;
     T.Fs = 0;
-    HIPCHK(h, hipMemsetAsync(T.st[0], 0, sizeof(StmState) * (size_t)S, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.ccnt[0], 0, sizeof(int32_t) * (size_t)S, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.st.in(), 0, sizeof(StmState) * (size_t)S, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.ccnt.in(), 0, sizeof(int32_t) * (size_t)S, h->stream));
     HIPCHK(h, hipMemsetAsync(T.uf, 0, sizeof(int32_t) * (size_t)h->max_frames, h->stream));
     return 0;
 }
@@ -78,11 +78,11 @@ static int stm_carry(dvbs2hip_t *h, long long cap)
     for (int i = 0; i < 2; i++)      // both buffers or neither
         if (int r = dev_alloc(h, &nb[i], sizeof(float) * (size_t)cap * (size_t)T.n_alloc, "hipMalloc of the timing synchronizer's carry buffers failed")) { (void)dev_free(h, &nb[0]); return r; }
     if (T.cap > 0) {
-        HIPCHK(h, hipMemcpy2DAsync(nb[T.c_cur], sizeof(float) * (size_t)cap, T.carry[T.c_cur], sizeof(float) * (size_t)T.cap, sizeof(float) * (size_t)T.cap, (size_t)T.n_alloc,
+        HIPCHK(h, hipMemcpy2DAsync(nb[T.carry.cur], sizeof(float) * (size_t)cap, T.carry.in(), sizeof(float) * (size_t)T.cap, sizeof(float) * (size_t)T.cap, (size_t)T.n_alloc,
                                    hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &T.carry[i])); T.carry[i] = nb[i]; }
+    for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &T.carry.p[i])); T.carry.p[i] = nb[i]; }
     T.cap = cap;
     return 0;
 }
@@ -150,10 +150,10 @@ int dvbs2hip_sync_timing_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float
     if ((r = stm_begin(h, F, "synchronize"))) return r;
     Timer tm(h, DVBS2HIP_K_MISC);
     if (T.type == DVBS2HIP_STM_ULTRA)
-        HIPCHK(h, stm_ultra_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.hold, T.act ? 1 : 0, T.kp, T.ki, h->stream));
+        HIPCHK(h, stm_ultra_launch(X_N1, Y_N1, B_N1, MU, T.st.in(), T.st.out(), T.S, F / T.S, stm_frame_cplx(h), T.hold, T.act ? 1 : 0, T.kp, T.ki, h->stream));
     else
-        HIPCHK(h, stm_sync_launch(X_N1, Y_N1, B_N1, MU, T.st[T.st_cur], T.st[T.st_cur ^ 1], T.S, F / T.S, stm_frame_cplx(h), T.kp, T.ki, h->stream));
-    T.st_cur ^= 1;
+        HIPCHK(h, stm_sync_launch(X_N1, Y_N1, B_N1, MU, T.st.in(), T.st.out(), T.S, F / T.S, stm_frame_cplx(h), T.kp, T.ki, h->stream));
+    T.st.flip();
     return 0;
 }
 
@@ -179,8 +179,8 @@ int dvbs2hip_sync_timing_extract_dev(dvbs2hip_t *h, const float *Y_N1, const int
         if ((r = stm_carry(h, cap))) return r;
     }
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, stm_extract_launch(Y_N1, B_N1, Y_N2, UFW, RDY, T.carry[T.c_cur], T.ccnt[T.c_cur], T.carry[T.c_cur ^ 1], T.ccnt[T.c_cur ^ 1], T.uf, T.S, Fs, N, T.cap, h->stream));
-    T.c_cur ^= 1;
+    HIPCHK(h, stm_extract_launch(Y_N1, B_N1, Y_N2, UFW, RDY, T.carry.in(), T.ccnt.in(), T.carry.out(), T.ccnt.out(), T.uf, T.S, Fs, N, T.cap, h->stream));
+    T.carry.flip(), T.ccnt.flip();
     return 0;
 }
 
@@ -203,15 +203,15 @@ int dvbs2hip_channel_set_delay(dvbs2hip_t *h, float D)
     auto &C = h->chn;
     farrow_taps(D - floorf(D), C.b[0], C.b[1], C.b[2]);                 // mu: DVBS2.cpp:522
     const long long H = (long long)floorf(D) + 1;                       // (floor(D) - 2) samples of delay line + 3 of the Farrow filter
-    if (H > C.H || !C.hist[0]) {
+    if (H > C.H || !C.hist.p[0]) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (int i = 0; i < 2; i++) {
-            HIPCHK(h, dev_free(h, &C.hist[i]));
-            if (int r = dev_alloc(h, &C.hist[i], sizeof(float) * 2 * (size_t)H, "hipMalloc of the channel delay's history failed")) return r;
+            HIPCHK(h, dev_free(h, &C.hist.p[i]));
+            if (int r = dev_alloc(h, &C.hist.p[i], sizeof(float) * 2 * (size_t)H, "hipMalloc of the channel delay's history failed")) return r;
         }
     }
-    C.D = D; C.H = H; C.cur = 0;
-    HIPCHK(h, hipMemsetAsync(C.hist[0], 0, sizeof(float) * 2 * (size_t)H, h->stream));
+    C.D = D; C.H = H; C.hist.cur = 0;
+    HIPCHK(h, hipMemsetAsync(C.hist.in(), 0, sizeof(float) * 2 * (size_t)H, h->stream));
     return 0;
 }
 
@@ -220,10 +220,10 @@ int dvbs2hip_channel_delay_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t 
     int r = check_frames(h, F); if (r) return r;
     if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     auto &C = h->chn;
-    if (!C.hist[0] && (r = dvbs2hip_channel_set_delay(h, C.D))) return r;
+    if (!C.hist.p[0] && (r = dvbs2hip_channel_set_delay(h, C.D))) return r;
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, chn_delay_launch(X, Y, C.hist[C.cur], C.hist[C.cur ^ 1], C.H, (long long)F * stm_frame_cplx(h), C.b[0], C.b[1], C.b[2], h->stream));
-    C.cur ^= 1;
+    HIPCHK(h, chn_delay_launch(X, Y, C.hist.in(), C.hist.out(), C.H, (long long)F * stm_frame_cplx(h), C.b[0], C.b[1], C.b[2], h->stream));
+    C.hist.flip();
     return 0;
 }
 
@@ -256,7 +256,7 @@ static int sfc_host(dvbs2hip_t *h)
     }
     if (C.where == C.DEV) {
         if (h->capturing) return fail(h, DVBS2HIP_EUNSUPPORTED, "the coarse synchronizer's state has to come back from the device: not inside a capture");
-        HIPCHK(h, hipMemcpyAsync(C.hs.data(), C.cf[C.cf_cur], sizeof(SfcState) * S, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(C.hs.data(), C.cf.in(), sizeof(SfcState) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (size_t s = 0; s < S; s++) C.frq[s] = C.hs[s].est;         // after the loop FRQ is estimated_freq (Synchronizer_freq_coarse.hxx:121-124)
         C.where = C.BOTH;
@@ -372,18 +372,18 @@ static int sfc_dev(dvbs2hip_t *h)
     }
     if (C.n_alloc < S) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &C.cf[i])); HIPCHK(h, dev_free(h, &C.hist[i])); }
+        for (int i = 0; i < 2; i++) { HIPCHK(h, dev_free(h, &C.cf.p[i])); HIPCHK(h, dev_free(h, &C.hist.p[i])); }
         C.n_alloc = 0;
         const char *what = "hipMalloc of the coarse synchronizer's state failed";
         for (int i = 0; i < 2; i++)
-            if ((r = dev_alloc(h, &C.cf[i], sizeof(SfcState) * (size_t)S, what)) || (r = dev_alloc(h, &C.hist[i], SMF_HIST_BYTES * (size_t)S, what))) return r;
-        HIPCHK(h, hipMemsetAsync(C.hist[0], 0, SMF_HIST_BYTES * (size_t)S, h->stream));
-        C.hist_cur = 0;
+            if ((r = dev_alloc(h, &C.cf.p[i], sizeof(SfcState) * (size_t)S, what)) || (r = dev_alloc(h, &C.hist.p[i], SMF_HIST_BYTES * (size_t)S, what))) return r;
+        C.hist.cur = 0;
+        HIPCHK(h, hipMemsetAsync(C.hist.in(), 0, SMF_HIST_BYTES * (size_t)S, h->stream));
         C.n_alloc = S;
         C.where = C.HOST;
     }
     if (C.hist_stale) {                                                // (the buffers just allocated are clear already; older ones hold other streams' samples)
-        HIPCHK(h, hipMemsetAsync(C.hist[C.hist_cur], 0, SMF_HIST_BYTES * (size_t)C.n_alloc, h->stream));
+        HIPCHK(h, hipMemsetAsync(C.hist.in(), 0, SMF_HIST_BYTES * (size_t)C.n_alloc, h->stream));
         C.hist_stale = false;
     }
     if (!C.pil) {
@@ -402,7 +402,7 @@ static int sfc_dev(dvbs2hip_t *h)
         C.n_p = n_p;
     }
     if (C.where == C.HOST) {
-        HIPCHK(h, hipMemcpyAsync(C.cf[C.cf_cur], C.hs.data(), sizeof(SfcState) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(C.cf.in(), C.hs.data(), sizeof(SfcState) * (size_t)S, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));                   // (pageable source: the copy has left the host buffer before it can change)
         C.where = C.BOTH;
     }
@@ -430,20 +430,19 @@ int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, con
     float pg, ig;
     sfc_gains(C.pll_sps, C.damping, C.nbw, pg, ig);
     // the matched filter's memory is the block-wise filter's own (the last 80 input samples per stream, oldest first) when the two stream counts agree, so dvbs2hip_filter*
-    // carry on from the loop and back: one stream on d_hist, S streams (dvbs2hip_set_streams) on bw.hist.  Otherwise the loop keeps a memory per stream of its own.
-    const bool shared = T.S == 1 && h->bw.S == 1, shared_s = T.S > 1 && h->bw.S == T.S;
-    if (shared_s) {
-        if ((r = bw_hist_ready(h))) return r;
-        if (started_over) HIPCHK(h, hipMemsetAsync(h->bw.hist[h->bw.hist_cur], 0, SMF_HIST_BYTES * (size_t)T.S, h->stream));
+    // carry on from the loop and back (bw_hist: d_hist at one stream, bw.hist at S).  Otherwise the loop keeps a memory per stream of its own, which sfc_dev has cleared
+    const bool shared = h->bw.S == T.S;
+    PingPong<float> *hist = &C.hist;
+    if (shared) {
+        if ((r = bw_hist(h, &hist))) return r;
+        if (started_over && T.S > 1) HIPCHK(h, hipMemsetAsync(hist->in(), 0, SMF_HIST_BYTES * (size_t)T.S, h->stream));      // (one stream carries on from dvbs2hip_filter* whatever the loop's state)
     }
-    const float *hin = shared ? h->d_hist[h->hist_cur] : shared_s ? h->bw.hist[h->bw.hist_cur] : C.hist[C.hist_cur];
-    float *hout = shared ? h->d_hist[h->hist_cur ^ 1] : shared_s ? h->bw.hist[h->bw.hist_cur ^ 1] : C.hist[C.hist_cur ^ 1];
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, stepmf_launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt[T.c_cur], T.st[T.st_cur], T.st[T.st_cur ^ 1], C.cf[C.cf_cur], C.cf[C.cf_cur ^ 1], hin, hout, h->d_taps_rev,
+    HIPCHK(h, stepmf_launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt.in(), T.st.in(), T.st.out(), C.cf.in(), C.cf.out(), hist->in(), hist->out(), h->d_taps_rev,
                             C.pil, C.n_p, T.S, F / T.S, stm_frame_cplx(h), h->pl_frame, T.kp, T.ki, pg, ig, (float)h->fir_osf, h->stream));
-    T.st_cur ^= 1;
-    C.cf_cur ^= 1;
-    if (shared) h->hist_cur ^= 1; else if (shared_s) h->bw.hist_cur ^= 1; else C.hist_cur ^= 1;
+    T.st.flip();
+    C.cf.flip();
+    hist->flip();
     C.where = C.DEV;
     return 0;
 }
@@ -463,9 +462,11 @@ int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h)                         // Synchr
     int r0 = enter(h); if (r0) return r0;
     if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "a capture is open on this handle");
     int r = dvbs2hip_sync_coarse_reset(h); if (r) return r;
-    if (h->stm.S == 1) { if (h->fir_T > 1 && h->d_hist[h->hist_cur]) HIPCHK(h, hipMemsetAsync(h->d_hist[h->hist_cur], 0, sizeof(float) * 2 * (size_t)(h->fir_T - 1), h->stream)); }
-    else if (h->bw.S == h->stm.S && h->bw.hist[h->bw.hist_cur] && h->bw.hist_n >= h->bw.S) HIPCHK(h, hipMemsetAsync(h->bw.hist[h->bw.hist_cur], 0, SMF_HIST_BYTES * (size_t)h->bw.S, h->stream));
-    else if (h->sfc.hist[h->sfc.hist_cur]) HIPCHK(h, hipMemsetAsync(h->sfc.hist[h->sfc.hist_cur], 0, SMF_HIST_BYTES * (size_t)h->sfc.n_alloc, h->stream));
+    // the memory the loop runs on (dvbs2hip_sync_step_mf_synchronize_dev): the block-wise filter's when the counts agree and it exists (nothing is allocated here), else the loop's own
+    PingPong<float> *hist = &h->sfc.hist;
+    size_t nb = SMF_HIST_BYTES * (size_t)h->sfc.n_alloc;
+    if (h->bw.S == h->stm.S && (h->bw.S == 1 || h->bw.hist_n >= h->bw.S)) { if ((r = bw_hist(h, &hist))) return r; nb = sizeof(float) * 2 * (size_t)(h->fir_T > 1 ? h->fir_T - 1 : 0) * (size_t)h->bw.S; }
+    if (nb && hist->in()) HIPCHK(h, hipMemsetAsync(hist->in(), 0, nb, h->stream));
     h->stm.act = false;
     return stm_alloc(h, h->stm.S);
 }

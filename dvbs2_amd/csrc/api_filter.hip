@@ -16,55 +16,50 @@ int dvbs2hip_set_filter_kernel(dvbs2hip_t *h, int32_t kernel)
 
 }  // extern "C"
 
-// the matched filter's memory for bw.S > 1 streams: both buffers or neither; a failure leaves what the handle had
-int dvbs2::bw_hist_ready(dvbs2hip_t *h)
+// the block-wise matched filter's memory for the handle's bw.S streams: d_hist at S = 1 (a part of d_hist_all), a pair of its own at S > 1 -- allocated and cleared on
+// first use, both buffers or neither; a failure leaves what the handle had
+int dvbs2::bw_hist(dvbs2hip_t *h, PingPong<float> **hist)
 {
     auto &B = h->bw;
-    if (B.hist_n >= B.S) return 0;
+    *hist = B.S == 1 ? &h->d_hist : &B.hist;
+    if (B.S == 1 || B.hist_n >= B.S) return 0;
     if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first call after dvbs2hip_set_streams allocates the streams' filter memory");
     const size_t nb = sizeof(float) * 2 * (size_t)(h->fir_T > 1 ? h->fir_T - 1 : 1) * (size_t)B.S;
     float *nw[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; i++)
         if (int r = dev_alloc(h, &nw[i], nb, "hipMalloc of the streams' filter memory failed")) { (void)dev_free(h, &nw[0]); return r; }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 2; i++) { (void)dev_free(h, &B.hist[i]); B.hist[i] = nw[i]; }
-    B.hist_n = B.S; B.hist_cur = 0;
-    HIPCHK(h, hipMemsetAsync(B.hist[0], 0, nb, h->stream));
+    for (int i = 0; i < 2; i++) { (void)dev_free(h, &B.hist.p[i]); B.hist.p[i] = nw[i]; }
+    B.hist_n = B.S; B.hist.cur = 0;
+    HIPCHK(h, hipMemsetAsync(B.hist.in(), 0, nb, h->stream));
     return 0;
 }
 
 extern "C" {
 
 // ------------------------------------------------------------------ a5
+// bw.S streams per call: every stream its own sample stream of n_cplx F/S samples, with its own memory
 int dvbs2hip_filter_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx, int32_t F)
 {
     int r = bw_check(h, F); if (r) return r;
     if (!X || !Y) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     if (h->fir_T <= 0) return fail(h, DVBS2HIP_EUNSUPPORTED, "handle was created without filter taps");
     if (n_cplx < 1) return fail(h, DVBS2HIP_EINVAL, "'n_cplx' has to be greater than 0");
-    if (h->bw.S > 1) {      // every stream its own sample stream of n_cplx F/S samples, with its own memory
-        auto &B = h->bw;
-        if ((r = bw_hist_ready(h))) return r;
-        Timer tm(h, DVBS2HIP_K_FIR);
-        HIPCHK(h, fir_streams_launch(X, Y, B.hist[B.hist_cur], B.hist[B.hist_cur ^ 1], h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
-                                     (long long)n_cplx * (F / B.S), B.S, h->stream));
-        B.hist_cur ^= 1;
-        return 0;
-    }
+    PingPong<float> *hist;
+    if ((r = bw_hist(h, &hist))) return r;
     Timer tm(h, DVBS2HIP_K_FIR);
-    HIPCHK(h, fir_launch(X, Y, h->d_hist[h->hist_cur], h->d_hist[h->hist_cur ^ 1], h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
-                         (long long)n_cplx * F, h->stream));
-    h->hist_cur ^= 1;
+    HIPCHK(h, fir_launch(X, Y, hist->in(), hist->out(), h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
+                         (long long)n_cplx * (F / h->bw.S), h->bw.S, h->stream));
+    hist->flip();
     return 0;
 }
 
 int dvbs2hip_filter(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx, int32_t F)
 {
-    if (h && h->bw.S > 1)      // several streams: the whole call at once (a chunk of a pinned socket would cut across the streams)
-        return host_wrap<false>(h, X, (size_t)2 * (n_cplx > 0 ? n_cplx : 0), Y, (size_t)2 * (n_cplx > 0 ? n_cplx : 0), F,
-                                [&](const float *a, float *b, int nf) { return dvbs2hip_filter_dev(h, a, b, n_cplx, nf); });
-    return host_wrap<true>(h, X, (size_t)2 * (n_cplx > 0 ? n_cplx : 0), Y, (size_t)2 * (n_cplx > 0 ? n_cplx : 0), F,
-                           [&](const float *a, float *b, int nf) { return dvbs2hip_filter_dev(h, a, b, n_cplx, nf); });
+    const size_t n = (size_t)2 * (n_cplx > 0 ? n_cplx : 0);
+    const auto dev = [&](const float *a, float *b, int nf) { return dvbs2hip_filter_dev(h, a, b, n_cplx, nf); };
+    // one stream: chunks of a pinned socket in order; several: the whole call at once (a chunk would cut across the streams)
+    return h && h->bw.S > 1 ? host_wrap<false>(h, X, n, Y, n, F, dev) : host_wrap<true>(h, X, n, Y, n, F, dev);
 }
 
 // filter1 / filter2: the reference splits the matched filter over two pipeline stages (Filter_FIR_ccr.cpp:144-294; bound
@@ -109,7 +104,7 @@ int dvbs2hip_filter2_dev(dvbs2hip_t *h, const float *X, const float *Yh, float *
     {   // the upper part of a frame reads nothing before the frame (split >= n_taps - 1): the state is neither used nor advanced
         Timer tm(h, DVBS2HIP_K_FIR);
         HIPCHK(h, fir_launch(X, (float *)tmp, h->d_hist_zero, h->d_hist_junk, h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
-                             (long long)n_cplx * F, h->stream));
+                             (long long)n_cplx * F, 1, h->stream));
     }
     const size_t lo = sizeof(float) * 2 * (size_t)split;
     if (Y != Yh) HIPCHK(h, hipMemcpy2DAsync(Y, row, Yh, row, lo, (size_t)F, hipMemcpyDeviceToDevice, h->stream));       // std::copy(Y_N2h, ..) :224
@@ -145,11 +140,11 @@ int dvbs2hip_filter_reset(dvbs2hip_t *h)
     int r0 = enter(h); if (r0) return r0;
     if (h->fir_T > 1 && h->d_hist_all) {      // buffers 0 become the current ones, zeroed by one memset (they are adjacent); buffers 1 are written before they are read
         HIPCHK(h, hipMemsetAsync(h->d_hist_all, 0, 2 * h->hist_stride, h->stream));
-        h->hist_cur = 0; h->uphist_cur = 0;
+        h->d_hist.cur = 0; h->d_uphist.cur = 0;
     }
-    if (h->bw.hist[0]) {                       // every stream's memory (dvbs2hip_set_streams)
-        HIPCHK(h, hipMemsetAsync(h->bw.hist[0], 0, sizeof(float) * 2 * (size_t)(h->fir_T > 1 ? h->fir_T - 1 : 1) * (size_t)h->bw.hist_n, h->stream));
-        h->bw.hist_cur = 0;
+    if (h->bw.hist.p[0]) {                     // every stream's memory (dvbs2hip_set_streams)
+        h->bw.hist.cur = 0;
+        HIPCHK(h, hipMemsetAsync(h->bw.hist.in(), 0, sizeof(float) * 2 * (size_t)(h->fir_T > 1 ? h->fir_T - 1 : 1) * (size_t)h->bw.hist_n, h->stream));
     }
     return 0;
 }
@@ -162,9 +157,9 @@ int dvbs2hip_shape_filter_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n
     if (h->fir_T <= 0) return fail(h, DVBS2HIP_EUNSUPPORTED, "handle was created without filter taps");
     if (n_cplx < 1) return fail(h, DVBS2HIP_EINVAL, "'n_cplx' has to be greater than 0");
     Timer tm(h, DVBS2HIP_K_FIR);
-    HIPCHK(h, upfir_launch(X, Y, h->d_uphist[h->uphist_cur], h->d_uphist[h->uphist_cur ^ 1], h->d_taps, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_upfir_afrag, h->fir_T, h->fir_osf,
+    HIPCHK(h, upfir_launch(X, Y, h->d_uphist.in(), h->d_uphist.out(), h->d_taps, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_upfir_afrag, h->fir_T, h->fir_osf,
                            (long long)n_cplx * F, h->stream));
-    h->uphist_cur ^= 1;
+    h->d_uphist.flip();
     return 0;
 }
 

@@ -59,14 +59,14 @@ static int sfm_state_reset(dvbs2hip_t *h, bool all)
         st0[s * SYNC_ST_STRIDE + 1] = 1;                                           // head2 = 0, first_time = true
     }
     for (int i = 0; i < 2; i++) {
-        HIPCHK(h, hipMemsetAsync(S.xh[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
-        HIPCHK(h, hipMemsetAsync(S.buff2[i], 0, sizeof(float) * (size_t)S.nbuff2 * ns, h->stream));
-        HIPCHK(h, hipMemcpyAsync(S.st[i], st0.data(), sizeof(int) * st0.size(), hipMemcpyHostToDevice, h->stream));
-        if (all) HIPCHK(h, hipMemsetAsync(S.sofh[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
+        HIPCHK(h, hipMemsetAsync(S.xh.p[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
+        HIPCHK(h, hipMemsetAsync(S.buff2.p[i], 0, sizeof(float) * (size_t)S.nbuff2 * ns, h->stream));
+        HIPCHK(h, hipMemcpyAsync(S.st.p[i], st0.data(), sizeof(int) * st0.size(), hipMemcpyHostToDevice, h->stream));
+        if (all) HIPCHK(h, hipMemsetAsync(S.sofh.p[i], 0, sizeof(float) * 2 * 64 * ns, h->stream));
     }
-    HIPCHK(h, hipMemcpyAsync(S.xh[S.xh_cur], xh0.data(), sizeof(float) * xh0.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(S.xh.in(), xh0.data(), sizeof(float) * xh0.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(S.cv, 0, sizeof(float) * (size_t)n * ns, h->stream));
-    if (all) { HIPCHK(h, hipMemsetAsync(S.yprev[S.yp_cur], 0, sizeof(float) * 2 * (size_t)n * ns, h->stream)); HIPCHK(h, hipMemsetAsync(S.metric, 0, sizeof(float) * ns, h->stream)); }
+    if (all) { HIPCHK(h, hipMemsetAsync(S.yprev.in(), 0, sizeof(float) * 2 * (size_t)n * ns, h->stream)); HIPCHK(h, hipMemsetAsync(S.metric, 0, sizeof(float) * ns, h->stream)); }
     HIPCHK(h, hipStreamSynchronize(h->stream));                                    // `xh0` / `st0` live on this stack
     return 0;
 }
@@ -93,13 +93,13 @@ static int sfm_alloc_streams(dvbs2hip_t *h, int ns)
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < 2; i++) {
-        (void)dev_free(h, &S.xh[i]); (void)dev_free(h, &S.sofh[i]); (void)dev_free(h, &S.buff2[i]); (void)dev_free(h, &S.st[i]); (void)dev_free(h, &S.yprev[i]);
-        S.xh[i] = xh[i]; S.sofh[i] = sofh[i]; S.buff2[i] = buff2[i]; S.st[i] = st[i]; S.yprev[i] = yprev[i];
+        (void)dev_free(h, &S.xh.p[i]); (void)dev_free(h, &S.sofh.p[i]); (void)dev_free(h, &S.buff2.p[i]); (void)dev_free(h, &S.st.p[i]); (void)dev_free(h, &S.yprev.p[i]);
+        S.xh.p[i] = xh[i]; S.sofh.p[i] = sofh[i]; S.buff2.p[i] = buff2[i]; S.st.p[i] = st[i]; S.yprev.p[i] = yprev[i];
     }
     (void)dev_free(h, &S.cv); (void)dev_free(h, &S.metric);
     S.cv = cv; S.metric = metric;
     S.n_alloc = ns;
-    S.xh_cur = S.sofh_cur = S.od_cur = S.yp_cur = 0;
+    S.xh.cur = S.sofh.cur = S.buff2.cur = S.st.cur = S.yprev.cur = 0;
     return sfm_state_reset(h, true);
 }
 
@@ -145,11 +145,9 @@ int dvbs2hip_sync_frame_synchronize1_dev(dvbs2hip_t *h, const float *X_N1, float
     if ((r = sfm_ready(h))) return r;
     auto &S = h->sfm;
     Timer tm(h, DVBS2HIP_K_MISC);
-    if (h->bw.S > 1)      // every stream from its own 64-sample memory
-        HIPCHK(h, sync_corr_streams_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * (F / h->bw.S), h->bw.S, h->stream));
-    else
-        HIPCHK(h, sync_corr_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * F, h->stream));
-    S.xh_cur ^= 1;
+    // every stream from its own 64-sample memory
+    HIPCHK(h, sync_corr_launch(X_N1, S.xh.in(), S.xh.out(), sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * (F / h->bw.S), h->bw.S, h->stream));
+    S.xh.flip();
     return 0;
 }
 
@@ -172,27 +170,13 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
     Timer tm(h, DVBS2HIP_K_MISC);
     if (TRI) met = TRI;
     const SyncTail tail{S.keys, delay, (float *)met, FLG, S.trigger, (int32_t *)dtab, S.metric, reinterpret_cast<float *>(S.keys + (size_t)h->max_frames * (size_t)((n + 63) / 64))};
-    if (NS > 1) {      // every stream on its own state; frame 0 of a stream continues from that stream's previous call
-        if (fused) {
-            HIPCHK(h, sync_corr_metric_streams_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], S.cv, (float *)corr, tail,
-                                                      n, Fs, NS, S.alpha, S.vec_width, h->stream));
-            S.xh_cur ^= 1;
-        } else
-            HIPCHK(h, sync_metric_streams_launch(cor_SOF, S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], cor_PLSC, S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
-        S.sofh_cur ^= 1;
-        HIPCHK(h, sync_vdelay_streams_launch(X_N1, S.yprev[S.yp_cur], S.yprev[S.yp_cur ^ 1], Y_N2, S.buff2[S.od_cur], S.buff2[S.od_cur ^ 1], S.st[S.od_cur], S.st[S.od_cur ^ 1],
-                                             (const int32_t *)dtab, n, S.nbuff2, Fs, NS, h->stream));
-        S.od_cur ^= 1;
-        S.yp_cur ^= 1;
-        return 0;
-    }
+    // every stream on its own state; frame 0 of a stream continues from that stream's previous call
     if (fused) {
-        HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh[S.xh_cur], S.xh[S.xh_cur ^ 1], sfm_frag(h), S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], S.cv, (float *)corr, tail,
-                                          n, F, S.alpha, S.vec_width, h->stream));
-        S.xh_cur ^= 1;
+        HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh.in(), S.xh.out(), sfm_frag(h), S.sofh.in(), S.sofh.out(), S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
+        S.xh.flip();
     } else
-        HIPCHK(h, sync_metric_launch(cor_SOF, S.sofh[S.sofh_cur], S.sofh[S.sofh_cur ^ 1], cor_PLSC, S.cv, (float *)corr, tail, n, F, S.alpha, S.vec_width, h->stream));
-    S.sofh_cur ^= 1;
+        HIPCHK(h, sync_metric_launch(cor_SOF, S.sofh.in(), S.sofh.out(), cor_PLSC, S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
+    S.sofh.flip();
     // the delay line is a recurrence from frame to frame made of copies only: resolved per output sample, one launch (k_sync.hip)
     void *need = nullptr;
     if (SRC) {      // located form: only the frames that are not a run of the input stream are materialized (into the handle's scratch); SRC[f] says where frame f starts
@@ -200,10 +184,10 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
         if ((r = ensure(h, B_SFM_SCR, sizeof(float) * 2 * (size_t)n * F, &scr)) || (r = ensure(h, B_SFM_NEED, sizeof(int32_t) * ((size_t)F + 2), &need))) return r;
         Y_N2 = (float *)scr;
     }
-    HIPCHK(h, sync_vdelay_launch(X_N1, S.yprev[S.yp_cur], S.yprev[S.yp_cur ^ 1], Y_N2, S.buff2[S.od_cur], S.buff2[S.od_cur ^ 1], S.st[S.od_cur], S.st[S.od_cur ^ 1],
-                                 (const int32_t *)dtab, n, S.nbuff2, F, h->stream, (int32_t *)need, SRC));
-    S.od_cur ^= 1;
-    S.yp_cur ^= 1;
+    HIPCHK(h, sync_vdelay_launch(X_N1, S.yprev.in(), S.yprev.out(), Y_N2, S.buff2.in(), S.buff2.out(), S.st.in(), S.st.out(), (const int32_t *)dtab, n, S.nbuff2, Fs, NS, h->stream,
+                                 (int32_t *)need, SRC));
+    S.buff2.flip(), S.st.flip();
+    S.yprev.flip();
     return 0;
 }
 
@@ -303,10 +287,9 @@ static int sff_call(dvbs2hip_t *h, bool lr, bool host, const float *X_N1, float 
     if ((r = ensure(h, lr ? B_LR_TMP0 + slot : B_SFF_TMP, sizeof(float) * 4 * (size_t)F, &tmp))) return r;
     auto launch = [&](const float *x, float *frq, float *phs, float *y) {
         Timer tm(h, DVBS2HIP_K_MISC);
-        if (lr && NS > 1) HIPCHK(h, sff_lr_streams_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, NS, h->lr_alpha, h->stream));      // three kernels: no waiting workgroup, nothing to look at later
-        else if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, h->lr_alpha, h->lr_err_dev + slot, h->stream));
+        if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, NS, h->lr_alpha, h->lr_err_dev + slot, h->stream));
         else HIPCHK(h, sff_fp_launch(x, y, (float *)tmp, frq, phs, n, F, h->stream));
-        if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host && NS == 1; }
+        if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host && NS == 1; }      // (NS > 1 is three kernels: no waiting workgroup, nothing to look at later)
         return 0;
     };
     if (!host) return launch(X_N1, FRQ, PHS, Y_N2);

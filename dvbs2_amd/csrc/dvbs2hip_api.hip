@@ -147,7 +147,7 @@ static int create_init(dvbs2hip_t *h, const dvbs2hip_cfg *cfg)
         h->hist_stride = (hb + 255) / 256 * 256;
         DEV_ALLOC_CHK(h, &h->d_hist_all, 4 * h->hist_stride);
         HIPCHK(h, hipMemset(h->d_hist_all, 0, 4 * h->hist_stride));
-        for (int i = 0; i < 2; i++) { h->d_hist[i] = (float *)((char *)h->d_hist_all + (size_t)(2 * i) * h->hist_stride); h->d_uphist[i] = (float *)((char *)h->d_hist_all + (size_t)(2 * i + 1) * h->hist_stride); }
+        for (int i = 0; i < 2; i++) { h->d_hist.p[i] = (float *)((char *)h->d_hist_all + (size_t)(2 * i) * h->hist_stride); h->d_uphist.p[i] = (float *)((char *)h->d_hist_all + (size_t)(2 * i + 1) * h->hist_stride); }
         if ((r = upload(h, &h->d_taps, cfg->fir_taps, (size_t)h->fir_T))) return r;
         if (h->fir_osf == 2) {
             const std::vector<uint16_t> af2 = upfir_mfma_afrag(cfg->fir_taps, h->fir_T);

@@ -19,6 +19,17 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// state a task carries from call to call, in two device buffers: a call reads in(), writes out(), and flip()s once its launch is queued.  The buffers belong to the
+// handle as before (dev_alloc / dev_free on p[i], or a part of a larger allocation); a reset makes buffer 0 the current one (cur = 0)
+template <typename T>
+struct PingPong {
+    T *p[2] = {nullptr, nullptr};
+    int cur = 0;
+    T *in() const { return p[cur]; }
+    T *out() const { return p[cur ^ 1]; }
+    void flip() { cur ^= 1; }
+};
+
 }  // namespace dvbs2
 
 struct dvbs2hip_handle {
@@ -44,13 +55,11 @@ struct dvbs2hip_handle {
     uint8_t *d_pl_seq = nullptr;
     float *d_taps_rev = nullptr;
     uint16_t *d_fir_afrag = nullptr, *d_upfir_afrag = nullptr;       // Toeplitz fragments of the split taps for the matrix-core FIR (T <= 81)
-    float *d_hist[2] = {nullptr, nullptr};
-    void *d_hist_all = nullptr;      // one allocation behind d_hist[] and d_uphist[]
+    dvbs2::PingPong<float> d_hist;   // the matched filter's memory at bw.S == 1 (dvbs2::bw_hist)
+    void *d_hist_all = nullptr;      // one allocation behind d_hist and d_uphist
     size_t hist_stride = 0;
-    int hist_cur = 0;
     float *d_taps = nullptr;            // natural order (shaping filter)
-    float *d_uphist[2] = {nullptr, nullptr};
-    int uphist_cur = 0;
+    dvbs2::PingPong<float> d_uphist;
     unsigned long long *d_ctr = nullptr;
     float *d_gwork = nullptr;
     // TX mirror (N1)
@@ -69,16 +78,15 @@ struct dvbs2hip_handle {
         float alpha = 0.9f, trigger = 30.f;    // factory defaults, Factory/Module/Synchronizer_frame/Synchronizer_frame.hpp:26-27
         int vec_width = 8;                     // mipp::N<float>() of the reference build (AVX2)
         int nbuff2 = 0;
-        float *xh[2] = {nullptr, nullptr};     // last 64 input samples (the correlators' memories + reg_channel)
-        float *sofh[2] = {nullptr, nullptr};   // last 64 cor_SOF samples (SOF_PLSC_delay)
+        dvbs2::PingPong<float> xh;             // last 64 input samples (the correlators' memories + reg_channel)
+        dvbs2::PingPong<float> sofh;           // last 64 cor_SOF samples (SOF_PLSC_delay)
         float *cv = nullptr;                   // corr_vec
-        float *buff2[2] = {nullptr, nullptr};  // output_delay.buff2
-        int *st[2] = {nullptr, nullptr};       // output_delay {head2, first_time}
-        float *yprev[2] = {nullptr, nullptr};  // the last output frame of the previous call
+        dvbs2::PingPong<float> buff2;          // output_delay.buff2 ...
+        dvbs2::PingPong<int> st;               // ... and its {head2, first_time}: the two flip together
+        dvbs2::PingPong<float> yprev;          // the last output frame of the previous call
         unsigned long long *keys = nullptr;    // arg max keys, max_frames x ceil(pl_frame / 64)
         float *metric = nullptr;               // max_corr of the last frame
         uint16_t *frag = nullptr;              // band fragments of the two correlators for the matrix cores (k_sync_mfma.hip)
-        int xh_cur = 0, sofh_cur = 0, od_cur = 0, yp_cur = 0;
         int n_alloc = 0;                       // streams the state above holds, side by side (dvbs2hip_set_streams; 1 without it)
     } sfm;
     // L&R fine frequency synchronizer (N4): damped autocorrelation R_l, alpha (factory default 0.999)
@@ -122,10 +130,8 @@ struct dvbs2hip_handle {
         int pll_sps = 1;                                        // Synchronizer_freq_coarse_DVBS2_aib.cpp:23 and Factory/Module/Synchronizer_freq_coarse/Synchronizer_freq_coarse.hpp:26-27
         float damping = 0.70710678f, nbw = 1e-4f;
         int n_alloc = 0;
-        dvbs2::SfcState *cf[2] = {nullptr, nullptr};
-        int cf_cur = 0;
-        float *hist[2] = {nullptr, nullptr};                    // S > 1: the matched filter's memory per stream (S = 1 shares the block-wise filter's, d_hist)
-        int hist_cur = 0;
+        dvbs2::PingPong<dvbs2::SfcState> cf;
+        dvbs2::PingPong<float> hist;                            // the matched filter's memory per stream while stm.S != bw.S (otherwise the loop runs on the block-wise filter's, dvbs2::bw_hist)
         bool hist_stale = false;                                // the streams started over: their matched-filter memories have to be cleared before the next loop call
         float *pil = nullptr;                                   // scrambled_pilots, n_p complex entries
         int n_p = 0;
@@ -139,11 +145,9 @@ struct dvbs2hip_handle {
         bool act = false;                                       // Synchronizer_timing::set_act: ULTRA holds only while it is set
         int Fs = 0;                                             // frames per stream of every call since the last reset (0: not yet fixed)
         int n_alloc = 0;                                        // streams the buffers below hold
-        dvbs2::StmState *st[2] = {nullptr, nullptr};
-        int st_cur = 0;
-        float *carry[2] = {nullptr, nullptr};                   // n_alloc x cap reals
-        int32_t *ccnt[2] = {nullptr, nullptr};                  // reals held per stream
-        int c_cur = 0;
+        dvbs2::PingPong<dvbs2::StmState> st;
+        dvbs2::PingPong<float> carry;                           // n_alloc x cap reals ...
+        dvbs2::PingPong<int32_t> ccnt;                          // ... and the reals held per stream: the two flip together
         long long cap = 0;                                      // reals per stream
         int32_t *uf = nullptr;                                  // underflow counts per frame slot, max_frames
     } stm;
@@ -152,18 +156,17 @@ struct dvbs2hip_handle {
         float D = 2.f;
         float b[3] = {0.f, 1.f, 0.f};
         long long H = 3;
-        float *hist[2] = {nullptr, nullptr};
-        int cur = 0;
+        dvbs2::PingPong<float> hist;
         float fs_omega = 0.f;                                   // the frequency shift: Multiplier_sine_ccc_naive's omega and sample counter
         uint32_t fs_n = 0;
     } chn;
     // dvbs2hip_set_streams: streams per call in the block-wise tasks that keep a memory (matched filter, frame synchronizer, L&R); the timing tasks' count is stm.S, and
     // dvbs2hip_sync_timing_set_streams sets that one alone.  S > 1: the matched filter's memory per stream, (fir_T - 1) complex samples each, side by side in a ping-pong pair
-    // of its own (S = 1 stays on d_hist); the coarse-frequency loop runs on it too when stm.S == S (api_acquire.hip)
+    // of its own (S = 1 stays on d_hist); dvbs2::bw_hist returns the pair of the current count, and the coarse-frequency loop runs on it too when stm.S == S (api_acquire.hip)
     struct {
         int S = 1;
-        float *hist[2] = {nullptr, nullptr};
-        int hist_n = 0, hist_cur = 0;                           // streams hist[] holds
+        dvbs2::PingPong<float> hist;
+        int hist_n = 0;                                         // streams hist holds
     } bw;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[DVBS2HIP_K_COUNT];
@@ -396,7 +399,7 @@ int host_wrap(dvbs2hip_t *h, const Tin *in, size_t nin_el, Tout *out, size_t nou
 
 // ---- defined in one translation unit, used from another
 int lr_check_all(dvbs2hip_t *h);                                                   // api_sync.hip
-int bw_hist_ready(dvbs2hip_t *h);                                                  // api_filter.hip: bw.hist for bw.S streams (allocated and cleared on first use)
+int bw_hist(dvbs2hip_t *h, PingPong<float> **hist);                                // api_filter.hip: the block-wise matched filter's memory for bw.S streams -- d_hist at S = 1, bw.hist (allocated and cleared on first use) at S > 1
 // api_tables.hip: what dvbs2hip_create uploads (pl_sequence: the coarse loop's pilots too)
 struct TxEncTable { std::vector<uint32_t> tab; std::vector<int32_t> deg; int stride = 0; };
 struct LdpcSynTables { std::vector<uint32_t> pos, prbs_s; int words = 0, rows = 0; };

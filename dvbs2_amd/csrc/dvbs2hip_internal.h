@@ -274,15 +274,12 @@ hipError_t tx_pl_scramble_launch(const float *X, float *Y, const uint8_t *seq, i
 std::vector<uint8_t> bch_generator(const BchPlan &pl);
 
 // ---------------------------------------------------------------- FIR (a5)
-hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag,
-                      int T, long long n_total, hipStream_t s);
+// S >= 1 streams of n_per samples per call (dvbs2hip_set_streams), stream s at x + 2 s n_per; the memories of T - 1 samples side by side in hist_in / hist_out
+hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
 // matrix-core form (k_fir_mfma.hip): bf16 x 3 split operands, fp32 accumulation
 std::vector<uint16_t> fir_mfma_afrag(const float *taps_rev, int T);
-bool fir_mfma_usable(const float *x, const float *y, int T, long long n_total);
-hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_total, hipStream_t s);
-// S streams of n_per samples per call (dvbs2hip_set_streams), stream s at x + 2 s n_per; the memories of T - 1 samples side by side in hist_in / hist_out
-hipError_t fir_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
-hipError_t fir_mfma_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
+bool fir_mfma_usable(const float *x, const float *y, int T, long long n_per, int S);
+hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
 
 hipError_t upfir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps, const uint16_t *afrag2, int T, int osf,
                         long long n_in, hipStream_t s);
@@ -301,35 +298,27 @@ struct SyncTail {
     float *seg;                      // 2 x ceil(max_frames / SYNC_SUB) x n floats of device scratch: per sub-segment of the call's frames {alpha^len, its own average from 0} (k_sync.hip)
 };
 constexpr int SYNC_MAX_SEG = 8, SYNC_SUB = 64;
-hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_total, hipStream_t s);
+// S >= 1 streams per call (dvbs2hip_set_streams): Fs = F / S frames per stream, n_per = n Fs samples; xh / sofh (64 complex), cv (n), yprev (2 n), buff2 (nbuff2), st
+// (SYNC_ST_STRIDE ints) and last_metric (1) hold the streams side by side, SyncTail's per-frame arrays and keys are stream-major like the sockets
+constexpr int SYNC_ST_STRIDE = 4;
+hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
 std::vector<uint16_t> sync_mfma_frag(const float *sof25, const float *plsc64);       // k_sync_mfma.hip: band fragments of the two correlators
-bool sync_mfma_usable(const float *x, const void *frag);
-hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_total, hipStream_t s);
-hipError_t sync_corr_m_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                   long long n_total, hipStream_t s);
+bool sync_mfma_usable(const float *x, const void *frag, long long n_per, int S);
+// corr != null: the one-task form (sofh_in / sofh_out its memories), else both correlations go to their sockets
+hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
+                                 float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
 std::vector<uint16_t> sync_frag_default();                                            // k_sync.hip: the fragments of conj_SOF / conj_PLSC
 hipError_t sync_corr_metric_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                   const SyncTail &t, int n, int F, float alpha, int vec_width, hipStream_t s);
+                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
 hipError_t sync_metric_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                              const SyncTail &t, int n, int F, float alpha, int vec_width, hipStream_t s);
-// S > 1 streams per call (dvbs2hip_set_streams): Fs = F / S frames per stream; xh / sofh (64 complex), cv (n), yprev (2 n), buff2 (nbuff2), st (SYNC_ST_STRIDE ints) and
-// last_metric (1) hold the streams side by side, SyncTail's per-frame arrays and keys are stream-major like the sockets
-constexpr int SYNC_ST_STRIDE = 4;
-hipError_t sync_corr_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
-hipError_t sync_corr_mfma_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                         float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
-hipError_t sync_corr_metric_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                           const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
-hipError_t sync_metric_streams_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                                      const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
-hipError_t sync_vdelay_streams_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                                      const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s);
-hipError_t sff_lr_streams_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s);
-hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, float alpha, uint32_t *err_dev, hipStream_t s);
+                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
+// list / src: the located form (S == 1 only)
+hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
+                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s, int32_t *list = nullptr, const float **src = nullptr);
+// S == 1: recurrence and rotation in one launch, err_dev its error word; S > 1: three kernels, err_dev unused
+hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, hipStream_t s);
 hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hipStream_t s);
 hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, hipStream_t s);
-hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                              const int32_t *Dtab, int n, int nbuff2, int F, hipStream_t s, int32_t *list = nullptr, const float **src = nullptr);
 
 // ---------------------------------------------------------------- symbol-timing recovery and the channel's delay tasks (k_timing.hip)
 // one stream's state of Synchronizer_Gardner_fast_osf2 between calls (all zeros = _reset): the Farrow history x[n-1], x[n-2], x[n-3], the TED buffer {T0, T1}, mu (the Farrow

@@ -107,52 +107,29 @@ __global__ void fir_hist_streams_kernel(const float2 *x, const float2 *hist_in, 
     hist_out[s * H + i] = gi >= 0 ? x[s * (size_t)n_per + gi] : hist_in[s * H + H + gi];
 }
 
-// afrag != nullptr: the matrix-core form (k_fir_mfma.hip) when it applies (T <= 81, 16-byte aligned sockets);
+// S >= 1 streams of n_per samples each (dvbs2hip_set_streams), stream s at x + 2 s n_per, the memories of T - 1 samples side by side in hist_in / hist_out.  S == 1 is the
+// one-stream kernels on a one-dimensional grid, S > 1 their stream instantiations with one grid row per stream.
+// afrag != nullptr: the matrix-core form (k_fir_mfma.hip) when it applies (fir_mfma_usable), chosen once for the call;
 // dvbs2hip_set_filter_kernel(h, DVBS2HIP_FIR_VALU) (afrag == nullptr here) or DVBS2HIP_FIR=valu keep the vector kernel
 hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag,
-                      int T, long long n_total, hipStream_t s)
-{
-    if (T < 1 || T > FIR_TMAX) return hipErrorInvalidValue;
-    const int H = T - 1;
-    static const bool force_valu = [] { const char *e = getenv("DVBS2HIP_FIR"); return e && e[0] == 'v'; }();
-    if (afrag && !force_valu && fir_mfma_usable(x, y, T, n_total))
-        return fir_mfma_launch(x, y, hist_in, hist_out, afrag, T, n_total, s);
-    const size_t lds = sizeof(float2) * (size_t)(fir_pad(FIR_TILE + H) + 1);
-    const unsigned grid = (unsigned)((n_total + FIR_TILE - 1) / FIR_TILE);
-    const float2 *x2 = reinterpret_cast<const float2 *>(x);
-    float2 *y2 = reinterpret_cast<float2 *>(y);
-    const float2 *h2 = reinterpret_cast<const float2 *>(hist_in);
-    if (T == 81) hipLaunchKernelGGL(fir_ccr_kernel<81>, dim3(grid), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_total);
-    else         hipLaunchKernelGGL(fir_ccr_kernel<0>, dim3(grid), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (H > 0)
-        hipLaunchKernelGGL(fir_hist_kernel, dim3((H + 63) / 64), dim3(64), 0, s, x2, h2,
-                           reinterpret_cast<float2 *>(hist_out), H, n_total);
-    return hipGetLastError();
-}
-
-// S streams of n_per samples each, memories of T - 1 samples per stream side by side; the kernel family is chosen once for the call, from the sockets and the per-stream
-// length (the matrix-core form loads 16 bytes at a time: every stream has to start on such a boundary)
-hipError_t fir_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag,
-                              int T, long long n_per, int S, hipStream_t s)
+                      int T, long long n_per, int S, hipStream_t s)
 {
     if (T < 1 || T > FIR_TMAX || S < 1 || S > 65535 || n_per < 1) return hipErrorInvalidValue;
     const int H = T - 1;
     static const bool force_valu = [] { const char *e = getenv("DVBS2HIP_FIR"); return e && e[0] == 'v'; }();
-    if (afrag && !force_valu && fir_mfma_usable(x, y, T, n_per) && n_per % 2 == 0)
-        return fir_mfma_streams_launch(x, y, hist_in, hist_out, afrag, T, n_per, S, s);
+    if (afrag && !force_valu && fir_mfma_usable(x, y, T, n_per, S))
+        return fir_mfma_launch(x, y, hist_in, hist_out, afrag, T, n_per, S, s);
     const size_t lds = sizeof(float2) * (size_t)(fir_pad(FIR_TILE + H) + 1);
     const unsigned grid = (unsigned)((n_per + FIR_TILE - 1) / FIR_TILE);
     const float2 *x2 = reinterpret_cast<const float2 *>(x);
     float2 *y2 = reinterpret_cast<float2 *>(y);
     const float2 *h2 = reinterpret_cast<const float2 *>(hist_in);
-    if (T == 81) hipLaunchKernelGGL((fir_ccr_kernel<81, true>), dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
-    else         hipLaunchKernelGGL((fir_ccr_kernel<0, true>), dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
+    const auto fir = T == 81 ? (S > 1 ? fir_ccr_kernel<81, true> : fir_ccr_kernel<81>) : (S > 1 ? fir_ccr_kernel<0, true> : fir_ccr_kernel<0>);
+    hipLaunchKernelGGL(fir, dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (H > 0)
-        hipLaunchKernelGGL(fir_hist_streams_kernel, dim3((H + 63) / 64, S), dim3(64), 0, s, x2, h2, reinterpret_cast<float2 *>(hist_out), H, n_per);
+        hipLaunchKernelGGL(S > 1 ? fir_hist_streams_kernel : fir_hist_kernel, dim3((H + 63) / 64, S), dim3(64), 0, s, x2, h2, reinterpret_cast<float2 *>(hist_out), H, n_per);
     return hipGetLastError();
 }
 

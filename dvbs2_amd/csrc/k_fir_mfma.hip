@@ -244,37 +244,27 @@ std::vector<uint16_t> fir_mfma_afrag(const float *taps_rev, int T)
     return out;
 }
 
-bool fir_mfma_usable(const float *x, const float *y, int T, long long n_total)
+// the kernel loads 16 bytes at a time: the sockets have to be so aligned, and with S > 1 streams every stream has to start on such a boundary (n_per even)
+bool fir_mfma_usable(const float *x, const float *y, int T, long long n_per, int S)
 {
-    return T >= 1 && T <= FM_H + 1 && n_total >= 2 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    return T >= 1 && T <= FM_H + 1 && n_per >= 2 && (S == 1 || n_per % 2 == 0) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 }
 
-// also leaves the next call's filter memory in hist_out (T - 1 samples)
-hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_total, hipStream_t s)
+// S streams of n_per samples (fir_launch); the tiles of a stream are dealt to its workgroups as in a one-stream call of n_per samples.  Also leaves the next call's filter
+// memory in hist_out (T - 1 samples per stream)
+hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s)
 {
-    const long long n_tiles = (n_total + FM_TILE - 1) / FM_TILE;
+    const long long n_tiles = (n_per + FM_TILE - 1) / FM_TILE;
     // Chunks of 4 tiles, handed to the CUs by the hardware dispatcher as workgroups retire: resident workgroups do not run at
     // the same speed (the arbiter favours the older waves), and one persistent workgroup per slot with an equal share of the
     // stream waited for the slowest -- same-box sweep at 68 M samples: 1024 workgroups (33 tiles each) 0.222 ms, 8192 (5 tiles)
-    // 0.207 ms, 16384 0.211 ms.  Short streams still get one workgroup per tile.  DVBS2HIP_FIR_WGS caps the grid instead.
+    // 0.207 ms, 16384 0.211 ms.  Short streams still get one workgroup per tile.  DVBS2HIP_FIR_WGS caps the grid (per stream) instead.
     static const int max_wg = [] { const char *e = getenv("DVBS2HIP_FIR_WGS"); return e ? atoi(e) : 0; }();
     const int tiles_per_wg = max_wg > 0 ? (int)((n_tiles + max_wg - 1) / max_wg) : (n_tiles >= 4096 ? 4 : (int)((n_tiles + 1023) / 1024));
     const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
-    hipLaunchKernelGGL(fir_mfma_kernel<1>, dim3(grid), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
-                       reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T, n_total,
-                       tiles_per_wg);
-    return hipGetLastError();
-}
-
-// the tiles of a stream are dealt to its workgroups as in a one-stream call of n_per samples
-hipError_t fir_mfma_streams_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s)
-{
-    const long long n_tiles = (n_per + FM_TILE - 1) / FM_TILE;
-    const int tiles_per_wg = n_tiles >= 4096 ? 4 : (int)((n_tiles + 1023) / 1024);
-    const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
-    hipLaunchKernelGGL(fir_mfma_kernel<1 + FM_STREAMS>, dim3(grid, S), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
-                       reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T, n_per,
-                       tiles_per_wg);
+    hipLaunchKernelGGL(S > 1 ? fir_mfma_kernel<1 + FM_STREAMS> : fir_mfma_kernel<1>, dim3(grid, S), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
+                       reinterpret_cast<float2 *>(y), reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T,
+                       n_per, tiles_per_wg);
     return hipGetLastError();
 }
 

@@ -974,7 +974,7 @@ static void sff_rotate_launch(const float *X, float *Y, const float2 *fr, int n,
                            reinterpret_cast<float2 *>(Y), fr, n, tot);
 }
 
-static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, float alpha, hipStream_t s);
+static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s);
 // the waiting workgroups' limit in ticks of s_memrealtime (100 MHz): one second; DVBS2HIP_LR_TIMEOUT_US overrides it (tests: 0 makes every waiting workgroup give up at
 // its first unsuccessful poll, which exercises the error word and the recovery)
 static unsigned long long sff_lr_timeout_ticks()
@@ -1113,11 +1113,14 @@ hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hi
     return hipGetLastError();
 }
 
-hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, float alpha, uint32_t *err_dev, hipStream_t s)
+// S == 1: the one launch above with its error word, or the three kernels (DVBS2HIP_LR=unfused, an odd frame length, unaligned sockets).  S > 1 streams per call
+// (dvbs2hip_set_streams): always the three kernels (the one-launch form's waiting workgroups rely on workgroup 0 being placed first: one assumption per launch, not
+// multiplied by the streams), err_dev is not used
+hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, hipStream_t s)
 {
     const char *ev = getenv("DVBS2HIP_LR");                    // read at every call
     const bool unfused = ev && !strcmp(ev, "unfused");
-    if (!unfused && n % 2 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
+    if (S == 1 && !unfused && n % 2 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
         float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
         const int cpf = (n / 2 + SFF_RCH - 1) / SFF_RCH;
         hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, fr, n);
@@ -1125,26 +1128,15 @@ hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F
                            F, alpha, n, cpf, err_dev, sff_lr_timeout_ticks());
         return hipGetLastError();
     }
-    return sff_lr_launch_unfused(X, Y, R_l, tmp, FRQ, PHS, n, F, alpha, s);
+    return sff_lr_launch_unfused(X, Y, R_l, tmp, FRQ, PHS, n, F, S, alpha, s);
 }
 
-static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, float alpha, hipStream_t s)
+// the pilots per frame, the recurrence as one workgroup per stream, the rotation per frame
+static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s)
 {
     float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
     hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, (float2 *)nullptr, n);
-    hipLaunchKernelGGL(sff_lr_iir_kernel<false>, dim3(1), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F, alpha);
-    const long long tot = (long long)n * F;
-    sff_rotate_launch<0>(X, Y, fr, n, tot, s);
-    return hipGetLastError();
-}
-
-// S > 1 streams per call: always the three kernels (the one-launch form's waiting workgroups rely on workgroup 0 being placed first: one assumption per launch, not
-// multiplied by the streams) -- the pilots per frame, the recurrence as one workgroup per stream, the rotation per frame
-hipError_t sff_lr_streams_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s)
-{
-    float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
-    hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, (float2 *)nullptr, n);
-    hipLaunchKernelGGL(sff_lr_iir_kernel<true>, dim3(S), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F / S, alpha);
+    hipLaunchKernelGGL(S > 1 ? sff_lr_iir_kernel<true> : sff_lr_iir_kernel<false>, dim3(S), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F / S, alpha);
     sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, s);
     return hipGetLastError();
 }
@@ -1160,34 +1152,41 @@ hipError_t sff_fp_launch(const float *X, float *Y, float *tmp /* 2 F floats */, 
 
 std::vector<uint16_t> sync_frag_default() { return sync_mfma_frag(K_CONJ_SOF, K_CONJ_PLSC); }
 
-hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_total, hipStream_t s)
+// ---- S >= 1 streams per call (dvbs2hip_set_streams): stream s = frames [s Fs, (s + 1) Fs) of every socket, n_per = n Fs samples; all state is laid out stream after stream.
+// S == 1 launches the one-stream kernels, S > 1 their stream forms with the stream in the grid's last dimension
+hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
 {
     // frag: the correlators on the matrix cores (k_sync_mfma.hip, which also leaves the next call's memory in xh_out); null = the fp32 vector kernel
-    if (sync_mfma_usable(x, frag)) return sync_corr_mfma_launch(x, xh_in, xh_out, frag, cor_sof, cor_plsc, n_total, s);
-    const unsigned grid = (unsigned)((n_total + SY_T - 1) / SY_T);
-    hipLaunchKernelGGL(sync_corr_kernel<false>, dim3(grid), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                       reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_total);
-    hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                       reinterpret_cast<float2 *>(xh_out), SY_H, n_total);
+    if (sync_mfma_usable(x, frag, n_per, S)) return sync_corr_mfma_launch(x, xh_in, xh_out, frag, nullptr, nullptr, nullptr, cor_sof, cor_plsc, n_per, S, s);
+    hipLaunchKernelGGL(S > 1 ? sync_corr_kernel<true> : sync_corr_kernel<false>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s,
+                       reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
+    hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                       reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
     return hipGetLastError();
 }
 
 // the average over frames with the arg max of every frame, then the per-frame sockets / delay-line table
-static void sync_average_argmax(float *cv, float *corr, int n, int F, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
+static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
 {
     const int end_vec = (n / vec_width) * vec_width, nwg = (n + 63) / 64;
+    if (S > 1) {      // the streams supply the parallelism: the plain walk, one wave per (stream, 64 positions)
+        hipLaunchKernelGGL(sync_average_argmax_streams_kernel, dim3(nwg, S), dim3(64), 0, s, cv, (const float *)corr, t.keys, n, Fs, alpha, end_vec);
+        hipLaunchKernelGGL(sync_finalize_kernel<true>, dim3(Fs, S), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, Fs);
+        return;
+    }
+    const int F = Fs;
     // few positions (short frames): the thirteen-wave form, one workgroup per CU at most; long frames: round 3's four-wave form (the stage is bound by its 4 bytes per
     // sample there: QPSK-N 1024 frames 42-45 us in the four-wave form, 65 us in this one)
     static const bool four = getenv("DVBS2HIP_SYNC_ARGMAX4") != nullptr;      // development: round 3's kernel for every frame length
     if (SYNC_ARGMAX10 && !four && nwg <= SYNC_UF96_MAX_WG) {
         // segments of the call's frames side by side while they fit the chip (one workgroup per CU) and stay long enough to be worth a seam (>= 768 frames each)
         static const int cap = getenv("DVBS2HIP_SYNC_SEGMENTS") ? atoi(getenv("DVBS2HIP_SYNC_SEGMENTS")) : SYNC_MAX_SEG;      // (development: 1 = the single walk)
-        int S = cap <= 1 || !t.seg ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);
+        int nseg = cap <= 1 || !t.seg ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);
         int seg_F = F;
-        if (S > 1) { seg_F = ((F + S - 1) / S + 191) / 192 * 192; S = (F + seg_F - 1) / seg_F; }      // (a multiple of the chunk's 96 frames and of SYNC_SUB)
-        if (S > 1) hipLaunchKernelGGL(sync_seg_partial_kernel, dim3(nwg, (S - 1) * (seg_F / SYNC_SUB)), dim3(64), 0, s, (const float *)corr, t.seg, n, F, alpha, end_vec);
-        else { S = 1; seg_F = F; }
-        hipLaunchKernelGGL(sync_metric_argmax_kernel<96>, dim3(nwg, S), dim3(64 * (SYM_NC + 12)), 0, s, cv, corr, t.keys, n, F, alpha, end_vec, (const float *)t.seg, seg_F);
+        if (nseg > 1) { seg_F = ((F + nseg - 1) / nseg + 191) / 192 * 192; nseg = (F + seg_F - 1) / seg_F; }      // (a multiple of the chunk's 96 frames and of SYNC_SUB)
+        if (nseg > 1) hipLaunchKernelGGL(sync_seg_partial_kernel, dim3(nwg, (nseg - 1) * (seg_F / SYNC_SUB)), dim3(64), 0, s, (const float *)corr, t.seg, n, F, alpha, end_vec);
+        else { nseg = 1; seg_F = F; }
+        hipLaunchKernelGGL(sync_metric_argmax_kernel<96>, dim3(nwg, nseg), dim3(64 * (SYM_NC + 12)), 0, s, cv, corr, t.keys, n, F, alpha, end_vec, (const float *)t.seg, seg_F);
     }
     else hipLaunchKernelGGL(sync_metric_argmax4_kernel, dim3(nwg), dim3(256), 0, s, cv, corr, t.keys, n, F, alpha, end_vec);
     hipLaunchKernelGGL(sync_finalize_kernel<false>, dim3(F), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, F);
@@ -1195,83 +1194,29 @@ static void sync_average_argmax(float *cv, float *corr, int n, int F, float alph
 
 // the one-task form: correlators + instantaneous metric fused (nothing but m leaves the chip), then the average / arg max as above
 hipError_t sync_corr_metric_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                   const SyncTail &t, int n, int F, float alpha, int vec_width, hipStream_t s)
+                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
 {
-    const long long tot = (long long)n * F;
-    if (sync_mfma_usable(x, frag)) (void)sync_corr_m_mfma_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, tot, s);
+    const long long n_per = (long long)n * Fs;
+    if (sync_mfma_usable(x, frag, n_per, S)) (void)sync_corr_mfma_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, nullptr, nullptr, n_per, S, s);
     else {
-        hipLaunchKernelGGL(sync_corr_m_kernel<false>, dim3((unsigned)((tot + SY_T - 1) / SY_T)), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
-                           reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, tot);
-        hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                           reinterpret_cast<float2 *>(xh_out), SY_H, tot);
+        hipLaunchKernelGGL(S > 1 ? sync_corr_m_kernel<true> : sync_corr_m_kernel<false>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s,
+                           reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, n_per);
+        hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                           reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
     }
-    sync_average_argmax(cv, corr, n, F, alpha, vec_width, t, s);
+    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, s);
     return hipGetLastError();
 }
 
 hipError_t sync_metric_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                              const SyncTail &t, int n, int F, float alpha, int vec_width, hipStream_t s)
-{
-    const long long tot = (long long)n * F;
-    hipLaunchKernelGGL(sync_m_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float2 *>(cor_sof),
-                       reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<const float2 *>(cor_plsc), corr, tot);
-    hipLaunchKernelGGL(sync_hist_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
-                       reinterpret_cast<float2 *>(sofh_out), 64, tot);
-    sync_average_argmax(cv, corr, n, F, alpha, vec_width, t, s);
-    return hipGetLastError();
-}
-
-// ---- S > 1 streams per call (dvbs2hip_set_streams): stream s = frames [s Fs, (s + 1) Fs) of every socket; all state is laid out stream after stream
-hipError_t sync_corr_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
-{
-    if (sync_mfma_usable(x, frag) && n_per % 2 == 0) return sync_corr_mfma_streams_launch(x, xh_in, xh_out, frag, nullptr, nullptr, nullptr, cor_sof, cor_plsc, n_per, S, s);
-    hipLaunchKernelGGL(sync_corr_kernel<true>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
-                       reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
-    hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                       reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
-    return hipGetLastError();
-}
-
-static void sync_average_argmax_streams(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
-{
-    const int end_vec = (n / vec_width) * vec_width, nwg = (n + 63) / 64;
-    hipLaunchKernelGGL(sync_average_argmax_streams_kernel, dim3(nwg, S), dim3(64), 0, s, cv, (const float *)corr, t.keys, n, Fs, alpha, end_vec);
-    hipLaunchKernelGGL(sync_finalize_kernel<true>, dim3(Fs, S), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, Fs);
-}
-
-hipError_t sync_corr_metric_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                           const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
+                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
 {
     const long long n_per = (long long)n * Fs;
-    if (sync_mfma_usable(x, frag) && n_per % 2 == 0) (void)sync_corr_mfma_streams_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, nullptr, nullptr, n_per, S, s);
-    else {
-        hipLaunchKernelGGL(sync_corr_m_kernel<true>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
-                           reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, n_per);
-        hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                           reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
-    }
-    sync_average_argmax_streams(cv, corr, n, Fs, S, alpha, vec_width, t, s);
-    return hipGetLastError();
-}
-
-hipError_t sync_metric_streams_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                                      const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
-{
-    const long long n_per = (long long)n * Fs;
-    hipLaunchKernelGGL(sync_m_streams_kernel, dim3((unsigned)((n_per + 255) / 256), S), dim3(256), 0, s, reinterpret_cast<const float2 *>(cor_sof),
+    hipLaunchKernelGGL(S > 1 ? sync_m_streams_kernel : sync_m_kernel, dim3((unsigned)((n_per + 255) / 256), S), dim3(256), 0, s, reinterpret_cast<const float2 *>(cor_sof),
                        reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<const float2 *>(cor_plsc), corr, n_per);
-    hipLaunchKernelGGL(sync_hist_streams_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
+    hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
                        reinterpret_cast<float2 *>(sofh_out), 64, n_per);
-    sync_average_argmax_streams(cv, corr, n, Fs, S, alpha, vec_width, t, s);
-    return hipGetLastError();
-}
-
-hipError_t sync_vdelay_streams_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                                      const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s)
-{
-    const int tot = ((nbuff2 > 2 * n ? nbuff2 : 2 * n) + 3) / 4;     // pairs of complex samples
-    const int gx = (tot + 256 * VD_SPL - 1) / (256 * VD_SPL);
-    hipLaunchKernelGGL(sync_vdelay_batch_kernel<true>, dim3(gx, Fs + 1, S), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, Fs, (const int32_t *)nullptr);
+    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, s);
     return hipGetLastError();
 }
 
@@ -1299,21 +1244,22 @@ __global__ void sync_locate_kernel(const float *X, float *scratch, const int32_t
     if (threadIdx.x == 0) { list[1 + cnt] = F; list[0] = cnt + 1; }
 }
 
-// all F frames of a call; Dtab (F ints) comes from sync_finalize_kernel; Yprev_new = the last output frame for the next call.  need / src != null: the located form
-// (Y = scratch for the frames that are materialized)
+// all Fs frames of each of the call's S streams; Dtab (Fs S ints) comes from sync_finalize_kernel; Yprev_new = the last output frame for the next call.  list / src != null:
+// the located form (Y = scratch for the frames that are materialized), one stream only
 hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                              const int32_t *Dtab, int n, int nbuff2, int F, hipStream_t s, int32_t *list, const float **src)
+                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s, int32_t *list, const float **src)
 {
+    if (list && S > 1) return hipErrorInvalidValue;
     const int tot = ((nbuff2 > 2 * n ? nbuff2 : 2 * n) + 3) / 4;     // pairs of complex samples
     const int gx = (tot + 256 * VD_SPL - 1) / (256 * VD_SPL);
+    int gy = Fs + 1;
     if (list) {
-        hipLaunchKernelGGL(sync_locate_kernel, dim3(1), dim3(1024), 0, s, X, Y, Dtab, n, nbuff2, F, list, src);
+        hipLaunchKernelGGL(sync_locate_kernel, dim3(1), dim3(1024), 0, s, X, Y, Dtab, n, nbuff2, Fs, list, src);
         // rows of the grid share the list's entries: in lock three of them have work (first frame, last frame, state row), while the synchronizer acquires all do
-        const int gy = F + 1 < 64 ? F + 1 : 64;
-        hipLaunchKernelGGL(sync_vdelay_batch_kernel<false>, dim3(gx, gy), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)list);
-        return hipGetLastError();
+        gy = Fs + 1 < 64 ? Fs + 1 : 64;
     }
-    hipLaunchKernelGGL(sync_vdelay_batch_kernel<false>, dim3(gx, F + 1), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new, st_old, st_new, Dtab, n, nbuff2, F, (const int32_t *)nullptr);
+    hipLaunchKernelGGL(S > 1 ? sync_vdelay_batch_kernel<true> : sync_vdelay_batch_kernel<false>, dim3(gx, gy, S), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new,
+                       st_old, st_new, Dtab, n, nbuff2, Fs, (const int32_t *)list);
     return hipGetLastError();
 }
 

@@ -225,41 +225,18 @@ std::vector<uint16_t> sync_mfma_frag(const float *sof25, const float *plsc64)
     return out;
 }
 
-bool sync_mfma_usable(const float *x, const void *frag) { return frag && (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
+// the kernel loads 16 bytes at a time: the socket has to be so aligned, and with S > 1 streams every stream has to start on such a boundary (n_per even)
+bool sync_mfma_usable(const float *x, const void *frag, long long n_per, int S) { return frag && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (S == 1 || n_per % 2 == 0); }
 
-// two-task form: both correlations to their sockets
-hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_total, hipStream_t s)
+// S streams of n_per samples.  corr != null is the one-task form (the instantaneous metric only; sofh_in / sofh_out its memories, cor_sof / cor_plsc null), else both
+// correlations go to their sockets (sofh_in / sofh_out null)
+hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
+                                 float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
 {
-    const unsigned grid = (unsigned)((n_total + SM_TILE - 1) / SM_TILE);
-    hipLaunchKernelGGL(sync_corr_mfma_kernel<false>, dim3(grid), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                       reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), nullptr, nullptr, nullptr, reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_total);
-    return hipGetLastError();
-}
-
-// one-task form: the instantaneous metric only
-hipError_t sync_corr_m_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                   long long n_total, hipStream_t s)
-{
-    const unsigned grid = (unsigned)((n_total + SM_TILE - 1) / SM_TILE);
-    hipLaunchKernelGGL(sync_corr_mfma_kernel<true>, dim3(grid), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                       reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, nullptr, nullptr,
-                       n_total);
-    return hipGetLastError();
-}
-
-// S streams: corr != null is the one-task form (sofh_in / sofh_out its memories), else both correlations go to their sockets
-hipError_t sync_corr_mfma_streams_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                         float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
-{
-    const dim3 grid((unsigned)((n_per + SM_TILE - 1) / SM_TILE), S);
-    if (corr)
-        hipLaunchKernelGGL(sync_corr_mfma_streams_kernel<true>, grid, dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                           reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr,
-                           (float2 *)nullptr, (float2 *)nullptr, n_per);
-    else
-        hipLaunchKernelGGL(sync_corr_mfma_streams_kernel<false>, grid, dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
-                           reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), (const float2 *)nullptr, (float2 *)nullptr, (float *)nullptr,
-                           reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
+    const auto k = corr ? (S > 1 ? sync_corr_mfma_streams_kernel<true> : sync_corr_mfma_kernel<true>) : (S > 1 ? sync_corr_mfma_streams_kernel<false> : sync_corr_mfma_kernel<false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)((n_per + SM_TILE - 1) / SM_TILE), S), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+                       reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr,
+                       reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
     return hipGetLastError();
 }
 

@@ -266,6 +266,35 @@ def test_rules_of_the_entry(O, Rx, P):
     rx.close()
 
 
+def test_stream_count_changed_on_a_live_handle_back_to_one_stream(O, Rx, monkeypatch):
+    """QPSK-S_8/9, one handle: set_streams(3) and two calls of 3 frames through filter, sync_frame_synchronize and L&R, then set_streams(1) and two calls of 2 frames.
+    The one-stream calls -- back on the one-stream filter memory and in the one-stream launch forms, the second call continuing from the state the first left -- are bit
+    for bit those of a fresh handle that never called the entry, sync_frame_metric included."""
+    for v in ("DVBS2HIP_SYNC", "DVBS2HIP_SYNC_UNFUSED", "DVBS2HIP_LR"):
+        monkeypatch.delenv(v, raising=False)
+    modcod = "QPSK-S_8/9"
+    _, pl, _, _ = make_pl_frames(O, modcod, 6, 9.0, seed=82)
+    n = pl.shape[1] // 2
+    stream = np.concatenate([np.zeros(2 * 55, np.float32), pl.reshape(-1)])[:6 * 2 * n].reshape(6, 2 * n)
+    desc = np.stack([_rot(O, pl[f], 2e-4, 0.05 * f) for f in range(6)])
+    rx, fresh = Rx(modcod, max_frames=3), Rx(modcod, max_frames=3)
+    rx.set_streams(3)
+    for f0 in (0, 3):
+        rx.filter(stream[f0:f0 + 3], 3); rx.sync_frame_synchronize(stream[f0:f0 + 3]); rx.sync_lr_synchronize(desc[f0:f0 + 3])
+    rx.set_streams(1)
+    for f0 in (1, 3):
+        outs = []
+        for h in (rx, fresh):
+            x, p = stream[f0:f0 + 2], desc[f0:f0 + 2]
+            outs.append([h.filter(x, 2), *h.sync_frame_synchronize(x, with_flags=True), *h.sync_lr_synchronize(p), *h.sync_frame_metric()])
+        assert len(outs[0]) == len(outs[1]) == 10
+        for k, (a, b) in enumerate(zip(*outs)):
+            assert _same(a, b), (f0, k)
+        assert np.abs(outs[0][0]).max() > 0.1 and np.abs(outs[0][4]).max() > 0.1          # (the filter's and the synchronizer's outputs are not empty)
+    assert rx.sync_lr_timeouts() == 0 and fresh.sync_lr_timeouts() == 0
+    rx.close(); fresh.close()
+
+
 # ------------------------------------------------------------------ the hand-over between the coarse-frequency loop and the block-wise filter
 def test_hand_over_from_step_mf_to_the_filter_per_stream(O):
     """S = 2 after dvbs2hip_set_streams: step_mf for 6 calls of one frame per stream, then sync_coarse_synchronize -> filter (the shape of

@@ -1,16 +1,18 @@
-"""Are the LDPC kernels of two builds the same device code?  Reads the gfx950 code objects out of two `lib` directories (dvbs2_amd/lib of two checkouts, each built by
-dvbs2_amd/build.py), disassembles every k_ldpc*.hip.o and compares each function's instruction text (mnemonic and operands; addresses and encodings left out) by symbol
-name -- a symbol may have moved to another translation unit.  No GPU.  It compares text only and looks for no particular instruction.
-usage: python tools/isa_same.py OLD_LIB_DIR NEW_LIB_DIR      -> one line per symbol: equal / DIFFERENT / only in ...; exit status 1 unless all are equal"""
+"""Are the kernels of two builds the same device code?  Reads the gfx950 code objects out of two `lib` directories (dvbs2_amd/lib of two checkouts, each built by
+dvbs2_amd/build.py), disassembles every object whose name matches OBJECTS (a glob without the .hip.o; default k_ldpc*, the LDPC kernels; 'k_*' is every kernel file) and
+compares each function's instruction text (mnemonic and operands; addresses and encodings left out) by symbol name -- a symbol may have moved to another translation
+unit.  No GPU.  It compares text only and looks for no particular instruction.
+usage: python tools/isa_same.py OLD_LIB_DIR NEW_LIB_DIR [OBJECTS]      -> one line per symbol: equal / DIFFERENT / only in ...; exit status 1 unless all are equal"""
 import glob, os, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_mix as KM
 
 
-def symbols(libdir):
+def symbols(libdir, objects):
     """demangled-as-is symbol -> (translation unit, [(mnemonic, operands)])"""
     out = {}
-    for o in sorted(glob.glob(os.path.join(libdir, "k_ldpc*.hip.o"))):
+    pattern = objects if objects.endswith(".hip.o") else objects + ".hip.o"
+    for o in sorted(glob.glob(os.path.join(libdir, pattern))):
         tu = os.path.basename(o)[:-len(".hip.o")]
         for name, insts in KM.functions(KM.disassemble_object(o)).items():
             out[name] = (tu, [(i[1], i[4].strip()) for i in insts])
@@ -18,7 +20,8 @@ def symbols(libdir):
 
 
 def main():
-    old, new = symbols(sys.argv[1]), symbols(sys.argv[2])
+    objects = sys.argv[3] if len(sys.argv) > 3 else "k_ldpc*"
+    old, new = symbols(sys.argv[1], objects), symbols(sys.argv[2], objects)
     bad = 0
     print("| symbol | instructions | old file | new file | device code |\n|---|---|---|---|---|")
     for name in sorted(set(old) | set(new)):
