@@ -19,14 +19,18 @@ from .rx_sequence import RxSequence
 
 
 def acquire(rx, receive, n_frames=1, osf=2, learn1=150, learn2=150, learn3=200, nbw_wait=1e-4, nbw1=1e-4, nbw2=5e-5, damping=0.5 ** 0.5, wait_max=2000, agc=True,
-            on_frames=None):
+            on_frames=None, smf_kernel=None):
     """rx: the handle; receive(): the next n_frames frames of pl_frame * osf complex samples (float32, interleaved), raising ProcessingAborted at the end of the source.
     on_frames(phase, n): called after every call of a phase with the frames it took (progress).
+    smf_kernel: "LANE" or "WAVE", the form of the coarse-frequency loop (rx.sync_step_mf_set_kernel: the same results, WAVE the faster with one stream); None leaves the
+    handle as it is and calls nothing.
     -> dict(acquired: the packet flag came within wait_max frames, and the source lasted through the learning phases; flag: the packet flag came;
             frames: {"waiting", "learning1", "learning2", "learning3"} frames spent; freq: estimated_freq per stream; nu: the floored frequency in use per stream)"""
     F = n_frames
     spent = dict(waiting=0, learning1=0, learning2=0, learning3=0)
     res = dict(acquired=False, flag=False, frames=spent, freq=None, nu=None)
+    if smf_kernel is not None:
+        rx.sync_step_mf_set_kernel(smf_kernel)
     fed_back = np.zeros(F, np.int32)                                  # Feedbacker: what memorize took at the last call, produce gives at this one (zeros at first)
 
     # the gain stages and the frame synchronizer of every phase, and learning phase 3, are the transmission phase's (rx_sequence.py)

@@ -438,8 +438,9 @@ int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, con
         if (started_over && T.S > 1) HIPCHK(h, hipMemsetAsync(hist->in(), 0, SMF_HIST_BYTES * (size_t)T.S, h->stream));      // (one stream carries on from dvbs2hip_filter* whatever the loop's state)
     }
     Timer tm(h, DVBS2HIP_K_MISC);
-    HIPCHK(h, stepmf_launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt.in(), T.st.in(), T.st.out(), C.cf.in(), C.cf.out(), hist->in(), hist->out(), h->d_taps_rev,
-                            C.pil, C.n_p, T.S, F / T.S, stm_frame_cplx(h), h->pl_frame, T.kp, T.ki, pg, ig, (float)h->fir_osf, h->stream));
+    const auto launch = C.smf_kernel == DVBS2HIP_SMF_WAVE ? stepmf_wave_launch : stepmf_launch;      // the same arguments, state and results
+    HIPCHK(h, launch(X_N1, Y_N1, B_N1, MU, FRQ, PHS, DEL, T.ccnt.in(), T.st.in(), T.st.out(), C.cf.in(), C.cf.out(), hist->in(), hist->out(), h->d_taps_rev,
+                     C.pil, C.n_p, T.S, F / T.S, stm_frame_cplx(h), h->pl_frame, T.kp, T.ki, pg, ig, (float)h->fir_osf, h->stream));
     T.st.flip();
     C.cf.flip();
     hist->flip();
@@ -455,6 +456,15 @@ int dvbs2hip_sync_step_mf_synchronize(dvbs2hip_t *h, const int32_t *DEL, const f
                      {{Y_N1, B_STM_Y, n4}, {B_N1, B_STM_B, n4}, {MU, B_STM_MU, nf4}, {FRQ, B_SMF_FRQ, nf4}, {PHS, B_SMF_FRQ, nf4, nf4}}, [&](void *const *i, void *const *o, int nf) {
         return dvbs2hip_sync_step_mf_synchronize_dev(h, (const int32_t *)i[1], (const float *)i[0], (float *)o[2], (float *)o[3], (float *)o[4], (float *)o[0], (int32_t *)o[1], nf);
     });
+}
+
+int dvbs2hip_sync_step_mf_set_kernel(dvbs2hip_t *h, int32_t kernel)
+{
+    int r0 = enter(h); if (r0) return r0;
+    if (kernel != DVBS2HIP_SMF_LANE && kernel != DVBS2HIP_SMF_WAVE)
+        return fail(h, DVBS2HIP_EINVAL, "'kernel' has to be DVBS2HIP_SMF_LANE or DVBS2HIP_SMF_WAVE ('kernel' = " + std::to_string(kernel) + ").");
+    h->sfc.smf_kernel = kernel;
+    return 0;
 }
 
 int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h)                         // Synchronizer_step_mf_cc::reset, .cpp:210-217: coarse, matched filter, timing

@@ -135,6 +135,7 @@ struct dvbs2hip_handle {
         bool hist_stale = false;                                // the streams started over: their matched-filter memories have to be cleared before the next loop call
         float *pil = nullptr;                                   // scrambled_pilots, n_p complex entries
         int n_p = 0;
+        int smf_kernel = DVBS2HIP_SMF_LANE;                     // dvbs2hip_sync_step_mf_set_kernel: the loop's form, read at launch; no reset touches it
     } sfc;
     // symbol-timing recovery (Synchronizer_Gardner_fast_osf2): per-stream state and carry buffers in ping-pong pairs, like the filters' memories
     struct {

@@ -351,5 +351,9 @@ struct SfcState {
 hipError_t stepmf_launch(const float *X, float *Y, int32_t *B, float *MU, float *FRQ, float *PHS, const int32_t *DEL, const int32_t *ccnt, const StmState *st_in, StmState *st_out,
                          const SfcState *cf_in, SfcState *cf_out, const float *hist_in, float *hist_out, const float *taps, const float *P, int n_p, int S, int Fs, int N, int pl_frame,
                          float kp, float ki, float pg, float ig, float sps, hipStream_t s);
+// the same loop and the same state, a wave per stream (k_stepmf_wave.hip): rotation and matched filter of 64 samples ahead of the serial steps
+hipError_t stepmf_wave_launch(const float *X, float *Y, int32_t *B, float *MU, float *FRQ, float *PHS, const int32_t *DEL, const int32_t *ccnt, const StmState *st_in,
+                              StmState *st_out, const SfcState *cf_in, SfcState *cf_out, const float *hist_in, float *hist_out, const float *taps, const float *P, int n_p, int S,
+                              int Fs, int N, int pl_frame, float kp, float ki, float pg, float ig, float sps, hipStream_t s);
 
 }  // namespace dvbs2

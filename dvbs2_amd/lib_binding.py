@@ -133,6 +133,7 @@ ABI = {
     "dvbs2hip_sync_step_mf_synchronize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_sync_step_mf_synchronize_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_sync_step_mf_reset": (C.c_int, [_vp]),
+    "dvbs2hip_sync_step_mf_set_kernel": (C.c_int, [_vp, _i]),
     "dvbs2hip_pl_descramble": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_pl_descramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_remove_plh": (C.c_int, [_vp, _vp, _vp, _i]),

@@ -344,6 +344,14 @@ class Dvbs2Hip:
     def sync_step_mf_reset(self):
         self._chk(self.L.dvbs2hip_sync_step_mf_reset(self.h))
 
+    SMF_KERNELS = {"LANE": 0, "WAVE": 1}                      # DVBS2HIP_SMF_LANE, DVBS2HIP_SMF_WAVE
+
+    def sync_step_mf_set_kernel(self, kernel="LANE"):
+        """the loop's form: "LANE" (one lane per stream, the default) or "WAVE" (one wave per stream, rotation and matched filter ahead of the serial steps); the same
+        results bit for bit, no state is cleared"""
+        code = self.SMF_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+        self._chk(self.L.dvbs2hip_sync_step_mf_set_kernel(self.h, code))
+
     def pl_descramble(self, Y_N1):
         X, F = self._frames(Y_N1, 2 * self.pl_frame, np.float32)
         out = np.empty_like(X)

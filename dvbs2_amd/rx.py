@@ -43,6 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
                                                              "needs --stm-type FAST, excludes --coarse-freq")
     ap.add_argument("--wl-frames", type=int, nargs=3, default=[150, 150, 200], metavar=("L1", "L2", "L3"), help="frames of learning phases 1, 2 and 3")
     ap.add_argument("--wl-wait-max", type=int, default=2000, help="frames after which the waiting phase gives up")
+    ap.add_argument("--smf-kernel", choices=["LANE", "WAVE"], default=None, help="with --wl-phases: the form of the coarse-frequency loop (LANE: one lane per stream, the library's "
+                                                                                 "default; WAVE: one wave per stream, the faster one here; the same results); default: not set")
     ap.add_argument("--snk-path", default="", help="decoded payload of every frame, eight bits per byte (the reference's Sink_user_binary: a file sent with dvbs2_tx --src-type USER_BIN comes out as it went in)")
     ap.add_argument("--timing-offset", type=int, default=-1, help="sample index of the first symbol after the matched filter (default: two group delays)")
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
@@ -74,6 +76,9 @@ def run(args, out=sys.stdout) -> dict:
     wl = getattr(args, "wl_phases", False)
     if wl and args.coarse_freq:
         raise ValueError("--wl-phases finds the carrier offset itself: it excludes --coarse-freq")
+    smf_kernel = getattr(args, "smf_kernel", None)
+    if smf_kernel is not None and not wl:
+        raise ValueError("--smf-kernel chooses the kernel of the coarse-frequency loop, which only --wl-phases runs: give both or neither")
     ultra = args.stm_type == "ULTRA"
     if wl and ultra:
         raise ValueError("--wl-phases steps FAST's detector inside the coarse-frequency loop: with --stm-type ULTRA it is not provided (use --stm-learn-frames)")
@@ -99,7 +104,8 @@ def run(args, out=sys.stdout) -> dict:
         if wl:
             from .acquire import acquire
             l1, l2, l3 = args.wl_frames
-            st["acquisition"] = acq = acquire(rx, rcv.receive, n_frames=F, osf=osf, learn1=l1, learn2=l2, learn3=l3, wait_max=args.wl_wait_max, agc=not args.no_agc)
+            st["acquisition"] = acq = acquire(rx, rcv.receive, n_frames=F, osf=osf, learn1=l1, learn2=l2, learn3=l3, wait_max=args.wl_wait_max, agc=not args.no_agc,
+                                              **({} if smf_kernel is None else dict(smf_kernel=smf_kernel)))
             print("# waiting %d | learning %d + %d + %d frames | packet flag %s | coarse frequency %s" % (
                 acq["frames"]["waiting"], acq["frames"]["learning1"], acq["frames"]["learning2"], acq["frames"]["learning3"], acq["flag"], acq["freq"]), file=out)
         while not args.max_frames or lock.frames < args.max_frames:

@@ -18,7 +18,8 @@
 //      behind it, as the reference's sequence does at processing_aborted, and the payload source only advances for batches that go through); the source is a file of the sent payloads delayed by --src-delay frames (the frame synchronizer's latency;
 //      what Filter_buffered_delay does in the TX_RX mains).
 //      --wl-phases (with --stm-type FAST) runs the reference's waiting and learning phases on the head of the file first (main_sched.cpp:407-635): Synchronizer_step_mf_hip,
-//      the coarse-frequency loop on the GPU, bound as main_sched.cpp:428-432 with a Feedbacker for DEL; --wl-frames L1 L2 L3 (150 150 200), --wl-wait-max (2000).
+//      the coarse-frequency loop on the GPU, bound as main_sched.cpp:428-432 with a Feedbacker for DEL; --wl-frames L1 L2 L3 (150 150 200), --wl-wait-max (2000);
+//      --smf-kernel LANE | WAVE chooses the loop's kernel (Synchronizer_step_mf_hip::set_kernel; not given: the library's default) and is refused without --wl-phases.
 //
 // With --src the monitor runs (check_errors in (1), check_errors2 with its BE / FE / BER / FER sockets read by probe stand-ins
 // in (2)) and FRA / BE / FE are printed like the reference's terminal.
@@ -135,7 +136,7 @@ public:
 static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite, float alpha, const std::string &implem, const std::string &in_path,
                                     const std::string &out_path, const std::string &src_path, int src_delay, int mon_skip, float coarse_freq, bool stm_fast,
                                     bool wl_phases = false, int wl1 = 150, int wl2 = 150, int wl3 = 200, int wl_wait_max = 2000, bool stm_ultra = false, int stm_hold_size = 101,
-                                    int stm_learn_frames = 500)
+                                    int stm_learn_frames = 500, int smf_kernel = -1)
 {
     using namespace module;
     const int osf = 2;
@@ -227,6 +228,7 @@ static int run_matched_filter_graph(const std::string &modcod, int F, int n_ite,
         // the waiting and learning phases of RX/main_sched.cpp:407-635 on the head of the file
         namespace fbr = spu::module::fbr;
         std::unique_ptr<Synchronizer_step_mf_hip<>> sync_step_mf(new Synchronizer_step_mf_hip<>(sync_coarse_f.get(), matched_flt.get(), sync_timing.get(), ctx));
+        if (smf_kernel >= 0) sync_step_mf->set_kernel(smf_kernel);                                                   // --smf-kernel
         std::unique_ptr<spu::module::Feedbacker<int>> feedbr(new spu::module::Feedbacker<int>(1, 0, F));
         // partial binding
         (*sync_step_mf)[             smf::sck::synchronize::X_N1] = (*front_agc   )[mlt::sck::imultiply   ::Z_N ];   // main_sched.cpp:428
@@ -312,7 +314,7 @@ int main(int argc, char **argv)
     float coarse_freq = 0.f;
     float alpha = 1.0f;
     bool frame_sync = false, matched = false, stm_fast = false, stm_ultra = false, wl_phases = false;
-    int wl[3] = {150, 150, 200}, wl_wait_max = 2000, stm_hold_size = 101, stm_learn_frames = -1;
+    int wl[3] = {150, 150, 200}, wl_wait_max = 2000, stm_hold_size = 101, stm_learn_frames = -1, smf_kernel = -1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; exit(2); } return argv[++i]; };
@@ -330,6 +332,11 @@ int main(int argc, char **argv)
         else if (a == "--wl-phases") wl_phases = true;                         // the waiting and learning phases on the head of the file (main_sched.cpp:407-635)
         else if (a == "--wl-frames") { for (int &w : wl) w = std::stoi(next()); }
         else if (a == "--wl-wait-max") wl_wait_max = std::stoi(next());
+        else if (a == "--smf-kernel") {
+            const std::string t = next();
+            if (t != "LANE" && t != "WAVE") { std::cerr << "--smf-kernel: LANE or WAVE\n"; return 2; }
+            smf_kernel = t == "WAVE" ? DVBS2HIP_SMF_WAVE : DVBS2HIP_SMF_LANE;
+        }
         else if (a == "--frame-sync") frame_sync = true;
         else if (a == "--matched-filter") matched = true;
         else if (a == "--stm-type") {
@@ -345,10 +352,11 @@ int main(int argc, char **argv)
         if (stm_fast && !matched) { std::cerr << "--stm-type FAST | ULTRA needs --matched-filter (the timing synchronizer runs on the samples)\n"; return 2; }
         if (stm_ultra && stm_hold_size <= 4) { std::cerr << "--stm-hold-size has to be greater than 4\n"; return 2; }
         if (stm_ultra && wl_phases) { std::cerr << "--wl-phases steps FAST's detector inside the coarse-frequency loop: with --stm-type ULTRA it is not provided (use --stm-learn-frames)\n"; return 2; }
+        if (smf_kernel >= 0 && !wl_phases) { std::cerr << "--smf-kernel chooses the kernel of the coarse-frequency loop, which only --wl-phases runs: give both or neither\n"; return 2; }
         if (stm_learn_frames < 0) stm_learn_frames = wl[0] + wl[1] + wl[2];
         if (wl_phases && (!stm_fast || coarse_freq != 0.f)) { std::cerr << "--wl-phases needs --matched-filter --stm-type FAST and excludes --coarse-freq\n"; return 2; }
         if (matched) return run_matched_filter_graph(modcod, F, n_ite, alpha, implem, in_path, out_path, src_path, src_delay, mon_skip, coarse_freq, stm_fast, wl_phases,
-                                                     wl[0], wl[1], wl[2], wl_wait_max, stm_ultra, stm_hold_size, stm_learn_frames);
+                                                     wl[0], wl[1], wl[2], wl_wait_max, stm_ultra, stm_hold_size, stm_learn_frames, smf_kernel);
         auto ctx = std::make_shared<module::Context>(modcod, F, n_ite, alpha, true, 0, implem);
         ctx->pin_sockets = true;            // the sockets below live until the modules go: pin them for overlapped PCIe copies
         module::Scrambler_PL_hip pl_scrambler(ctx);

@@ -395,7 +395,7 @@ private:
 };
 
 // replaces Synchronizer_step_mf_cc<B,R> (Synchronizer_step_mf_cc.cpp:13-71), the task of the waiting and learning phases 1-2 (RX/main_sched.cpp:428-432): the coarse
-// synchronizer's rotation and PLL, the matched filter's step and the timing synchronizer's step, fused per sample (k_stepmf.hip).  The reference builds it from its three
+// synchronizer's rotation and PLL, the matched filter's step and the timing synchronizer's step, fused per sample (k_stepmf.hip; set_kernel: k_stepmf_wave.hip).  The reference builds it from its three
 // modules and runs on their state; here that state lives in the handle, so the modules passed in only have to belong to the same Context.  One stream; sockets by the
 // reference's names.  reset() = Synchronizer_step_mf_cc::reset (coarse, matched filter, timing).
 template <typename B = int, typename R = float>
@@ -426,6 +426,8 @@ public:
     spu::runtime::Task &operator[](smf::tsk t) { return *tasks[(size_t)t]; }
     spu::runtime::Socket &operator[](smf::sck::synchronize s) { return (*tasks[0])[(size_t)s]; }
     void reset() { DVBS2HIP_CHK(ctx, dvbs2hip_sync_step_mf_reset(ctx->h)); }
+    // the loop's form, DVBS2HIP_SMF_LANE (the default) or DVBS2HIP_SMF_WAVE (one wave per stream): the same results, no state is cleared
+    void set_kernel(int kernel) { DVBS2HIP_CHK(ctx, dvbs2hip_sync_step_mf_set_kernel(ctx->h, kernel)); }
 };
 
 // replaces Framer<B>::remove_plh (Framer.hxx:330-343)

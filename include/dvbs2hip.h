@@ -514,6 +514,20 @@ int dvbs2hip_sync_coarse_get_freq(dvbs2hip_t *h, float *estimated_freq, float *n
 int dvbs2hip_sync_step_mf_synchronize(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t n_frames);
 int dvbs2hip_sync_step_mf_synchronize_dev(dvbs2hip_t *h, const int32_t *DEL, const float *X_N1, float *MU, float *FRQ, float *PHS, float *Y_N1, int32_t *B_N1, int32_t n_frames);
 int dvbs2hip_sync_step_mf_reset(dvbs2hip_t *h);
+/* The form of the coarse-frequency loop behind dvbs2hip_sync_step_mf_synchronize / _dev
+ * DVBS2HIP_SMF_LANE (the default): one lane per stream walks rotation, the 81 taps, the timing step and the PLL for every sample; 64 streams share a wave.  A handle that
+ * never calls this entry launches that kernel exactly as before the entry existed.
+ * DVBS2HIP_SMF_WAVE: one wave per stream.  nu changes only in the PLL update on a pilot strobe, so rotation and matched filter are a feed-forward of the input in between:
+ * the wave takes chunks of up to 64 samples, lane i rotates and filters sample i of the chunk with the nu in use, and only the timing step and the PLL then run sample by
+ * sample.  When the PLL update at sample i of a chunk changes nu, samples 0 .. i are final, the chunk is cut there and what lay behind is rotated and filtered again from
+ * the input with the new nu.  Every lane evaluates the lane form's expressions in the lane form's order: results and state are bit for bit the lane form's (and the CPU
+ * twin's, tests/stepmf_twin.c; tests/stepmf_wave_twin.c states the chunked order on the CPU).  Five times faster than LANE with one stream and faster up to a few thousand; with a
+ * full device of streams LANE, which shares a wave among 64 of them, has the higher throughput (results/coarse/README.md has both forms and where they cross).
+ * The choice is a host-side field read at launch: it clears no state, no reset or set_streams changes it, and a handle may change form between any two calls.  It is
+ * allowed inside an open capture; a recorded graph keeps the kernel it was recorded with, as with dvbs2hip_sync_timing_set_act.  Any other value: DVBS2HIP_EINVAL.
+ * Every condition of the loop holds for both forms: 81 symmetric taps, two samples per symbol, DVBS2HIP_EUNSUPPORTED while the timing type is DVBS2HIP_STM_ULTRA. */
+enum { DVBS2HIP_SMF_LANE = 0, DVBS2HIP_SMF_WAVE = 1 };
+int dvbs2hip_sync_step_mf_set_kernel(dvbs2hip_t *h, int32_t kernel);
 
 /* ------------------------------------------------------------------ N4: frame synchronizer
  * replaces: Synchronizer_frame_DVBS2_fast<R> (type "FAST", the factory default,

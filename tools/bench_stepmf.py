@@ -4,7 +4,8 @@ time of a full 150 / 150 / 200 acquisition at S = 1 through dvbs2_amd/acquire.py
 
 Every stream gets the same received signal (a shaped QPSK-S 8/9 stream with pilots, 0.05 cycles per sample off, delayed by 4.5, noisy, made once on the host and tiled on
 the device); the loop's work does not depend on the data.  Per S: one warm-up call, then `reps` timed calls, median.
-usage: python tools/bench_stepmf.py [--reps 5] [--streams 1,64,1024,4096,16384] [--out results/coarse/bench_stepmf.json]"""
+--kernel LANE | WAVE chooses the loop's form (dvbs2hip_sync_step_mf_set_kernel; k_stepmf_wave.hip is WAVE), for the timed calls and for the acquisition alike.
+usage: python tools/bench_stepmf.py [--reps 5] [--streams 1,64,1024,4096,16384] [--kernel LANE] [--out results/coarse/bench_stepmf.json]"""
 import argparse
 import ctypes as C
 import json
@@ -24,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--streams", default="1,64,1024,4096,16384")
+    ap.add_argument("--kernel", choices=["LANE", "WAVE"], default="LANE")
     ap.add_argument("--no-acquisition", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -52,6 +54,7 @@ def main():
         F = S * Fs
         rx = Dvbs2Hip("QPSK-S_8/9", max_frames=F)
         rx.sync_timing_set_streams(S)
+        rx.sync_step_mf_set_kernel(a.kernel)
         X = torch.from_numpy(base[:Fs]).to(dev).reshape(1, -1).repeat(S, 1).reshape(F, 2 * N).contiguous()
         Yd = torch.empty_like(X)
         Bd = torch.empty(X.shape, dtype=torch.int32, device=dev)
@@ -79,7 +82,7 @@ def main():
             ms.append(tot.value)
         med = float(np.median(ms))
         samples = F * N
-        row = dict(S=S, frames_per_stream=Fs, samples=samples, ms_median=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4),
+        row = dict(kernel=a.kernel, S=S, frames_per_stream=Fs, samples=samples, ms_median=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4),
                    Msamples_per_s=round(samples / med / 1e3, 2), ns_per_sample_per_stream=round(med * 1e6 / (Fs * N), 2))
         print(json.dumps(row), flush=True)
         rows.append(row)
@@ -98,15 +101,15 @@ def main():
         it = iter(stream)
         rx = Dvbs2Hip("QPSK-S_8/9", max_frames=1)
         t0 = time.perf_counter()
-        res = acquire(rx, lambda: next(it)[None, :], n_frames=1)
+        res = acquire(rx, lambda: next(it)[None, :], n_frames=1, smf_kernel=a.kernel)
         wall = time.perf_counter() - t0
         rx.close()
-        acq = dict(acquisition_wall_s=round(wall, 3), frames=res["frames"], flag=res["flag"], acquired=res["acquired"], freq=res["freq"],
+        acq = dict(kernel=a.kernel, acquisition_wall_s=round(wall, 3), frames=res["frames"], flag=res["flag"], acquired=res["acquired"], freq=res["freq"],
                    what="acquire() at S = 1, F = 1, 150 / 150 / 200, host-socket calls, PCIe copies and the Python loop included")
         print(json.dumps(acq), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(dict(rows=rows, summary=summ, acquisition=acq), open(a.out, "w"), indent=1)
+        json.dump(dict(kernel=a.kernel, rows=rows, summary=summ, acquisition=acq), open(a.out, "w"), indent=1)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,7 @@ are the first --skip frames, which are not counted.
 --chn-max-freq-shift f puts the channel's frequency shift (dvbs2hip_channel_freq_shift, f cycles per sample) behind the delay tasks, and --wl-phases runs the reference's
 waiting and learning phases (dvbs2_amd/acquire.py: the coarse-frequency loop on the GPU, 150 / 150 / 200 frames) on the head of the stream before anything is counted; the
 transmission phase then shifts by the frozen estimate (dvbs2hip_sync_coarse_synchronize) in front of the matched filter.  --wl-phases needs --stm-type FAST.
+--smf-kernel {LANE,WAVE} chooses the loop's kernel for --wl-phases (dvbs2hip_sync_step_mf_set_kernel).
 --stm-type ULTRA --stm-hold-size H is the held loop (dvbs2hip_sync_timing_set_type): the whole loop for --stm-learn-frames frames, then it holds."""
 import argparse, json, os, sys, time
 import numpy as np
@@ -44,6 +45,9 @@ def run_point(Rx, P, mc, ebn0, variant, a):
     wl = getattr(a, "wl_phases", False)
     if wl and stm_type != "FAST":
         raise ValueError("--wl-phases needs --stm-type FAST")
+    smf_kernel = getattr(a, "smf_kernel", None)
+    if smf_kernel is not None and not wl:
+        raise ValueError("--smf-kernel chooses the kernel of the coarse-frequency loop, which only --wl-phases runs: give both or neither")
     if stm_type == "ULTRA":
         rx.sync_timing_set_type("ULTRA", a.stm_hold_size)                              # the held loop: the whole loop for --stm-learn-frames frames, then set_act
     if delay_D is not None:
@@ -78,7 +82,7 @@ def run_point(Rx, P, mc, ebn0, variant, a):
 
     if wl:
         from dvbs2_amd.acquire import acquire
-        st["acquisition"] = acquire(rx, received, n_frames=F, agc=a.agc)
+        st["acquisition"] = acquire(rx, received, n_frames=F, agc=a.agc, **({} if smf_kernel is None else dict(smf_kernel=smf_kernel)))
         if not st["acquisition"]["acquired"]:
             raise RuntimeError("the waiting phase gave up: %r" % (st["acquisition"],))
     while st["fe"] < a.fe and st["counted"] < a.max_frames:
@@ -115,6 +119,8 @@ def build_parser():
     add_timing_args(ap, learn_default=LEARN_FRAMES)
     ap.add_argument("--chn-max-freq-shift", type=float, default=None, help="the reference channel's frequency shift (cycles per sample) behind the delay tasks")
     ap.add_argument("--wl-phases", action="store_true", help="run the waiting and learning phases (the coarse-frequency loop on the GPU) before anything is counted")
+    ap.add_argument("--smf-kernel", choices=["LANE", "WAVE"], default=None, help="with --wl-phases: the form of the coarse-frequency loop (LANE: one lane per stream; WAVE: one wave "
+                                                                                 "per stream; the same results); default: not set")
     ap.add_argument("--json", default=None)
     return ap
 
