@@ -12,6 +12,16 @@ using namespace dvbs2;
 
 namespace dvbs2 {
 thread_local std::string g_create_error;
+
+const char *modcod_name_by_pls(int b0_b6)
+{
+    for (int i = 0; i < DVBS2_N_MODCODS; i++) {
+        int v = 0;
+        for (int k = 0; k < 7; k++) v = v << 1 | (dvbs2_modcod_rows[i].pls[k] & 1);
+        if (v == b0_b6) return dvbs2_modcod_rows[i].name;
+    }
+    return nullptr;
+}
 }
 
 extern "C" {
@@ -118,6 +128,8 @@ static int create_init(dvbs2hip_t *h, const dvbs2hip_cfg *cfg)
         h->syn_words = syn.words; h->syn_rows = syn.rows;
     }
     if ((r = upload(h, &h->d_plh, plheader(*cfg)))) return r;
+    h->pls_value = 1;                                                              // (the framer's pairing is always the complementary one)
+    for (int k = 0; k < 7; k++) h->pls_value |= (cfg->pls[k] & 1) << (7 - k);
 
     // ---- modem
     const std::vector<float> cs = unit_constellation(*cfg);

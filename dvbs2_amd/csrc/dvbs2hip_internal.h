@@ -319,6 +319,8 @@ hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_n
 hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, hipStream_t s);
 hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hipStream_t s);
 hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, hipStream_t s);
+// k_pls.hip: the PLHEADER of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), decoded to V = b0 128 + .. + b6 2 + p; MET, ENE may be null
+hipError_t pls_decode_launch(const float *X, const float *const *SRC, size_t stride_cplx, int32_t *PLS, float *MET, float *ENE, int F, hipStream_t s);
 
 // ---------------------------------------------------------------- symbol-timing recovery and the channel's delay tasks (k_timing.hip)
 // one stream's state of Synchronizer_Gardner_fast_osf2 between calls (all zeros = _reset): the Farrow history x[n-1], x[n-2], x[n-3], the TED buffer {T0, T1}, mu (the Farrow

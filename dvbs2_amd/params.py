@@ -100,6 +100,24 @@ def get_modcod(name: str) -> ModCod:
     return MODCODS[name]
 
 
+def pls_value(mc: ModCod, pilots: bool = True) -> int:
+    """What the PLS decoder returns for a frame of this MODCOD: b0 128 + b1 64 + .. + b6 2 + pilots, b0..b6 the `pls` row (QPSK-S_8/9 with pilots: 43)."""
+    v = 0
+    for b in mc.pls:
+        v = v << 1 | (b & 1)
+    return v << 1 | bool(pilots)
+
+
+def pls_name(value: int):
+    """-> (the MODCOD of the table whose `pls` row is value >> 1, or None; pilots), as dvbs2hip_pls_describe"""
+    if not 0 <= value <= 255:
+        raise ValueError("a PLS value has 8 bits ('value' = %d)." % value)
+    for m in MODCODS.values():
+        if pls_value(m, False) == value & ~1:
+            return m.name, bool(value & 1)
+    return None, bool(value & 1)
+
+
 def load_ldpc_table(fname: str):
     """-> (row_ptr int32[n_rows+1], addr int32[n_addr]) from dvbs2_amd/data/ldpc/<fname>."""
     rows = []

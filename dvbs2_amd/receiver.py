@@ -622,6 +622,28 @@ class Dvbs2Hip:
     def sync_freq_phase_synchronize(self, X_N1):
         return self._sff(self.L.dvbs2hip_sync_freq_phase_synchronize, X_N1)
 
+    # ------------------------------------------------------------------ PLS decoder (an extension: include/dvbs2hip.h)
+    def pls_decode(self, X_N1):
+        """aligned PL frames -> (PLS, MET, ENE) per frame: the header's value b0 128 + .. + b6 2 + pilots, its correlation metric, the header's energy"""
+        X, F = self._frames(X_N1, 2 * self.pl_frame, np.float32)
+        PLS, MET, ENE = np.empty(F, np.int32), np.empty(F, np.float32), np.empty(F, np.float32)
+        self._chk(self.L.dvbs2hip_pls_decode(self.h, _ptr(X), _ptr(PLS), _ptr(MET), _ptr(ENE), F))
+        return PLS, MET, ENE
+
+    def pls_decode_dev(self, X, PLS, MET, ENE, n_frames):
+        """device addresses (MET, ENE may be None), stream-ordered"""
+        self._chk(self.L.dvbs2hip_pls_decode_dev(self.h, X, PLS, MET, ENE, n_frames))
+
+    def pls_decode_located_dev(self, SRC, PLS, MET, ENE, n_frames):
+        """the same on the frames SRC points to: the table sync_frame_locate_dev fills"""
+        self._chk(self.L.dvbs2hip_pls_decode_located_dev(self.h, SRC, PLS, MET, ENE, n_frames))
+
+    def pls_expected(self) -> int:
+        """what pls_decode returns for a frame of this handle's own MODCOD"""
+        v = C.c_int32()
+        self._chk(self.L.dvbs2hip_pls_expected(self.h, C.byref(v)))
+        return v.value
+
     def set_filter_kernel(self, kernel):
         """B.FIR_AUTO (default: matrix cores for <= 81 taps), B.FIR_VALU or B.FIR_MFMA"""
         self._chk(self.L.dvbs2hip_set_filter_kernel(self.h, int(kernel)))

@@ -12,6 +12,7 @@ offsets): README.md:151-169 of the reference.
 from __future__ import annotations
 
 import argparse
+import collections
 import sys
 
 import numpy as np
@@ -48,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--snk-path", default="", help="decoded payload of every frame, eight bits per byte (the reference's Sink_user_binary: a file sent with dvbs2_tx --src-type USER_BIN comes out as it went in)")
     ap.add_argument("--timing-offset", type=int, default=-1, help="sample index of the first symbol after the matched filter (default: two group delays)")
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
+    ap.add_argument("--pls-check", action="store_true", help="decode the PLHEADER of every aligned frame (MODCOD, frame type, pilots) and count the frames in lock whose value is not "
+                                                              "the one of --mod-cod; a stream of another MODCOD stops the run once 16 frames in lock have been seen and most of them differ")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
                                                                    "phase (the frequency shift) with this as its loop's frozen estimate (--wl-phases runs the loop instead)")
     add_timing_args(ap, learn_default=None)
@@ -58,6 +61,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sim-stats", action="store_true", help="per-kernel-group device time at the end (the reference's --sim-stats)")
     return ap
+
+
+def _pls_text(v):
+    """a decoded PLS value for a message: `QPSK-S_3/5 (PLS 23, pilots on)`, or the value alone when the table has no MODCOD for it"""
+    name, pilots = P.pls_name(v)
+    return "%s (PLS %d, pilots %s)" % (name, v, "on" if pilots else "off") if name else "PLS %d, pilots %s" % (v, "on" if pilots else "off")
 
 
 def run(args, out=sys.stdout) -> dict:
@@ -80,6 +89,7 @@ def run(args, out=sys.stdout) -> dict:
     if smf_kernel is not None and not wl:
         raise ValueError("--smf-kernel chooses the kernel of the coarse-frequency loop, which only --wl-phases runs: give both or neither")
     ultra = args.stm_type == "ULTRA"
+    pls_check = getattr(args, "pls_check", False)
     if wl and ultra:
         raise ValueError("--wl-phases steps FAST's detector inside the coarse-frequency loop: with --stm-type ULTRA it is not provided (use --stm-learn-frames)")
     if wl and not fast:
@@ -97,8 +107,11 @@ def run(args, out=sys.stdout) -> dict:
     # the task sequence (rx_sequence.py); --wl-phases: the frozen coarse estimate in front, and L&R as learning phase 3 has trained it, for what that estimate leaves
     seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq or wl), timing=args.stm_type, learn_frames=learn,
                      timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf,      # two group delays of grp_delay * osf samples
-                     fine=bool(args.sync_fine or wl), lr=wl)
+                     fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check)
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
+    if pls_check:
+        st["pls_mismatches"] = 0
+        pls_want, pls_locked, pls_seen = rx.pls_expected(), 0, collections.Counter()
     lock = LockTracker()
     try:
         if wl:
@@ -120,6 +133,12 @@ def run(args, out=sys.stdout) -> dict:
             bits = seq.decode(aligned)
             for f in range(len(sym)):
                 locked = lock.update(delay[f]) >= 2                                # the delay line has settled on this alignment
+                if pls_check and locked:
+                    v = int(seq.pls[0][f])
+                    pls_locked += 1; st["pls_mismatches"] += v != pls_want
+                    pls_seen[v] += v != pls_want
+                    if pls_locked >= 16 and 2 * st["pls_mismatches"] > pls_locked:
+                        raise ValueError("stream carries %s; the receiver was built for %s (PLS %d)" % (_pls_text(pls_seen.most_common(1)[0][0]), mc.name, pls_want))
                 if snk:
                     snk.send(bits[f])
                 if pattern is not None and locked:
@@ -135,7 +154,8 @@ def run(args, out=sys.stdout) -> dict:
     st["frames"], st["delay"] = lock.frames, lock.delay
     st["ber"] = st["be"] / max(1, st["locked_frames"] * mc.K_bch)
     st["fer"] = st["fe"] / max(1, st["locked_frames"])
-    print("# frames %(frames)d | in lock %(locked_frames)d | BE %(be)d | FE %(fe)d | BER %(ber).2e | FER %(fer).2e | delay %(delay)s" % st, file=out)
+    print("# frames %(frames)d | in lock %(locked_frames)d | BE %(be)d | FE %(fe)d | BER %(ber).2e | FER %(fer).2e | delay %(delay)s" % st +
+          (" | PLS mismatches %d" % st["pls_mismatches"] if pls_check else ""), file=out)
     return st
 
 

@@ -3,7 +3,7 @@ and learning phase 3 of dvbs2_amd/acquire.py drive it, each with its own source,
 
   front       front gain stage (Multiplier_AGC, :197)
   symbols     coarse frequency shift (:198) -> matched filter (:199-201) -> symbol timing: Gardner synchronize -> extract (:202-204), or every osf-th sample at a known offset
-  align       gain stage (:205) -> frame synchronizer (:206-209)
+  align       gain stage (:205) -> frame synchronizer (:206-209) [-> PLS decoder on the aligned frames' headers: pls_check, an extension]
   fine_sync   PL descrambler (:210) -> L&R (:211) -> pilot-aided phase synchronizer (:212)
   decode      fine_sync -> remove PLH -> estimate -> demodulate + deinterleave -> LDPC -> BCH -> BB descrambler (:213-220), one C-ABI call per task; or the fused chain
 
@@ -15,12 +15,14 @@ import numpy as np
 class RxSequence:
     """One per handle and stream.  agc: the two gain stages; coarse: the shift in front of the matched filter; timing: "PERFECT" (every osf-th matched-filter sample from
     timing_offset, needs pl_frame), "FAST" or "ULTRA" (the Gardner loop the handle has been set to; ULTRA holds once learn_frames frames have been fed); fine: the fine
-    synchronizers and the chain task by task, lr: L&R among them; fused (None: unless fine): rx_bb, the fused chain; sigma: the channel's, None for the estimator's."""
+    synchronizers and the chain task by task, lr: L&R among them; fused (None: unless fine): rx_bb, the fused chain; sigma: the channel's, None for the estimator's;
+    pls_check: align() also reads the aligned frames' PLHEADERs and leaves (PLS, MET, ENE) of its last call in self.pls (off: the call sequence has no such task)."""
 
-    def __init__(self, rx, F, osf=2, pl_frame=None, agc=True, coarse=False, timing="PERFECT", timing_offset=0, learn_frames=0, fine=False, lr=False, sigma=None, fused=None):
+    def __init__(self, rx, F, osf=2, pl_frame=None, agc=True, coarse=False, timing="PERFECT", timing_offset=0, learn_frames=0, fine=False, lr=False, sigma=None, fused=None, pls_check=False):
         if fused == fine:
             raise ValueError("the fused chain has no fine synchronizer in it, the tasks one by one start with them: fine or fused, not both or neither")
         self.rx, self.F, self.osf, self.n, self.agc, self.coarse, self.timing, self.learn_frames, self.fine, self.lr, self.sigma = rx, F, osf, pl_frame, agc, coarse, timing, learn_frames, fine, lr, sigma
+        self.pls_check, self.pls = pls_check, None
         self.fed = 0                                                               # frames the timing loop has taken
         self.skip = timing_offset
         self.tail = np.zeros((0, 2), np.float32)                                   # PERFECT: matched-filter samples not yet turned into symbols
@@ -51,7 +53,10 @@ class RxSequence:
         """-> (delay, flags, tri, aligned)"""
         if self.agc:
             sym = self.rx.agc(sym, n_frames=len(sym), output_energy=1.0).reshape(len(sym), -1)     # mult_agc: DVBS2.cpp:653-657
-        return self.rx.sync_frame_synchronize(sym, with_flags=True)
+        out = self.rx.sync_frame_synchronize(sym, with_flags=True)
+        if self.pls_check:
+            self.pls = self.rx.pls_decode(out[3])
+        return out
 
     def fine_sync(self, aligned):
         desc = self.rx.pl_descramble(aligned)

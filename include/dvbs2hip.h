@@ -588,6 +588,29 @@ int dvbs2hip_sync_lr_timeouts(dvbs2hip_t *h, int32_t *n_launches_repeated);
 int dvbs2hip_sync_freq_phase_synchronize(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t n_frames);
 int dvbs2hip_sync_freq_phase_synchronize_dev(dvbs2hip_t *h, const float *X_N1, float *FRQ, float *PHS, float *Y_N2, int32_t n_frames);
 
+/* ------------------------------------------------------------------ PLS decoder (extension: the reference has no such task, it takes the MODCOD from the command line)
+ * inverts: Framer<B>::generate_plh -- src/common/Module/Framer/Framer.hxx:97-196: seven bits b0..b6 times the 7 x 32 matrix G (row 0 the extension row, rows 1-5
+ *   the Walsh rows, row 6 all ones), every coded bit sent twice as y[2i] = c[i], y[2i+1] = c[i] ^ p (the framer always sends p = 1), XOR the 64-bit PLS scrambler,
+ *   pi/2-BPSK, times j when b0 = 1, behind the 26 SOF symbols.
+ * Per aligned PL frame, from its 90 header symbols r[k]:
+ *   PLS: int32_t[n_frames], V = b0 128 + b1 64 + b2 32 + b3 16 + b4 8 + b5 4 + b6 2 + p -- V & 127 is the standard's MODCOD * 4 + TYPE (pilots in bit 0), bit 7 the
+ *        extension bit; QPSK-S_8/9 with pilots is 43.  V = the one of the 256 headers H with the largest |sum_k r[k] conj(H[k])| over all 90 symbols (maximum
+ *        likelihood for an unknown constant phase; the SOF tells a code word from its complement).  Of equal metrics the smallest V wins.
+ *   MET: float[n_frames] (may be NULL), that metric; ENE: float[n_frames] (may be NULL), sum_k |r[k]|^2 -- MET / sqrt(90 ENE) is the normalised correlation.
+ *   X_N1: float[n_frames * 2*pl_frame], aligned frames: the frame synchronizer's Y_N2, before or after dvbs2hip_pl_descramble (the scrambler copies the header,
+ *        Scrambler_PL.hxx:63).  The located form reads frame f at SRC[f] instead: the table dvbs2hip_sync_frame_locate_dev fills (device pointers, 8-byte
+ *        aligned), same results bit for bit as the plain form on the same samples.
+ * Stateless: frames of S streams in one call are just frames.  n_frames in [1, max_frames].  The _dev forms are stream-ordered and may be recorded in a graph.
+ * fp32 in an order of its own (dvbs2_amd/csrc/k_pls.hip): bit-exact with nothing, held to a float64 search over the 256 headers by tests/test_pls_gpu.py.
+ * expected: the V of the handle's own configuration (cfg.pls, p = 1), what every frame of a matching stream decodes to.
+ * describe: no handle; the name of the MODCOD of the library's table whose pls row is value >> 1 ("" when there is none) and pilots = value & 1 (may be NULL);
+ *   DVBS2HIP_EINVAL for a value outside 0..255.                                                    */
+int dvbs2hip_pls_decode(dvbs2hip_t *h, const float *X_N1, int32_t *PLS, float *MET, float *ENE, int32_t n_frames);
+int dvbs2hip_pls_decode_dev(dvbs2hip_t *h, const float *X_N1, int32_t *PLS, float *MET, float *ENE, int32_t n_frames);
+int dvbs2hip_pls_decode_located_dev(dvbs2hip_t *h, const float *const *SRC, int32_t *PLS, float *MET, float *ENE, int32_t n_frames);
+int dvbs2hip_pls_expected(dvbs2hip_t *h, int32_t *value);
+int dvbs2hip_pls_describe(int32_t value, char *name, int32_t name_len, int32_t *pilots);
+
 /* ------------------------------------------------------------------ measurement
  * Per-kernel device time, measured with hipEvents recorded on the handle's stream around
  * each launch while timing is enabled (the equivalent of `--sim-stats`,
