@@ -341,7 +341,7 @@ int dvbs2hip_set_streams(dvbs2hip_t *h, int32_t S)
     if ((r = lr_check_all(h))) return r;                                           // (one-launch L&R calls not looked at yet belong to the old count)
     if ((r = dvbs2hip_sync_timing_set_streams(h, S))) return r;
     h->bw.S = S;                                                                   // (the per-stream state of the new count is allocated by the first call that needs it)
-    if ((r = dvbs2hip_filter_reset(h)) || (r = dvbs2hip_sync_lr_reset(h))) return r;
+    if ((r = dvbs2hip_filter_reset(h)) || (r = dvbs2hip_sync_lr_reset(h)) || (r = dvbs2hip_estimate_pilots_reset(h))) return r;
     if (h->sfm.ready && (r = sfm_state_reset(h, true))) return r;                  // as a new handle: the SOF delay, the previous output frame and the last metric too
     return 0;
 }

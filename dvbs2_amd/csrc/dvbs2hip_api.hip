@@ -252,6 +252,7 @@ int dvbs2hip_reset(dvbs2hip_t *h)
     if (!h) return DVBS2HIP_EINVAL;
     int r = dvbs2hip_filter_reset(h);
     if (r) return r;
+    if ((r = dvbs2hip_estimate_pilots_reset(h))) return r;
     return dvbs2hip_monitor_reset(h);
 }
 

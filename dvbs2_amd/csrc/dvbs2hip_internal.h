@@ -321,6 +321,12 @@ hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hi
 hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, hipStream_t s);
 // k_pls.hip: the PLHEADER of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), decoded to V = b0 128 + .. + b6 2 + p; MET, ENE may be null
 hipError_t pls_decode_launch(const float *X, const float *const *SRC, size_t stride_cplx, int32_t *PLS, float *MET, float *ENE, int F, hipStream_t s);
+// k_est_pilots.hip: the pilot-aided noise estimate of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), from its L = 90 + 36 N_pilots known symbols
+// (compact: the frame holds those L symbols and nothing else); plh: the 90 header symbols, seq: the PL sequence (read for scrambled = 1).  AN null: SIG / EB / ES (each
+// may be null) are written; AN given: (A, N) per frame and nothing else, and est_pilots_walk_launch averages them per stream (state: 3 floats per stream) and writes the outputs
+hipError_t est_pilots_launch(const float *X, const float *const *SRC, size_t stride_cplx, int compact, const float *plh, const uint8_t *seq, int scrambled, int L,
+                             float code_rate, int bps, float *AN, float *SIG, float *EB, float *ES, int F, hipStream_t s);
+hipError_t est_pilots_walk_launch(const float *AN, float *state, float alpha, int L, float code_rate, int bps, float *SIG, float *EB, float *ES, int Fs, int S, hipStream_t s);
 
 // ---------------------------------------------------------------- symbol-timing recovery and the channel's delay tasks (k_timing.hip)
 // one stream's state of Synchronizer_Gardner_fast_osf2 between calls (all zeros = _reset): the Farrow history x[n-1], x[n-2], x[n-3], the TED buffer {T0, T1}, mu (the Farrow

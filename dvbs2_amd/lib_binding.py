@@ -79,6 +79,11 @@ ABI = {
     "dvbs2hip_pls_decode_located_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_pls_expected": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "dvbs2hip_pls_describe": (C.c_int, [_i, C.c_char_p, _i, C.POINTER(C.c_int32)]),
+    "dvbs2hip_estimate_pilots": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "dvbs2hip_estimate_pilots_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "dvbs2hip_estimate_pilots_located_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "dvbs2hip_estimate_pilots_set_alpha": (C.c_int, [_vp, _f]),
+    "dvbs2hip_estimate_pilots_reset": (C.c_int, [_vp]),
     "dvbs2hip_sync_frame_get_metric": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "dvbs2hip_set_ldpc_params": (C.c_int, [_vp, _i, _f, _i]),
     "dvbs2hip_get_stream": (_vp, [_vp]),

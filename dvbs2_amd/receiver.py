@@ -644,6 +644,30 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_pls_expected(self.h, C.byref(v)))
         return v.value
 
+    # ------------------------------------------------------------------ pilot-aided noise estimator (an extension: include/dvbs2hip.h)
+    def estimate_pilots(self, X_N1, scrambled=True):
+        """aligned PL frames -> (SIG, Eb_N0, Es_N0) per frame from the header and pilot symbols; scrambled: the frames are as the frame synchronizer delivers them
+        (False: already PL-descrambled)"""
+        X, F = self._frames(X_N1, 2 * self.pl_frame, np.float32)
+        sig, eb, es = (np.empty(F, dtype=np.float32) for _ in range(3))
+        self._chk(self.L.dvbs2hip_estimate_pilots(self.h, _ptr(X), 1 if scrambled else 0, _ptr(sig), _ptr(eb), _ptr(es), F))
+        return sig, eb, es
+
+    def estimate_pilots_dev(self, X, scrambled, SIG, Eb_N0, Es_N0, n_frames):
+        """device addresses (each output may be None), stream-ordered; SIG goes straight into rx_bb_dev as sigma"""
+        self._chk(self.L.dvbs2hip_estimate_pilots_dev(self.h, X, int(scrambled), SIG, Eb_N0, Es_N0, n_frames))
+
+    def estimate_pilots_located_dev(self, SRC, scrambled, SIG, Eb_N0, Es_N0, n_frames):
+        """the same on the frames SRC points to: the table sync_frame_locate_dev fills"""
+        self._chk(self.L.dvbs2hip_estimate_pilots_located_dev(self.h, SRC, int(scrambled), SIG, Eb_N0, Es_N0, n_frames))
+
+    def estimate_pilots_set_alpha(self, alpha):
+        """0 (default): every frame on its own; 0 < alpha < 1: (A, N) averaged per stream, x = alpha x + (1 - alpha) v"""
+        self._chk(self.L.dvbs2hip_estimate_pilots_set_alpha(self.h, float(alpha)))
+
+    def estimate_pilots_reset(self):
+        self._chk(self.L.dvbs2hip_estimate_pilots_reset(self.h))
+
     def set_filter_kernel(self, kernel):
         """B.FIR_AUTO (default: matrix cores for <= 81 taps), B.FIR_VALU or B.FIR_MFMA"""
         self._chk(self.L.dvbs2hip_set_filter_kernel(self.h, int(kernel)))

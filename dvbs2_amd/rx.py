@@ -49,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--snk-path", default="", help="decoded payload of every frame, eight bits per byte (the reference's Sink_user_binary: a file sent with dvbs2_tx --src-type USER_BIN comes out as it went in)")
     ap.add_argument("--timing-offset", type=int, default=-1, help="sample index of the first symbol after the matched filter (default: two group delays)")
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
+    ap.add_argument("--est-type", default="DVBS2", choices=["DVBS2", "PILOTS"], help="the noise estimator: DVBS2 is the reference's M2M4 (biased low on 16APSK and 32APSK: it takes every point to have "
+                                                                                    "the same modulus), PILOTS the data-aided one on the frames' header and pilot symbols")
     ap.add_argument("--pls-check", action="store_true", help="decode the PLHEADER of every aligned frame (MODCOD, frame type, pilots) and count the frames in lock whose value is not "
                                                               "the one of --mod-cod; a stream of another MODCOD stops the run once 16 frames in lock have been seen and most of them differ")
     ap.add_argument("--coarse-freq", type=float, default=0.0, help="carrier offset of the received samples in cycles per sample: the coarse frequency synchronizer's task of the transmission "
@@ -107,7 +109,7 @@ def run(args, out=sys.stdout) -> dict:
     # the task sequence (rx_sequence.py); --wl-phases: the frozen coarse estimate in front, and L&R as learning phase 3 has trained it, for what that estimate leaves
     seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq or wl), timing=args.stm_type, learn_frames=learn,
                      timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf,      # two group delays of grp_delay * osf samples
-                     fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check)
+                     fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check, estimator=getattr(args, "est_type", "DVBS2"))
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
     if pls_check:
         st["pls_mismatches"] = 0

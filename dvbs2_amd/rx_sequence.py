@@ -6,6 +6,7 @@ and learning phase 3 of dvbs2_amd/acquire.py drive it, each with its own source,
   align       gain stage (:205) -> frame synchronizer (:206-209) [-> PLS decoder on the aligned frames' headers: pls_check, an extension]
   fine_sync   PL descrambler (:210) -> L&R (:211) -> pilot-aided phase synchronizer (:212)
   decode      fine_sync -> remove PLH -> estimate -> demodulate + deinterleave -> LDPC -> BCH -> BB descrambler (:213-220), one C-ABI call per task; or the fused chain
+              (estimator="PILOTS", an extension: sigma from the frames' header and pilot symbols instead, ahead of remove PLH or of the fused chain)
 
 The handle is a `Dvbs2Hip` or anything with the methods used here.  ULTRA's set_act(True) goes in front of the matched filter: the reference sets it once, ahead of the
 whole sequence (main_sched.cpp:655), and it touches the timing task's state alone, so where it stands among the tasks before sync_timing_synchronize changes no result."""
@@ -16,13 +17,17 @@ class RxSequence:
     """One per handle and stream.  agc: the two gain stages; coarse: the shift in front of the matched filter; timing: "PERFECT" (every osf-th matched-filter sample from
     timing_offset, needs pl_frame), "FAST" or "ULTRA" (the Gardner loop the handle has been set to; ULTRA holds once learn_frames frames have been fed); fine: the fine
     synchronizers and the chain task by task, lr: L&R among them; fused (None: unless fine): rx_bb, the fused chain; sigma: the channel's, None for the estimator's;
-    pls_check: align() also reads the aligned frames' PLHEADERs and leaves (PLS, MET, ENE) of its last call in self.pls (off: the call sequence has no such task)."""
+    pls_check: align() also reads the aligned frames' PLHEADERs and leaves (PLS, MET, ENE) of its last call in self.pls (off: the call sequence has no such task);
+    estimator: "DVBS2" (M2M4, the reference's; the call sequence is as it was) or "PILOTS" (estimate_pilots: unbiased for 16APSK and 32APSK too), used when sigma is None."""
 
-    def __init__(self, rx, F, osf=2, pl_frame=None, agc=True, coarse=False, timing="PERFECT", timing_offset=0, learn_frames=0, fine=False, lr=False, sigma=None, fused=None, pls_check=False):
+    def __init__(self, rx, F, osf=2, pl_frame=None, agc=True, coarse=False, timing="PERFECT", timing_offset=0, learn_frames=0, fine=False, lr=False, sigma=None, fused=None, pls_check=False,
+                 estimator="DVBS2"):
+        if estimator not in ("DVBS2", "PILOTS"):
+            raise ValueError("estimator is DVBS2 or PILOTS")
         if fused == fine:
             raise ValueError("the fused chain has no fine synchronizer in it, the tasks one by one start with them: fine or fused, not both or neither")
         self.rx, self.F, self.osf, self.n, self.agc, self.coarse, self.timing, self.learn_frames, self.fine, self.lr, self.sigma = rx, F, osf, pl_frame, agc, coarse, timing, learn_frames, fine, lr, sigma
-        self.pls_check, self.pls = pls_check, None
+        self.pls_check, self.pls, self.estimator = pls_check, None, estimator
         self.fed = 0                                                               # frames the timing loop has taken
         self.skip = timing_offset
         self.tail = np.zeros((0, 2), np.float32)                                   # PERFECT: matched-filter samples not yet turned into symbols
@@ -67,10 +72,15 @@ class RxSequence:
     def decode(self, aligned):
         """-> bits [frames, K_bch]"""
         rx = self.rx
+        pilots = self.estimator == "PILOTS" and self.sigma is None
         if not self.fine:
-            return rx.rx_bb(aligned, sigma=self.sigma)[0]
-        xf = rx.remove_plh(self.fine_sync(aligned))
-        sig = rx.estimate(xf)[0] if self.sigma is None else np.full(len(aligned), self.sigma, np.float32)
+            return rx.rx_bb(aligned, sigma=rx.estimate_pilots(aligned, scrambled=True)[0] if pilots else self.sigma)[0]
+        desc = self.fine_sync(aligned)
+        xf = rx.remove_plh(desc)
+        if pilots:
+            sig = rx.estimate_pilots(desc, scrambled=False)[0]
+        else:
+            sig = rx.estimate(xf)[0] if self.sigma is None else np.full(len(aligned), self.sigma, np.float32)
         vk, _ = rx.decode_siho(rx.demodulate(sig, xf, deinterleave=True))
         return rx.bb_descramble(rx.decode_hiho(vk)[0])
 

@@ -33,7 +33,8 @@ def build_parser():
     ap.add_argument("--dec-sched", default="QC", choices=["QC", "NATURAL"], help="NATURAL: the reference's sweep order over the rows of H (k_ldpc_nat.hip; a validation mode that wants -F 32768)")
     ap.add_argument("--dec-alpha", type=float, default=1.0)
     ap.add_argument("--no-early-stop", action="store_true")
-    ap.add_argument("--est-type", default="DVBS2", choices=["DVBS2", "PERFECT"])
+    ap.add_argument("--est-type", default="DVBS2", choices=["DVBS2", "PERFECT", "PILOTS"], help="DVBS2: the reference's M2M4 estimator inside the chain; PERFECT: the channel's sigma; "
+                                                                                              "PILOTS: the pilot-aided estimator on the frames' header and pilot symbols (unbiased for 16APSK and 32APSK too)")
     ap.add_argument("--max-frames", type=int, default=10_000_000, help="cap on frames per noise point (all ranks)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--clones", type=int, default=3,
@@ -122,6 +123,7 @@ def run(args, out=sys.stdout):
             self.sent = torch.empty((F, self.rx.K_bch), dtype=torch.int32, device=dev)
             self.got = torch.empty((F, self.rx.K_bch), dtype=torch.int32, device=dev)
             self.sig = torch.empty((F,), dtype=torch.float32, device=dev)
+            self.sig_est = torch.empty((F,), dtype=torch.float32, device=dev) if args.est_type == "PILOTS" else None      # (its own buffer: sig stays the channel's for the next batch)
             if args.filtered:
                 self.up = torch.empty((F, 2 * self.rx.pl_frame * osf), dtype=torch.float32, device=dev)
                 self.up2 = torch.empty_like(self.up)
@@ -142,7 +144,9 @@ def run(args, out=sys.stdout):
                 rx.extract_dev(self.up.data_ptr(), self.pl.data_ptr(), rx.pl_frame, osf, delay, F)
             else:
                 rx.tx_bb_dev(info, seed, self.sig.data_ptr(), self.sent.data_ptr(), self.pl.data_ptr(), F)
-            rx.rx_bb_dev(self.pl.data_ptr(), self.sig.data_ptr() if args.est_type == "PERFECT" else None, self.got.data_ptr(), None, None, F)
+            if args.est_type == "PILOTS":
+                rx.estimate_pilots_dev(self.pl.data_ptr(), 1, self.sig_est.data_ptr(), None, None, F)
+            rx.rx_bb_dev(self.pl.data_ptr(), self.sig.data_ptr() if args.est_type == "PERFECT" else self.sig_est.data_ptr() if args.est_type == "PILOTS" else None, self.got.data_ptr(), None, None, F)
             rx.check_errors_dev(self.sent.data_ptr(), self.got.data_ptr(), F - 1 if args.filtered else F)
             self.busy = True
 

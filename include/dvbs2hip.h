@@ -611,6 +611,37 @@ int dvbs2hip_pls_decode_located_dev(dvbs2hip_t *h, const float *const *SRC, int3
 int dvbs2hip_pls_expected(dvbs2hip_t *h, int32_t *value);
 int dvbs2hip_pls_describe(int32_t value, char *name, int32_t name_len, int32_t *pilots);
 
+/* ------------------------------------------------------------------ pilot-aided noise estimator (extension: the reference has no such task; its only estimator is
+ * Estimator_DVBS2, dvbs2hip_estimate above, whose Se = sqrt(|2 m2^2 - m4|) takes every constellation point to have the same modulus: on 16APSK it never reads above
+ * about 8.8 dB of Es/N0 and on 32APSK it stops near 5 dB, so sigma comes out 2 to 2.8 times too large)
+ * Per aligned PL frame y[n] of pl_frame symbols, from the L = 90 + 36 N_pilots symbols the receiver knows: the header at [0, 90), which carries the header of the
+ * handle's framer (cfg.pls, pairing bit 1), and pilot block b = 1..N_pilots at [90 + 1440 b + 36 (b - 1), +36), which carries (1 + j) / sqrt(2).  With p[k] those
+ * unit-modulus values and y[k] the received ones:
+ *   c = (1/L) sum_k y[k] conj(p[k])
+ *   N = sum_k |y[k] - c p[k]|^2 / (L - 1)          (noise power per complex symbol; the residual form: nothing small is the difference of two large numbers)
+ *   A = |c|^2,  S = A - N / L,  Es_N0 = 10 log10(S / N)
+ *   S <= 0: Es_N0 = -100; N = 0, or a ratio of 100 dB and more: Es_N0 = +100 (an fp32 frame without noise leaves N near 1e-14 A).
+ *   SIG = sqrt(1 / (2 10^(Es_N0 / 10))), Eb_N0 = Es_N0 - 10 log10(code rate x bits per symbol): the M2M4 task's expressions, and its sockets -- SIG, Eb_N0, Es_N0:
+ *   float[n_frames], each may be NULL.
+ * scrambled = 1: X_N1 is what the frame synchronizer delivers (header copied, pilots PL-scrambled); every pilot sample is first descrambled as dvbs2hip_pl_descramble
+ *   does it for its position (a swap or a sign change, exact).  scrambled = 0: X_N1 is already PL-descrambled (what L&R and the pilot-phase synchronizer produce).  The
+ *   two give the same results bit for bit.
+ * X_N1: float[n_frames * 2*pl_frame]; the host form stages only the known symbols' bytes.  The located form reads frame f at SRC[f] instead: the table
+ *   dvbs2hip_sync_frame_locate_dev fills (device pointers, 8-byte aligned), same results bit for bit as the plain form on the same samples.  SIG of a _dev form is a
+ *   device array that goes straight into dvbs2hip_rx_bb_dev / dvbs2hip_rx_bb_located_dev as sigma_in.
+ * The estimate is coherent over the frame: a constant phase does not move it, a residual carrier lowers S.  It belongs behind the fine synchronizers, or on a baseband
+ *   loop with no carrier error; removing the carrier is not this task's job.
+ * set_alpha(alpha), 0 <= alpha < 1, default 0 = every frame on its own and no state.  alpha > 0: the handle keeps (Abar, Nbar) per stream of dvbs2hip_set_streams
+ *   (stream s = frames [s F/S, (s+1) F/S); n_frames has to be a multiple of S); a stream's first frame after _reset sets Abar = A, Nbar = N, every later one does
+ *   x = alpha x + (1 - alpha) v in fp32, frames in order, and S and the outputs are formed from Abar, Nbar.  dvbs2hip_reset and dvbs2hip_set_streams reset this state too.
+ * n_frames in [1, max_frames].  The _dev forms are stream-ordered and may be recorded in a graph (alpha > 0: after one call outside the capture, which allocates the state).
+ * fp32 in an order of its own (dvbs2_amd/csrc/k_est_pilots.hip): bit-exact with nothing, held to float64 (tests/est_pilots_ref.py) at 1e-4 max(1, |x|).                  */
+int dvbs2hip_estimate_pilots(dvbs2hip_t *h, const float *X_N1, int32_t scrambled, float *SIG, float *Eb_N0, float *Es_N0, int32_t n_frames);
+int dvbs2hip_estimate_pilots_dev(dvbs2hip_t *h, const float *X_N1, int32_t scrambled, float *SIG, float *Eb_N0, float *Es_N0, int32_t n_frames);
+int dvbs2hip_estimate_pilots_located_dev(dvbs2hip_t *h, const float *const *SRC, int32_t scrambled, float *SIG, float *Eb_N0, float *Es_N0, int32_t n_frames);
+int dvbs2hip_estimate_pilots_set_alpha(dvbs2hip_t *h, float alpha);
+int dvbs2hip_estimate_pilots_reset(dvbs2hip_t *h);
+
 /* ------------------------------------------------------------------ measurement
  * Per-kernel device time, measured with hipEvents recorded on the handle's stream around
  * each launch while timing is enabled (the equivalent of `--sim-stats`,
