@@ -665,8 +665,8 @@ std::string emit_layer_table(LdpcPlan &pl, const Layers &layers, const Image &im
 // rotated byte offset of check t's element inside the row of an entry
 inline uint32_t rotated(uint32_t t, uint32_t shift) { return (t * 4u + (uint32_t)LDPC_Z * 4u - shift) % ((uint32_t)LDPC_Z * 4u); }
 
-// per-lane address table of the min-sum layer (k_ldpc_wg8.hip, W8_ATAB: every slot of the LDS-only image; -DW8_ATAB_HYB: the LDS slots of the hybrid images)
-void emit_atab_minsum(LdpcPlan &pl, const Image &im)
+// per-lane address table of the min-sum layer (k_ldpc_wg8.hip, ATAB: every slot of the LDS-only image)
+void emit_atab_minsum(LdpcPlan &pl)
 {
     const int q = pl.q, NW4 = (pl.fast_deg + 3) / 4;
     pl.w8_atab.assign((size_t)q * NW4 * LDPC_AT_LANES * 4, 0u);
@@ -677,16 +677,15 @@ void emit_atab_minsum(LdpcPlan &pl, const Image &im)
                 uint32_t v = ATAB_DROPPED;                                       // lanes past the 360th check / padding slots: an offset every buffer access drops
                 if (j < pl.fast_deg) {
                     const uint32_t shift = lt_shift(T8[j]), base = lt_base(T8[j]);
-                    const bool il = pl.fast_mode == 0 || (im.hyb && j < im.NLH);            // (what the kernel takes for an LDS slot: w8_slot_lds; a NULL slot's entry carries no flag)
-                    if (t < LDPC_Z) { const uint32_t d = rotated((uint32_t)t, shift); v = il ? d + base : d; }
-                    else if (il) v = base;                                      // an LDS slot of an idle lane: any address inside the allocation (never accessed: `act`)
+                    if (t < LDPC_Z) v = rotated((uint32_t)t, shift) + base;      // (every slot of the LDS-only image is an LDS slot; a NULL slot's entry carries no flag)
+                    else v = base;                                              // an LDS slot of an idle lane: any address inside the allocation (never accessed: `act`)
                 }
                 pl.w8_atab[(((size_t)r * NW4 + j / 4) * LDPC_AT_LANES + t) * 4 + (j & 3)] = v;
             }
     }
 }
 
-// (round 5) per-lane address table of the SUM-PRODUCT layer on the LDS-only image (k_ldpc_wg8.hip, W8_SPA_AT16): two 16-bit LDS byte addresses per dword (slot 2 k in the low
+// (round 5) per-lane address table of the SUM-PRODUCT layer on the LDS-only image (k_ldpc_wg8.hip, AT16): two 16-bit LDS byte addresses per dword (slot 2 k in the low
 // half), [q][pieces of 16 bytes][LDPC_AT_LANES][4] -- the image's 45 rows end at byte 64800, so every address of a real slot fits; a NULL slot reads the +inf WORD the
 // kernel keeps at junk row + 4 (the +inf row itself lies beyond 64 KB; the junk row is written at its word 0 only in this form), and the slot of check 0's absent
 // p_{c-1} points at the junk row's word 0 (its value is replaced by +inf, its store lands there).  false: an address does not fit (no DVB-S2 code: an LDS-only image is 45 rows)
@@ -890,8 +889,8 @@ std::string plan_fast(LdpcPlan &pl, const Layers &layers, const GenericStorage &
     bool park_bad, kd_ok;
     std::string e = emit_layer_table(pl, layers, im, park_bad, kd_ok);
     if (!e.empty()) return e;
-    if (!spa && !im.cu1 && (pl.fast_mode == 0 || LDPC_ATAB_HYB)) emit_atab_minsum(pl, im);
-    if (spa && !im.cu1 && pl.fast_mode == 0 && LDPC_SPA_AT16 && pl.fast_deg <= LDPC_SPA_AT16_MAXDEG && !emit_atab_spa16(pl, im)) return PLAN_RETRY_GENERIC;
+    if (!spa && !im.cu1 && pl.fast_mode == 0) emit_atab_minsum(pl);
+    if (spa && !im.cu1 && pl.fast_mode == 0 && pl.fast_deg <= LDPC_SPA_AT16_MAXDEG && !emit_atab_spa16(pl, im)) return PLAN_RETRY_GENERIC;
     e = emit_rows_and_swaps(pl, im, park_bad);
     if (!e.empty()) return e;
     size_workspace(pl, im, knobs);

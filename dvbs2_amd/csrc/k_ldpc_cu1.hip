@@ -18,6 +18,7 @@
 // Same schedule and arithmetic as the oracle (bit-exact): tests/test_ldpc_gpu.py, tests/test_golden_gpu.py.
 #include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
+#include "ldpc_device.h"           // address-space typedefs, and_or, ldpc_unpack, LDPC_ROW, LDPC_PROF_MARK
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -25,58 +26,12 @@
 
 namespace dvbs2 {
 
-typedef __attribute__((address_space(3))) float lds_float;
-typedef __attribute__((address_space(3))) int lds_int;
-typedef const __attribute__((address_space(4))) uint32_t *const_u32;
-
-constexpr int C1_ROW = LDPC_Z * 4;           // bytes per bit-group row
 constexpr int C1_IO = 16;                    // independent loads per lane in flight during frame I/O
 constexpr int C1_HA = LDPC_CU1_HA;           // slots of half A
-#ifndef LDPC_CU1_HA_SPA_V
-#define LDPC_CU1_HA_SPA_V 13
-#endif
-constexpr int C1_HA_SPA = LDPC_CU1_HA_SPA_V;    // ... in the sum-product kernel (half A also keeps the duplicate edges' deltas: 13 + 14 balances the registers)
+constexpr int C1_HA_SPA = 13;                // ... in the sum-product kernel (half A also keeps the duplicate edges' deltas: 13 + 14 balances the registers)
 constexpr int C1_WAVES = 16, C1_THREADS = C1_WAVES * 64;
 
-// development knobs (tools/build_variant_tus.sh): the row-keeping waves swap with ds_wrxchg_rtn (0) or with a read and a write per word (1); they swap right behind the
-// end-of-layer barrier (0) or behind the layer's first barrier (1), when the working waves' loads are out of the way
-#ifndef C1_SPA_BS        // sum-product layer: suffix values kept for every C1_SPA_BS-th slot
-#define C1_SPA_BS 2
-#endif
-#ifndef C1_SPA_KEEPW     // sum-product layer: a slot's LDS address is kept from its load to its store (1) or formed twice (0)
-#define C1_SPA_KEEPW 1
-#endif
-#ifndef C1_SPA_FENCE
-#define C1_SPA_FENCE 2
-#endif
-#ifndef C1_KEEP_RW
-#define C1_KEEP_RW 0
-#endif
-#ifndef C1_KEEP_LATE
-#define C1_KEEP_LATE 0
-#endif
-#ifdef LDPC_PHASE_PROF
-#define C1_MARK(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); prof[i] += (uint32_t)(n_ - pt_); pt_ = n_; } while (0)
-#else
-#define C1_MARK(i)
-#endif
-
 __device__ __forceinline__ lds_float *c1_lds(uint32_t a) { return (lds_float *)(size_t)a; }
-
-__device__ __forceinline__ float c1_and_or(uint32_t a, uint32_t m_sgpr, float b)      // (a & m) | b in one VALU operation
-{
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m_sgpr), "v"(b));
-    return r;
-}
-
-// message on local slot j of a half with NS slots from the packed per-check state: magnitude c1 at the recorded minimum, c2 elsewhere; sign = bit (NS-1-j) of pk
-template <int NS>
-__device__ __forceinline__ float c1_unpack(float c1, float c2, uint32_t pk, uint32_t j, uint32_t sb)
-{
-    const float mag = ((pk >> 27) == j) ? c1 : c2;
-    return c1_and_or(pk << ((32u - NS) + j), sb, mag);
-}
 
 // ---- the row-keeping waves: group `grp` (two waves, 120 of their 128 lanes hold elements e, e + 120, e + 240 of NRG rows) follows the working waves barrier for
 // barrier and swaps rows with LDS positions by the plan's table (w8_park_server of k_ldpc_wg8.hip, for a workgroup with two such groups and the barrier
@@ -97,7 +52,7 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
     const const_u32 srow = (const_u32)p.w8.rows + p.w8.nl + p.w8.ng + q + grp * NRG;        // bit-group in this group's slot k at the start of an iteration
     const int el = sidx * 64 + lane;
     const bool on = el < LDPC_Z / 3;
-    const uint32_t a0 = (uint32_t)el * 4u + (uint32_t)(grp * NRG) * (uint32_t)C1_ROW;       // this lane's first word of the group's first position
+    const uint32_t a0 = (uint32_t)el * 4u + (uint32_t)(grp * NRG) * (uint32_t)LDPC_ROW;       // this lane's first word of the group's first position
     constexpr uint32_t A1 = LDPC_Z / 3 * 4u, A2 = 2u * A1;
     auto lst = [&](uint32_t a, float v) { *c1_lds(a) = v; };
     auto lxc = [&](uint32_t a, float v) -> float { return __hip_atomic_exchange(c1_lds(a), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
@@ -121,14 +76,8 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
         for (int k = 0; k < NRG; k++) {
             const bool sw = k < 32 ? ((mlo >> k) & 1u) != 0u : ((mhi >> (k - 32)) & 1u) != 0u;
             if (sw) {
-                const uint32_t b = a0 + (uint32_t)k * (uint32_t)C1_ROW;
-#if C1_KEEP_RW
-                const float n0 = *c1_lds(b), n1 = *c1_lds(b + A1), n2 = *c1_lds(b + A2);
-                lst(b, R[k][0]); lst(b + A1, R[k][1]); lst(b + A2, R[k][2]);
-                R[k][0] = n0; R[k][1] = n1; R[k][2] = n2;
-#else
+                const uint32_t b = a0 + (uint32_t)k * (uint32_t)LDPC_ROW;
                 R[k][0] = lxc(b, R[k][0]); R[k][1] = lxc(b + A1, R[k][1]); R[k][2] = lxc(b + A2, R[k][2]);
-#endif
             }
         }
     };
@@ -138,9 +87,6 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
         const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
         bar_nowait();                               // the halves' partial minima are in the exchange area; every read of the layer precedes its writes
         if (SPA == 1) bar_nowait();                 // sum-product layer with the per-check scale: the halves' products are in the exchange area (the capped rule needs one exchange)
-#if C1_KEEP_LATE
-        moves(r);
-#endif
         if (ncf > 0) {
             bar_nowait();                           // the primary writes are in place
             uint32_t prev_lvl = 1u;
@@ -149,9 +95,9 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
                 if (lvl != prev_lvl) { bar_nowait(); prev_lvl = lvl; }
             }
         }
-        C1_MARK(0);
+        LDPC_PROF_MARK(0);
         __syncthreads();                            // end of the layer: the swapped rows are in place
-        C1_MARK(1);
+        LDPC_PROF_MARK(1);
     };
     const bool es = p.early_stop != 0;
     for (int qp = blockIdx.x; qp < p.n_frames; ) {
@@ -170,14 +116,14 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
             R[k][0] = __builtin_nontemporal_load(&Yg[elc]); R[k][1] = __builtin_nontemporal_load(&Yg[elc + LDPC_Z / 3]); R[k][2] = __builtin_nontemporal_load(&Yg[elc + 2 * (LDPC_Z / 3)]);
         }
         __syncthreads();                            // the image is in place
-        C1_MARK(8);
+        LDPC_PROF_MARK(8);
         // ph 0: layer r of an iteration; 1: layer r of the syndrome sweep; 2: catching up with the schedule after a sweep that stopped early
         int ph = 0, r = 0, it = 0;
         bool ok = false, fin = false;
         while (!fin) {
             bool mv = true;
             if (ph == 1 && es && r == 0 && vote0()) { ok = false; mv = false; ph = 3; }       // stopping rule: the vote on layer 0 comes before anything moves
-            if (mv && !(C1_KEEP_LATE && ph == 0)) moves(r);
+            if (mv) moves(r);
             if (ph == 0) {
                 layer_barriers(r);
                 if (++r == q) { r = 0; it++; if (es || it == p.n_ite) { ph = 1; ok = true; } }
@@ -192,15 +138,15 @@ __device__ __forceinline__ void cu1_keeper(const LdpcKParams &p, lds_int *const 
             }
             if (ph == 3) { if (ok || it >= p.n_ite) fin = true; else { ph = 0; r = 0; } }
         }
-        C1_MARK(6);
+        LDPC_PROF_MARK(6);
         // outputs: the parked rows go through LDS positions grp * NRG .. once the working waves have read the LDS rows
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < NRG; k++) if (on) { const uint32_t b = a0 + (uint32_t)k * (uint32_t)C1_ROW; lst(b, R[k][0]); lst(b + A1, R[k][1]); lst(b + A2, R[k][2]); }
+        for (int k = 0; k < NRG; k++) if (on) { const uint32_t b = a0 + (uint32_t)k * (uint32_t)LDPC_ROW; lst(b, R[k][0]); lst(b + A1, R[k][1]); lst(b + A2, R[k][2]); }
         __syncthreads();
         __syncthreads();                            // the image is reused by the next frame
         qp = s_misc[19];
-        C1_MARK(7);
+        LDPC_PROF_MARK(7);
 #ifdef LDPC_PHASE_PROF
         prof[9]++;
 #endif
@@ -226,7 +172,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
     const const_u32 tab = (const_u32)p.w8.tab;
     const const_u32 rows = (const_u32)p.w8.rows;
     const uint32_t ljunk = p.w8.lds_junk;
-    const uint32_t xch = ljunk + (uint32_t)C1_ROW;                    // exchange area: [half][360] x 8 bytes
+    const uint32_t xch = ljunk + (uint32_t)LDPC_ROW;                    // exchange area: [half][360] x 8 bytes
     const uint32_t xmine = xch + (uint32_t)HALF * (LDPC_Z * 8u) + (uint32_t)t * 8u, xother = xch + (uint32_t)(1 - HALF) * (LDPC_Z * 8u) + (uint32_t)t * 8u;
     uint32_t SB = 0x80000000u;
     asm volatile("" : "+s"(SB));
@@ -251,7 +197,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
 #pragma unroll
                 for (int k = 0; k < C1_IO; k++) { const int g = (int)rows[l0 + k < nl_info ? l0 + k : nl_info - 1]; v[k] = __builtin_nontemporal_load(&Y[(g < p.n_info ? g : 0) * LDPC_Z + t]); }
 #pragma unroll
-                for (int k = 0; k < C1_IO; k++) if (l0 + k < nl_info && (int)rows[l0 + k < nl_info ? l0 + k : 0] < p.n_info) lst((uint32_t)(l0 + k) * C1_ROW + t4, v[k]);      // (a parity group's position: filled by the scatter below)
+                for (int k = 0; k < C1_IO; k++) if (l0 + k < nl_info && (int)rows[l0 + k < nl_info ? l0 + k : 0] < p.n_info) lst((uint32_t)(l0 + k) * LDPC_ROW + t4, v[k]);      // (a parity group's position: filled by the scatter below)
             }
         }
         {
@@ -280,7 +226,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
         }
         if (p.packed && first_wave && lane == 0 && (p.K & 31)) p.packed[(size_t)f * ((p.K + 31) / 32) + p.K / 32] = 0u;     // the bits behind K in the last word
         __syncthreads();
-        C1_MARK(8);
+        LDPC_PROF_MARK(8);
 
         int it = 0;
         bool ok = false;
@@ -317,17 +263,17 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     // workgroup's global slot as [layer][half][group of 4 slots][360][4]: 778 KB per frame, 199 MB for the 256 workgroups of a launch -- inside
                     // the 256 MB Infinity Cache, which the 512 x 778 KB of the two-frames-per-CU kernel are not (there the messages are an HBM stream).
                     constexpr int NG4 = NS / 4, NT = NS % 4;
-                    constexpr uint32_t HB = HALF == 0 ? 0u : (uint32_t)((HA / 4) * (C1_ROW * 4) + (HA % 4) * C1_ROW), LB = (uint32_t)(DEG * C1_ROW);
+                    constexpr uint32_t HB = HALF == 0 ? 0u : (uint32_t)((HA / 4) * (LDPC_ROW * 4) + (HA % 4) * LDPC_ROW), LB = (uint32_t)(DEG * LDPC_ROW);
                     typedef uint32_t m_u32x4 __attribute__((ext_vector_type(4)));
                     typedef uint32_t m_u32x2 __attribute__((ext_vector_type(2)));
                     typedef uint32_t m_u32x3 __attribute__((ext_vector_type(3)));
                     auto msg_ld = [&](float *dst, uint32_t lbase) __attribute__((always_inline)) {
 #pragma unroll
                         for (int g = 0; g < NG4; g++) {
-                            const m_u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(rs, t4 * 4u, lbase + HB + (uint32_t)g * (C1_ROW * 4u), 0);
+                            const m_u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(rs, t4 * 4u, lbase + HB + (uint32_t)g * (LDPC_ROW * 4u), 0);
                             dst[4 * g] = __uint_as_float(q4.x); dst[4 * g + 1] = __uint_as_float(q4.y); dst[4 * g + 2] = __uint_as_float(q4.z); dst[4 * g + 3] = __uint_as_float(q4.w);
                         }
-                        const uint32_t tb = lbase + HB + (uint32_t)NG4 * (C1_ROW * 4u);
+                        const uint32_t tb = lbase + HB + (uint32_t)NG4 * (LDPC_ROW * 4u);
                         if (NT == 3) { const m_u32x3 q3 = __builtin_amdgcn_raw_buffer_load_b96(rs, t4 * 3u, tb, 0); dst[4 * NG4] = __uint_as_float(q3.x); dst[4 * NG4 + 1] = __uint_as_float(q3.y); dst[(NT == 3 ? 4 * NG4 + 2 : 0)] = __uint_as_float(q3.z); }
                         if (NT == 2) { const m_u32x2 q2 = __builtin_amdgcn_raw_buffer_load_b64(rs, t4 * 2u, tb, 0); dst[4 * NG4] = __uint_as_float(q2.x); dst[(NT >= 2 ? 4 * NG4 + 1 : 0)] = __uint_as_float(q2.y); }
                         if (NT == 1) dst[4 * NG4] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, t4, tb, 0));
@@ -336,11 +282,11 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     asm volatile("" : "+s"(MAGM));
                     // registers: the suffix values are kept for every second slot and rebuilt from there on the way forward; the circulant offsets are formed twice (loads,
                     // stores) through an opaque copy of the lane's offset so that the compiler does not hold them across the arithmetic (as in k_ldpc_wg8.hip's SPA layer)
-                    constexpr int BS = C1_SPA_BS, NB = (NS + BS - 1) / BS;
+                    constexpr int BS = 2, NB = (NS + BS - 1) / BS;
                     float x[NS], u[NS], Bs[NB], od[LDPC_SPA_MAXC];
                     uint32_t t4s = t4;
-                    uint32_t wk[C1_SPA_KEEPW ? NS : 1];
-                    auto woff = [&](int j, uint32_t tt) __attribute__((always_inline)) { const uint32_t d = tt - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK); };
+                    uint32_t wk[NS];                          // a slot's LDS address, kept from its load to its store
+                    auto woff = [&](int j, uint32_t tt) __attribute__((always_inline)) { const uint32_t d = tt - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW) + ((E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK); };
                     float mn1 = INFINITY, mn2 = INFINITY, kap = 1.f, cln = 0.f, key = 0.f, Qown = 0.f;
                     uint32_t sx = 0u;
                     auto comb = [&](float a, float b) __attribute__((always_inline)) { return __builtin_fmaf(b, __builtin_fmaf(-kap, a, 1.f), a); };      // Q'_ab
@@ -349,13 +295,8 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     if (act) {
 #pragma unroll
                         for (int j = 0; j < NS; j++) {
-#if C1_SPA_KEEPW
                             wk[j] = woff(j, t4);
-                            if (FWD && j == NS - 1 && r > 0) x[j] = pfw; else x[j] = lld(wk[j]);
-#else
-                            if (FWD && j == NS - 1 && r > 0) x[j] = pfw;         // p_{c-1}: handed over by layer r - 1
-                            else x[j] = lld(woff(j, t4));
-#endif
+                            if (FWD && j == NS - 1 && r > 0) x[j] = pfw; else x[j] = lld(wk[j]);      // p_{c-1}: handed over by layer r - 1
                         }
                         if (HALF == 0) {
 #pragma unroll
@@ -390,9 +331,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         *(lds_f32x2 *)(size_t)xmine = mine;
                         }
                     }
-                    C1_MARK(1);
+                    LDPC_PROF_MARK(1);
                     __syncthreads();         // the halves' minima (SPA = 3: products) are in place; every read of the layer precedes its writes
-                    C1_MARK(2);
+                    LDPC_PROF_MARK(2);
                     uint32_t SXT = 0u;
                     float Aoth = 0.f;
                     if constexpr (SPA == 3) {
@@ -433,9 +374,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         asm volatile("" : "+v"(t4s));
 #pragma unroll
                         for (int j = 0; j < NS; j++) {
-                            // (a scheduling fence every C1_SPA_FENCE slots: left alone the scheduler interleaves all 13 / 14 slots' reciprocal / logarithm chains and needs
+                            // (a scheduling fence every second slot: left alone the scheduler interleaves all 13 / 14 slots' reciprocal / logarithm chains and needs
                             // ~30 registers more than the kernel has)
-                            if (C1_SPA_FENCE > 0 && j > 0 && j % C1_SPA_FENCE == 0) __builtin_amdgcn_sched_barrier(0);
+                            if (j > 0 && j % 2 == 0) __builtin_amdgcn_sched_barrier(0);
                             const float wA = __builtin_fmaf(-kap, A, 1.f);
                             float Bj;
                             {
@@ -452,7 +393,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                             float nw;
                             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(nw) : "s"(MAGM), "v"(o), "v"(SXT ^ __float_as_uint(x[j])));
                             A = __builtin_fmaf(u[j], wA, A);
-                            uint32_t a = C1_SPA_KEEPW ? wk[C1_SPA_KEEPW ? j : 0] : woff(j, t4s);
+                            uint32_t a = wk[j];
                             if (HALF == 1 && j == NS - 1 && mask0) a = ljunk + t4s;
                             if (FWD && j == NS - 2 && r + 1 < q) pfw = x[j] + nw;                    // p_c: kept for layer r + 1
                             else if (HALF == 0 && j < ldpc_w8_kd(DEG)) { if (((prim >> j) & 1u) != 0u) lst(a, x[j] + nw); }      // a duplicate edge's plain store is left out
@@ -460,9 +401,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                             mq[j & 3] = nw;
                             if ((j & 3) == 3)
                                 __builtin_amdgcn_raw_buffer_store_b128(m_u32x4{__float_as_uint(mq[0]), __float_as_uint(mq[1]), __float_as_uint(mq[2]), __float_as_uint(mq[3])}, rs,
-                                                                       wide_off(t4s * 4u, mrow + HB + (uint32_t)(j >> 2) * (C1_ROW * 4u)), 0u, 0);
+                                                                       wide_off(t4s * 4u, mrow + HB + (uint32_t)(j >> 2) * (LDPC_ROW * 4u)), 0u, 0);
                             else if (j == NS - 1) {
-                                const uint32_t tb = mrow + HB + (uint32_t)NG4 * (C1_ROW * 4u);
+                                const uint32_t tb = mrow + HB + (uint32_t)NG4 * (LDPC_ROW * 4u);
                                 if (NT == 3) __builtin_amdgcn_raw_buffer_store_b96(m_u32x3{__float_as_uint(mq[0]), __float_as_uint(mq[1]), __float_as_uint(mq[2])}, rs, wide_off(t4s * 3u, tb), 0u, 0);
                                 if (NT == 2) __builtin_amdgcn_raw_buffer_store_b64(m_u32x2{__float_as_uint(mq[0]), __float_as_uint(mq[1])}, rs, t4s * 2u, tb, 0);
                                 if (NT == 1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mq[0]), rs, t4s, tb, 0);
@@ -478,10 +419,10 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         }
                     }
                     tev = p.w8.tab[(r + 1 < q ? r + 1 : 0) * LDPC_FAST_STRIDE + (lane & 31)];      // the next layer's table (see `tev`)
-                    C1_MARK(3);
+                    LDPC_PROF_MARK(3);
                     // duplicate edges: ordered delta updates, level by level, by half A's lanes (conflict entry i is slot i: what it adds is od[i] = new - old)
                     if (ncf > 0) {
-                        auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
+                        auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
                         uint32_t prev_lvl = 0u;
 #pragma unroll
                         for (int i = 0; i < LDPC_SPA_MAXC; i++) {
@@ -492,9 +433,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                             if (HALF == 0 && act) { const uint32_t a = addr_of(e); const float Lv = lld(a); lst(a, Lv + od[i]); }
                         }
                     }
-                    C1_MARK(4);
+                    LDPC_PROF_MARK(4);
                     __syncthreads();
-                    C1_MARK(5);
+                    LDPC_PROF_MARK(5);
                     continue;
                 }
                 float v[NS];
@@ -509,7 +450,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     for (int j = 0; j < NS; j++) {
                         const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK);
                         const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
-                        w[j] = min(d, d + (uint32_t)C1_ROW) + base;
+                        w[j] = min(d, d + (uint32_t)LDPC_ROW) + base;
                         if (FWD && j == NS - 1 && r > 0) v[j] = pfw;         // p_{c-1}: handed over by layer r - 1
                         else v[j] = lld(w[j]);
                     }
@@ -520,7 +461,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         if (HALF == 0) { const u32x3 sv = __builtin_amdgcn_raw_buffer_load_b96(rs, t4 * 4u, so, 0); nx1 = __uint_as_float(sv.x); nx2 = __uint_as_float(sv.y); nxk = __uint_as_float(sv.z); }
                         else { const u32x4 sv = __builtin_amdgcn_raw_buffer_load_b128(rs, t4 * 4u, so, 0); nx1 = __uint_as_float(sv.x); nx2 = __uint_as_float(sv.y); nxk = __uint_as_float(sv.w); }
                     }
-                    C1_MARK(0);
+                    LDPC_PROF_MARK(0);
                     // ---- pass 1b: v->c = posterior - old c->v ; running min1 / min2 / signs of this half
                     const uint32_t idxo = pko >> 27;
                     if (it == 0) {
@@ -538,7 +479,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
 #pragma unroll
                     for (int j = 0; j < NS; j++) {
                         const float mag = (idxo == (uint32_t)j) ? c1o : c2o;
-                        const float old = c1_and_or(pko << ((32u - NS) + j), SB, mag);          // sign bit of local slot j | magnitude (>= 0)
+                        const float old = and_or(pko << ((32u - NS) + j), SB, mag);          // sign bit of local slot j | magnitude (>= 0)
                         float x = v[j] - old;
                         if (HALF == 1 && j == NS - 1 && mask0) x = INFINITY;
                         v[j] = x;
@@ -554,9 +495,9 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     *(lds_f32x2 *)(size_t)xmine = mine;
                     tot = par;
                 }
-                C1_MARK(1);
+                LDPC_PROF_MARK(1);
                 __syncthreads();         // the halves' partial results are in place; every read of the layer precedes its writes
-                C1_MARK(2);
+                LDPC_PROF_MARK(2);
                 if (act) {
                     // ---- merge: the two smallest magnitudes of the whole check and the parity of all its signs
                     const f32x2 oth = *(lds_f32x2 *)(size_t)xother;
@@ -606,11 +547,11 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     }
                     if (q == 1) { nx1 = cst1; nx2 = cst2; nxk = __uint_as_float(pkn); }
                 }
-                C1_MARK(3);
+                LDPC_PROF_MARK(3);
                 // ---- duplicate edges of a bit-group inside this layer: ordered delta updates, level by level, by half A's lanes (conflict entry i is slot i)
                 if (ncf > 0) {
-                    auto addr_of = [&](uint32_t e) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
-                    auto delta_of = [&](uint32_t j) { return c1_unpack<NS>(cst1, cst2, pkn, j, SB) - c1_unpack<NS>(c1o, c2o, pko, j, SB); };
+                    auto addr_of = [&](uint32_t e) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK); };
+                    auto delta_of = [&](uint32_t j) { return ldpc_unpack<NS>(cst1, cst2, pkn, j, SB) - ldpc_unpack<NS>(c1o, c2o, pko, j, SB); };
                     const uint32_t j0 = (cinfo >> LT_CINFO_SLOT0_SHIFT) & LT_SLOT_MASK, j1 = (cinfo >> LT_CINFO_SLOT1_SHIFT) & LT_SLOT_MASK, lvl1 = (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK;
                     const bool two = ncf > 1 && lvl1 == 1u;         // entry 1 commutes with entry 0 (another bit-group)
                     __syncthreads();                                // the primary writes of the layer are in place
@@ -618,7 +559,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         const uint32_t a0 = addr_of(ce0), a1 = addr_of(ce1);
                         float L0, L1 = 0.f;
                         L0 = lld(a0); if (two) L1 = lld(a1);
-                        const float d0 = it == 0 ? c1_unpack<NS>(cst1, cst2, pkn, j0, SB) : delta_of(j0), d1 = it == 0 ? c1_unpack<NS>(cst1, cst2, pkn, j1, SB) : delta_of(j1);
+                        const float d0 = it == 0 ? ldpc_unpack<NS>(cst1, cst2, pkn, j0, SB) : delta_of(j0), d1 = it == 0 ? ldpc_unpack<NS>(cst1, cst2, pkn, j1, SB) : delta_of(j1);
                         lst(a0, L0 + d0); if (two) lst(a1, L1 + d1);
                     }
                     uint32_t prev_lvl = 1u;
@@ -629,13 +570,13 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         if (HALF == 0 && act) {
                             const uint32_t a = addr_of(e);
                             const float Lv = lld(a);
-                            lst(a, Lv + (it == 0 ? c1_unpack<NS>(cst1, cst2, pkn, j, SB) : delta_of(j)));
+                            lst(a, Lv + (it == 0 ? ldpc_unpack<NS>(cst1, cst2, pkn, j, SB) : delta_of(j)));
                         }
                     }
                 }
-                C1_MARK(4);
+                LDPC_PROF_MARK(4);
                 __syncthreads();
-                C1_MARK(5);
+                LDPC_PROF_MARK(5);
             }
             it++;
             if (p.early_stop || it == p.n_ite) {
@@ -660,7 +601,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                         for (int j = 0; j < DEG; j++) {
                             const uint32_t e = T[j];
                             const uint32_t d = t4 - (e & LT_SHIFT_MASK);
-                            Lv[j] = lld(min(d, d + (uint32_t)C1_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK));
+                            Lv[j] = lld(min(d, d + (uint32_t)LDPC_ROW) + ((e >> LT_BASE_SHIFT) & LT_BASE_MASK));
                         }
                         if (r == 0 && t == 0) Lv[DEG - 1] = 0.f;                               // absent edge
                         uint32_t x = 0u;
@@ -674,7 +615,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
                     } else if (r == q - 1) { if (vote(bad)) ok = false; }
                     else __syncthreads();
                 }
-                C1_MARK(6);
+                LDPC_PROF_MARK(6);
                 if (ok) break;
             }
         }
@@ -712,7 +653,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
         for (int l0 = HALF * C1_IO; l0 < nl_out; l0 += 2 * C1_IO) {
             float v[C1_IO];
 #pragma unroll
-            for (int k = 0; k < C1_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < nl_out ? l0 + k : nl_out - 1) * C1_ROW + t4) : 0.f;
+            for (int k = 0; k < C1_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < nl_out ? l0 + k : nl_out - 1) * LDPC_ROW + t4) : 0.f;
 #pragma unroll
             for (int k = 0; k < C1_IO; k++) if (l0 + k < nl_out) emit((int)rows[l0 + k], v[k]);
         }
@@ -724,7 +665,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
             for (int l0 = HALF * C1_IO; l0 < NRT; l0 += 2 * C1_IO) {
                 float v[C1_IO];
 #pragma unroll
-                for (int k = 0; k < C1_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRT ? l0 + k : NRT - 1) * C1_ROW + t4) : 0.f;
+                for (int k = 0; k < C1_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRT ? l0 + k : NRT - 1) * LDPC_ROW + t4) : 0.f;
 #pragma unroll
                 for (int k = 0; k < C1_IO; k++) if (l0 + k < NRT && srow[l0 + k] != ROWS_NONE) emit((int)srow[l0 + k], v[k]);
             }
@@ -732,7 +673,7 @@ __device__ __forceinline__ void cu1_work(const LdpcKParams &p, lds_int *const s_
         if (first_wave && lane == 0) s_misc[19] = p.cu_ctr ? (int)(atomicAdd(&p.cu_ctr[LDPC_FRAME_CTR], 1u) + gridDim.x) : qp + (int)gridDim.x;
         __syncthreads();     // the posterior image is reused by the next frame of this workgroup
         qp = s_misc[19];
-        C1_MARK(7);
+        LDPC_PROF_MARK(7);
 #ifdef LDPC_PHASE_PROF
         prof[9]++;
 #endif

@@ -4,23 +4,13 @@
 // duplicate edges per layer -- and the subject of `DVBS2HIP_LDPC_PATH=generic` experiments; every DVB-S2 code shipped here runs on k_ldpc_wg8.hip or
 // k_ldpc_cu1.hip.  ldpc_dispatch.hip chooses between the three.  Behind it: the two small kernels of the work queue's opt-in frame order.
 #include "ldpc_dispatch.h"
+#include "ldpc_device.h"           // lds_float, const_u32 / const_i32 / const_u64 (and why they exist)
 
 namespace dvbs2 {
 
 // ------------------------------------------------------------------------------------------
 // device
 // ------------------------------------------------------------------------------------------
-// LDS pointers carry their address space in the type, so the optimiser can never merge an
-// LDS access and a global access into one flat access through a selected generic pointer.
-typedef __attribute__((address_space(3))) float lds_float;
-// The layer tables are read-only for the whole launch.  Reading them through the CONSTANT
-// address space lets the compiler use scalar loads (SGPRs, scalar cache) for these
-// wave-uniform addresses; through a plain global pointer it must assume the kernel's own
-// stores may alias them and falls back to per-lane vector loads with a full memory round
-// trip in front of every edge.
-typedef const __attribute__((address_space(4))) uint32_t *const_u32;
-typedef const __attribute__((address_space(4))) int32_t *const_i32;
-typedef const __attribute__((address_space(4))) unsigned long long *const_u64;
 static_assert(sizeof(LdpcGroup) == 8, "group table is read as 64-bit scalars");
 
 __device__ __forceinline__ LdpcGroup group_ld(const_u64 groups, int g)

@@ -16,31 +16,28 @@
 // Min-sum / normalised min-sum only; used by dvbs2hip_api.hip for calls of at most one frame per CU on codes whose image and state fit the LDS.
 #include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
+#include "ldpc_device.h"           // lds_float, const_u32, quad_xor1
 
 namespace dvbs2 {
 
-typedef __attribute__((address_space(3))) float lat_lds_float;
 typedef __attribute__((address_space(3))) uint32_t lat_lds_u32;
-typedef const __attribute__((address_space(4))) uint32_t *lat_const_u32;
 constexpr int LAT_THREADS = 768, LAT_ROW = LDPC_Z * 4;
 
-__device__ __forceinline__ lat_lds_float *lat_f(uint32_t a) { return (lat_lds_float *)(size_t)a; }
+__device__ __forceinline__ lds_float *lat_f(uint32_t a) { return (lds_float *)(size_t)a; }
 __device__ __forceinline__ lat_lds_u32 *lat_u(uint32_t a) { return (lat_lds_u32 *)(size_t)a; }
-__device__ __forceinline__ float lat_swap(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }      // quad_perm [1,0,3,2]
-__device__ __forceinline__ uint32_t lat_swap(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true); }
 
 template <int DEG>
 __global__ void __launch_bounds__(LAT_THREADS)
 ldpc_lat_kernel(const LdpcKParams p)
 {
     extern __shared__ float lat_smem[];
-    if ((uint32_t)(size_t)(lat_lds_float *)lat_smem != 0u) __builtin_trap();      // LDS is addressed by plain byte offsets
+    if ((uint32_t)(size_t)(lds_float *)lat_smem != 0u) __builtin_trap();      // LDS is addressed by plain byte offsets
     constexpr int H = (DEG + 1) / 2;                       // slots of the first half-check; the second holds DEG - H
     const int L = (int)threadIdx.x, t = L >> 1, part = L & 1;
     const bool act = t < LDPC_Z;
     const uint32_t t4 = (uint32_t)(act ? t : 0) * 4u;
     const int q = p.q, N = p.N, K = p.K, M = p.M, n_info = p.n_info;
-    const lat_const_u32 tab = (lat_const_u32)p.w8.tab;
+    const const_u32 tab = (const_u32)p.w8.tab;
     const uint32_t junk = p.w8.lds_junk, inf_row = junk + (uint32_t)LAT_ROW;
     const uint32_t st0 = inf_row + (uint32_t)LAT_ROW;      // packed state: [layer][check][3] dwords
     const uint32_t flag_a = st0 + (uint32_t)M * 12u;       // one word: "some check of the sweep is unsatisfied"
@@ -65,7 +62,7 @@ ldpc_lat_kernel(const LdpcKParams p)
         bool ok = false;
         while (it < p.n_ite) {
             for (int r = 0; r < q; r++) {
-                const lat_const_u32 T = tab + r * LDPC_FAST_STRIDE;
+                const const_u32 T = tab + r * LDPC_FAST_STRIDE;
                 const uint32_t prim = T[LT_PRIM], ncf = T[LT_CINFO] & LT_CINFO_NCF_MASK;
                 // ---- this half-check's slots: posterior loads, v->c = posterior - old c->v, local minima and signs
                 const uint32_t sa = st0 + (uint32_t)(r * LDPC_Z + (act ? t : 0)) * 12u;
@@ -98,9 +95,9 @@ ldpc_lat_kernel(const LdpcKParams p)
                     sw |= (__float_as_uint(v) >> 31) << ((uint32_t)(DEG - 1) - js);
                 }
                 // ---- the two halves merge inside their lane pair
-                const float o1 = lat_swap(mn1), o2 = lat_swap(mn2);
+                const float o1 = quad_xor1(mn1), o2 = quad_xor1(mn2);
                 const float g1 = fminf(mn1, o1), g2 = fminf(fmaxf(mn1, o1), fminf(mn2, o2));
-                const uint32_t sall = sw | lat_swap(sw);
+                const uint32_t sall = sw | quad_xor1(sw);
                 const uint32_t tot = (uint32_t)(__popc(sall) & 1);
                 const float cst1 = g2 * p.alpha, cst2 = g1 * p.alpha;
                 if (ncf > 0) __syncthreads();                         // every read of the layer precedes its writes
@@ -120,7 +117,7 @@ ldpc_lat_kernel(const LdpcKParams p)
                     if (i < (int)(sizeof(delta) / sizeof(delta[0]))) delta[i] = nw - old[i];
                 }
                 // position of the minimum for the packed state: the LAST slot (in slot order) that holds min1
-                const int lo = (int)lat_swap((uint32_t)li);
+                const int lo = (int)quad_xor1((uint32_t)li);
                 const int idxn = part ? (li >= 0 ? li : lo) : (lo >= 0 ? lo : li);
                 if (act && part == 0) {
                     *lat_f(sa) = cst1; *lat_f(sa + 4u) = cst2;
@@ -148,7 +145,7 @@ ldpc_lat_kernel(const LdpcKParams p)
                 // ---- syndrome of the hard decisions: every check, both halves
                 uint32_t bad = 0u;
                 for (int r = 0; r < q; r++) {
-                    const lat_const_u32 T = tab + r * LDPC_FAST_STRIDE;
+                    const const_u32 T = tab + r * LDPC_FAST_STRIDE;
                     uint32_t xs = 0u;
 #pragma unroll
                     for (int i = 0; i < H; i++) {
@@ -160,7 +157,7 @@ ldpc_lat_kernel(const LdpcKParams p)
                         const bool absent = r == 0 && t == 0 && js == (uint32_t)(DEG - 1);
                         if (valid && !absent) xs ^= (*lat_f(a) < 0.f) ? SB : 0u;          // (the oracle's hard decision: L < 0, so -0 counts as 0)
                     }
-                    xs ^= lat_swap(xs);
+                    xs ^= quad_xor1(xs);
                     bad |= xs >> 31;
                 }
                 if (__any(bad != 0u) && (L & 63) == 0) *lat_u(flag_a) = 1u;

@@ -18,18 +18,11 @@
 #include "ldpc_dispatch.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
 #include "ldpc_det.h"
+#include "ldpc_device.h"           // const_u32, and_or, ldpc_boxplus, quad_xor1 / quad_xor2
 
 namespace dvbs2 {
 
-typedef const __attribute__((address_space(4))) uint32_t *const_u32;
 constexpr int NAT_ROW = 64 * 4;          // bytes per row: one fp32 per frame of the wave
-
-__device__ __forceinline__ float nat_and_or(uint32_t a, uint32_t m_sgpr, float b)
-{
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m_sgpr), "v"(b));
-    return r;
-}
 
 struct NatParams {
     const float *llr;          // [F][N]
@@ -114,7 +107,7 @@ ldpc_nat_kernel(const NatParams p)
 #pragma unroll
             for (int j = 0; j < DEG; j++) {
                 const float mag = (idxo == (uint32_t)j) ? c1o : c2o;
-                const float old = nat_and_or(pko << ((32u - DEG) + j), SB, mag);
+                const float old = and_or(pko << ((32u - DEG) + j), SB, mag);
                 const float x = v[j] - old;
                 v[j] = x;
                 const float a = fabsf(x);
@@ -179,15 +172,6 @@ ldpc_nat_kernel(const NatParams p)
 // to what the reference's `Decoder_LDPC_BP_horizontal_layered<.., Update_rule_SPA>` does as this library can get.  RULE 1: exact boxplus (forward / backward recursions on
 // the hardware exp2 / log2 units), every message clipped to p.spa_cap (`--dec-implem SPA`: AFF3CT's cap; SPA_EXACT: +inf): within 1e-4 max(1, |L|) of the oracle.
 // A validation mode: a frame's checks are a serial chain of memory round trips (~1 us each), so a launch wants tens of thousands of frames.
-__device__ __forceinline__ float nat_boxplus(float a, float b)
-{
-    const float e1 = __builtin_amdgcn_exp2f(-1.44269504088896341f * fabsf(a + b)), e2 = __builtin_amdgcn_exp2f(-1.44269504088896341f * fabsf(a - b));
-    const float l = (__builtin_amdgcn_logf(1.0f + e1) - __builtin_amdgcn_logf(1.0f + e2)) * 0.693147180559945309f;
-    const float mn = fminf(fabsf(a), fabsf(b));
-    const float sg = __uint_as_float((__float_as_uint(mn) & 0x7FFFFFFFu) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-    return a == INFINITY ? b : (b == INFINITY ? a : sg + l);
-}
-
 template <int DEG, int RULE>
 __global__ void __launch_bounds__(64)
 ldpc_nat_spa_kernel(const NatParams p)
@@ -245,13 +229,13 @@ ldpc_nat_spa_kernel(const NatParams p)
                 float fw[DEG], bw;
                 fw[0] = INFINITY;
 #pragma unroll
-                for (int j = 1; j < DEG; j++) fw[j] = nat_boxplus(fw[j - 1], x[j - 1]);
+                for (int j = 1; j < DEG; j++) fw[j] = ldpc_boxplus<true>(fw[j - 1], x[j - 1]);
                 bw = INFINITY;
 #pragma unroll
                 for (int j = DEG - 1; j >= 0; j--) {
-                    const float o = nat_boxplus(fw[j], bw);
+                    const float o = ldpc_boxplus<true>(fw[j], bw);
                     nw[j] = __uint_as_float((__float_as_uint(fminf(fabsf(o), p.spa_cap)) & 0x7FFFFFFFu) | (__float_as_uint(o) & 0x80000000u));
-                    bw = nat_boxplus(bw, x[j]);
+                    bw = ldpc_boxplus<true>(bw, x[j]);
                 }
             }
             if (live) {
@@ -330,8 +314,6 @@ nat_store_kernel(const NatParams p)
 // On top: check c + 1's posteriors and state are REQUESTED BEFORE check c is computed (the sweep is a chain of ~2 us memory round trips otherwise), except where the
 // host's second hazard plane says that check c + 1 shares a bit with check c or c - 1.
 // Image: [bit][G frames] rows of 4 G bytes, same row order as above.
-template <int PARTS> __device__ __forceinline__ float nat_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }     // quad_perm [1,0,3,2]
-template <int PARTS> __device__ __forceinline__ float nat_xor2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }     // quad_perm [2,3,0,1]
 template <int PARTS> __device__ __forceinline__ float nat_mir8(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)); }    // row_half_mirror: lane i <-> 7 - i
 
 // AHEAD = NAT_AHEAD (8 lanes per frame; half of it with 4): the loads of check c + AHEAD go out when check c has been computed -- only for codes whose second hazard plane is empty (no check shares a bit
@@ -423,7 +405,7 @@ ldpc_nat_part_kernel(const NatParams p)
                     float val = R.v[k];
                     if (js0 + k == DEG - 1) val = c == 0 ? INFINITY : fwd;
                     const float mag = (idxo == js) ? c1o : c2o;
-                    const float old = nat_and_or(pko << (((32u - DEG) + js) & 31u), SB, mag);
+                    const float old = and_or(pko << (((32u - DEG) + js) & 31u), SB, mag);
                     float x = val - old;
                     if (js0 + k >= DEG) x = INFINITY;                          // NULL slot of the padding
                     v[k] = x;
@@ -434,10 +416,10 @@ ldpc_nat_part_kernel(const NatParams p)
                 }
                 // ---- merge over the PARTS lanes of the frame: minima, parity, the sign word
                 uint32_t sw = sacc << (uint32_t)(DEGP - js0 - SPP);             // this part's sign bits where slot js has bit DEGP - 1 - js
-                merge_min(mn1, mn2, nat_xor1<PARTS>(mn1), nat_xor1<PARTS>(mn2));
-                sw |= __float_as_uint(nat_xor1<PARTS>(__uint_as_float(sw)));
-                merge_min(mn1, mn2, nat_xor2<PARTS>(mn1), nat_xor2<PARTS>(mn2));
-                sw |= __float_as_uint(nat_xor2<PARTS>(__uint_as_float(sw)));
+                merge_min(mn1, mn2, quad_xor1(mn1), quad_xor1(mn2));
+                sw |= __float_as_uint(quad_xor1(__uint_as_float(sw)));
+                merge_min(mn1, mn2, quad_xor2(mn1), quad_xor2(mn2));
+                sw |= __float_as_uint(quad_xor2(__uint_as_float(sw)));
                 if (PARTS == 8) {
                     merge_min(mn1, mn2, nat_mir8<PARTS>(mn1), nat_mir8<PARTS>(mn2));
                     sw |= __float_as_uint(nat_mir8<PARTS>(__uint_as_float(sw)));
@@ -476,8 +458,8 @@ ldpc_nat_part_kernel(const NatParams p)
                     uint32_t fb = 0u;
 #pragma unroll
                     for (int k = 0; k < SPP; k++) if (js0 + k == DEG - 2) fb = __float_as_uint(v[k]);
-                    fb |= __float_as_uint(nat_xor1<PARTS>(__uint_as_float(fb)));
-                    fb |= __float_as_uint(nat_xor2<PARTS>(__uint_as_float(fb)));
+                    fb |= __float_as_uint(quad_xor1(__uint_as_float(fb)));
+                    fb |= __float_as_uint(quad_xor2(__uint_as_float(fb)));
                     if (PARTS == 8) fb |= __float_as_uint(nat_mir8<PARTS>(__uint_as_float(fb)));
                     fwd = __uint_as_float(fb);
                 }
@@ -503,8 +485,8 @@ ldpc_nat_part_kernel(const NatParams p)
                     const float Lv = gldv((js0 + k == DEG - 1 && c == 0) ? inf_row + vo : a);       // (+inf: sign bit 0)
                     x ^= __float_as_uint(Lv);
                 }
-                x ^= __float_as_uint(nat_xor1<PARTS>(__uint_as_float(x)));
-                x ^= __float_as_uint(nat_xor2<PARTS>(__uint_as_float(x)));
+                x ^= __float_as_uint(quad_xor1(__uint_as_float(x)));
+                x ^= __float_as_uint(quad_xor2(__uint_as_float(x)));
                 if (PARTS == 8) x ^= __float_as_uint(nat_mir8<PARTS>(__uint_as_float(x)));
                 bad |= x >> 31;
                 if (++r2 == q) { r2 = 0; t2++; }
@@ -625,7 +607,7 @@ ldpc_nat_ck_kernel(const NatParams p)
 #pragma unroll
                 for (int j = 0; j < DEG - 1; j++) {
                     const float mag = (idxo == (uint32_t)j) ? c1o : c2o;
-                    const float old = nat_and_or(pko << ((32u - DEG) + j), SB, mag);
+                    const float old = and_or(pko << ((32u - DEG) + j), SB, mag);
                     const float x = R.v[j] - old;
                     v[j] = x;
                     const float a = fabsf(x);
@@ -633,7 +615,7 @@ ldpc_nat_ck_kernel(const NatParams p)
                     pm1 = fminf(pm1, a);
                     psacc = __builtin_amdgcn_alignbit(psacc, __float_as_uint(x), 31);
                 }
-                const float oldp = nat_and_or(pko << ((32u - DEG) + (DEG - 1)), SB, (idxo == (uint32_t)(DEG - 1)) ? c1o : c2o);
+                const float oldp = and_or(pko << ((32u - DEG) + (DEG - 1)), SB, (idxo == (uint32_t)(DEG - 1)) ? c1o : c2o);
                 const float xc = v[DEG - 2];      // p_c's edge
                 // ---- B. the chain over the eight checks of the group
                 float lout = 0.f, xl = 0.f, mn1 = 0.f, m1s = 0.f, m2s = 0.f, cst1 = 0.f, cst2 = 0.f;

@@ -29,6 +29,7 @@
 //    v_and_or / v_bitop3 with the sign mask in an SGPR, store redirection selected on the scalar unit.
 #include "dvbs2hip_internal.h"
 #include "ldpc_layer_table.h"      // the layout of the plan's tables: constants only in device code
+#include "ldpc_device.h"           // address-space typedefs, and_or, ldpc_unpack, ldpc_boxplus, LDPC_ROW, LDPC_PROF_MARK
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -38,13 +39,7 @@
 #include "ldpc_det.h"      // w8_det_tanh_half / w8_det_log1p: the tanh-product rule's two functions, correctly rounded operations only (bit for bit the oracle's)
 namespace dvbs2 {
 
-typedef __attribute__((address_space(3))) float lds_float;
-typedef __attribute__((address_space(3))) int lds_int;
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(4))) uint32_t *const_u32;
-
 constexpr int W8_NL = 9;                    // MODE 3: LDS-resident slots per layer (the first ones)
-constexpr int W8_ROW = LDPC_Z * 4;          // bytes per bit-group row
 constexpr int W8_IO = 16;                  // independent loads per lane in flight during frame I/O
 constexpr uint32_t W8_OOB = ATAB_DROPPED;    // voffset beyond every workspace: the store is dropped
 __host__ __device__ __forceinline__ constexpr bool w8_parked(int mode) { return mode == 4 || mode == 5; }      // static hybrid with rows parked in the idle waves' registers
@@ -52,95 +47,19 @@ __host__ __device__ __forceinline__ constexpr bool w8_hybrid(int mode) { return 
 // (forced: once the kernel had grown by the round-5 output loops the inliner left this one out of line -- 80 calls per layer, the launch 3.7 x as long)
 __host__ __device__ __forceinline__ constexpr bool w8_slot_lds(int mode, int j) { return mode == 0 || (mode == 3 && j < W8_NL) || (w8_parked(mode) && j < ldpc_park_nl(mode)); }
 
-// development knobs of the SPA layer (tools/build_variant.sh): suffix values kept every SPA_BS-th slot; next layer's messages
-// requested under the current layer's stores; cache policy of the message traffic
-#ifndef SPA_BS
-#define SPA_BS 3
-#endif
-#ifndef SPA_PREFETCH
-#define SPA_PREFETCH 1
-#endif
-#ifndef SPA_AUX
-#define SPA_AUX 0
-#endif
-// Cache policy of the message STORES alone.  Default: non-temporal (aux = 2) where the image does not fit LDS, i.e. for the long codes, whose message
-// store (512 x 778 KB for N = 64800) is larger than the Infinity Cache and is read back one whole iteration later -- same-box A/B 64.9 -> 61.1 ms per 16384
-// normal frames, 16.6 -> 15.0 ms per 4096; for N = 16200 (512 x 194 KB: cache-resident) the default policy is 7 % faster, and non-temporal LOADS lose on both.
-#ifndef SPA_AUX_ST
-#define SPA_AUX_ST (MODE == 0 ? SPA_AUX : 2)
-#endif
-#ifndef NMS_AUX_ST       // cache policy of the min-sum kernel's packed-state stores: 2 (non-temporal) measured 6.95 -> 8.21 ms (the 44 MB of state live in the Infinity Cache)
-#define NMS_AUX_ST 0
-#endif
-#ifndef SPA_MSG4         // 1: a lane keeps the messages of four consecutive slots as one 16-byte piece ([layer][slot / 4][360][4]); 0: [layer][slot][360]
-#define SPA_MSG4 1
-#endif
+constexpr int SPA_BS = 3;      // sum-product layer, 27 slots: suffix values kept every SPA_BS-th slot (every 2nd / every slot measured slower: docs/negative_results.md)
 #ifndef SPA_ABL          // timing-only ablations (wrong results): 1 no message stores, 2 no message loads, 4 no posterior stores to global memory, 8 no check-node arithmetic
 #define SPA_ABL 0
-#endif
-
-#ifndef W8_ATAB           // min-sum layer: the slots' addresses come from a per-lane table (L2-resident, requested behind the previous layer's last store) instead of the vector ALU
-#define W8_ATAB 1
 #endif
 #ifndef W8_ABL             // development only (wrong results): what the min-sum layer is sensitive to.  1: pass 2's global stores dropped; 2: pass 1a's global loads replaced by a
 #define W8_ABL 0           // register move; 4: pass 1b without the min / sign tracking (3 of 8.5 instructions per slot); 8: pass 2 without the compare and the two selects (3 of 5); 16 / 32: the fused chain's output phase without the packed bytes / the information bits
 #endif
-#ifndef W8_EARLY_B1        // LDS-only image: the layer's "every read precedes the writes" barrier (duplicate edges) sits right behind pass 1a -- the loads are back within ~100 cycles of the layer's
-#define W8_EARLY_B1 1      // start, when the waves have just left the end barrier together -- instead of behind pass 1b, 3000 contended cycles later (QPSK-S 8/9 +2 %, 32APSK-S 3/4 +1.3 %, 3/5 -0.5 %)
-#endif
-#ifndef W8_P2_GFIRST       // pass 2 on the hybrid images: the global slots first, the LDS slots behind them -- a wave sits out its stores' acknowledgements (s_waitcnt vmcnt(0)) in front of
-#define W8_P2_GFIRST 1     // the layer's barrier; issued first they come back under the LDS slots' work (the ablation: no global store in pass 2 is worth 11 % of the launch)
-#endif
-#ifndef W8_ABS_FOLD       // min-sum layer, pass 1b: min1 = v_min_f32(min1, |x|) with the modifier in the instruction; `fminf(m, fabsf(x))` costs a v_max_f32 |x|, |x| in front of it (IEEE
-#define W8_ABS_FOLD 1     // mode: the compiler quiets a signalling NaN first), one instruction of 17 per slot at the 4.25-cycle price (tools/probe_issue4.hip)
-#endif
-#ifndef W8_SIGN_ADD       // pass 1b: the old message's sign bit moves up by p += p (v_add_u32: 2.1 SIMD cycles) instead of a shift per slot (v_lshlrev_b32: 4.25)
-#define W8_SIGN_ADD 1
-#endif
-#ifndef W8_ATAB_HYB       // the table for the LDS slots of the hybrid images too: measured and left off (docs/negative_results.md: 2 % slower with the request in front of the global stores, 19 % behind them --
-                          // the table's loads share the fabric the image's global rows already keep 0.64 busy)
-#define W8_ATAB_HYB LDPC_ATAB_HYB      // (dvbs2hip_internal.h: the plan builds the table for the hybrid images only with this set)
-#endif
-#ifndef W8_DELTA_REG      // LDS-only image: new - old of the duplicate-edge slots kept from the passes instead of rebuilt behind the barrier
-#define W8_DELTA_REG 1
-#endif
-#ifndef W8_FAST_OUT       // output loops of their own for the bits socket alone and for the fused chain (buffer descriptors per frame, scalar descrambling)
-#define W8_FAST_OUT 1
-#endif
-// the fused chain trusts the per-frame BCH flags (dvbs2hip_api.hip: ldpc_verifies_bch), which only the run_out_fast<4|6> output loops write: a build without them would leave
-// bch_flag / cwd_bch unwritten while bch_decode_kernel skips frames on those bytes
-static_assert(W8_FAST_OUT, "W8_FAST_OUT=0 never writes bch_flag / cwd_bch, which the fused chain's BCH stage reads");
-#ifndef W8_SPA_AT16        // sum-product layer, LDS-only image, the 11- and 13-slot codes: the slots' LDS addresses come from a per-lane table of 16-bit entries (two per register) instead of
-#define W8_SPA_AT16 LDPC_SPA_AT16      // being formed on the vector ALU (4 instructions per edge, two of them with an SGPR operand); the 27-slot layer has no registers for it (dvbs2hip_internal.h)
-#endif
-#ifndef W8_SPA_ANYKEY      // sum-product layer: the overflow rule behind a wave-uniform branch per slot (k_ldpc_cu1.hip has it): same-box A/B here QPSK-S 8/9 1697 -> 1654 k,
-#define W8_SPA_ANYKEY 0      // 3/5 1178 -> 1151 k frames/s -- 27 scalar branches per layer cut the unrolled slot loop into scheduling regions; off
-#endif
-#ifndef W8_SPA_TEV        // sum-product layer: the next layer's table in one vector register (what made k_ldpc_cu1.hip's sum-product kernel 12 % faster: there the compiler had parked
-#define W8_SPA_TEV 0      // the 32 scalars in vector registers).  Here, same-box A/B: QPSK-S 8/9 1712 -> 1655 k, 3/5 1190 -> 1092 k frames/s, normal frames (mode 4) 315 -> 307 k: off
-#endif
-#ifndef W8_IN_FAST        // frame input of the information rows, LDS-only image: branch-free batches through a buffer descriptor (see there)
-#define W8_IN_FAST 1
-#endif
-#ifndef W8_OUT_BAR_LGKM   // output phase of the production forms: the barriers wait for the LDS traffic only (same-box A/B: no difference, 6.28 / 6.32 ms under the profiler)
-#define W8_OUT_BAR_LGKM 1
-#endif
-#ifndef W8_OUT_GFIRST     // ... and the rows of the workgroup's global slot are emitted before the LDS rows
-#define W8_OUT_GFIRST 1
-#endif
-#ifndef W8_KEEP_NOWAIT    // the row-keeping waves take a layer's inner barriers without draining their exchanges
-#define W8_KEEP_NOWAIT 1
-#endif
-#ifndef W8_IDX_E32        // pass 2's selects in the 32-bit encoding (inline asm): see the note there.  Measured without effect (round 4: 5.94 against 5.95 ms, same box), off
-#define W8_IDX_E32 0
-#endif
 #ifdef LDPC_PHASE_PROF
-#define PROF_MARK_(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); prof[i] += (uint32_t)(n_ - pt_); pt_ = n_; } while (0)
 #ifdef LDPC_PROF_OUT      // the six layer slots show the parts of the OUTPUT phase instead: global rows, LDS rows, the hand-over barriers, parked rows, the wave's fold, the end barrier
-#define PROF_MARK(i) do { if ((i) >= 6) PROF_MARK_(i); } while (0)
-#define PROF_MARK_O(i) PROF_MARK_(i)
+#define PROF_MARK(i) do { if ((i) >= 6) LDPC_PROF_MARK(i); } while (0)
+#define PROF_MARK_O(i) LDPC_PROF_MARK(i)
 #else
-#define PROF_MARK(i) PROF_MARK_(i)
+#define PROF_MARK(i) LDPC_PROF_MARK(i)
 #define PROF_MARK_O(i)
 #endif
 #else
@@ -151,47 +70,12 @@ static_assert(W8_FAST_OUT, "W8_FAST_OUT=0 never writes bch_flag / cwd_bch, which
 // LDS word at byte offset a of the workgroup's allocation (see the kernel's note on `smem`)
 __device__ __forceinline__ lds_float *w8_lds(uint32_t a) { return (lds_float *)(size_t)a; }
 
-// (a & m) | b in one VALU operation (the compiler emits v_and + v_or)
-__device__ __forceinline__ float and_or(uint32_t a, uint32_t m_sgpr, float b)
-{
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m_sgpr), "v"(b));
-    return r;
-}
-
 // the lane's index, re-formed where it is needed (two instructions) instead of kept in a register across the layer loop
 __device__ __forceinline__ int w8_lane_now()
 {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
-}
-
-// message on slot j from the packed per-check state: magnitude c1 at the recorded minimum, c2 elsewhere
-// (both >= 0); sign = bit (DEG-1-j) of pk.  `sb` = 0x80000000 held in an SGPR.
-template <int DEG>
-__device__ __forceinline__ float w8_unpack(float c1, float c2, uint32_t pk, uint32_t j, uint32_t sb)
-{
-    const float mag = ((pk >> 27) == j) ? c1 : c2;
-    return and_or(pk << ((32u - DEG) + j), sb, mag);
-}
-
-// exact sum-product pairing (`--dec-implem SPA`, the reference's default), as the oracle's chk_update_spa:
-//     a [+] b = sign(a) sign(b) min(|a|,|b|) + log(1 + e^-|a+b|) - log(1 + e^-|a-b|)
-// on the hardware exp2 / log2 units.  +inf is the neutral element (absent / NULL slots carry it).
-// CHECKED = false: at most one operand is +inf (regular codes: only the absent edge of lane 0 carries it), for which the
-// formula itself returns the other operand (e^-inf = 0); CHECKED = true (padded layers, several +inf slots in a row): the
-// inf - inf of two neutral elements is caught by selects.
-template <bool CHECKED>
-__device__ __forceinline__ float w8_boxplus(float a, float b)
-{
-    const float e1 = __builtin_amdgcn_exp2f(-1.44269504088896341f * fabsf(a + b)), e2 = __builtin_amdgcn_exp2f(-1.44269504088896341f * fabsf(a - b));
-    const float l = (__builtin_amdgcn_logf(1.0f + e1) - __builtin_amdgcn_logf(1.0f + e2)) * 0.693147180559945309f;
-    const float mn = fminf(fabsf(a), fabsf(b));
-    const float sg = __uint_as_float((__float_as_uint(mn) & 0x7FFFFFFFu) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-    const float r = sg + l;
-    if (!CHECKED) return r;
-    return a == INFINITY ? b : (b == INFINITY ? a : r);
 }
 
 typedef float w8_f32x32 __attribute__((ext_vector_type(32)));
@@ -237,16 +121,12 @@ __device__ __forceinline__ void w8_park_server(const LdpcKParams &p, lds_int *co
         for (int k = 0; k < NR; k++) {
             const bool sw = k < 32 ? ((mlo >> k) & 1u) != 0u : ((mhi >> (k - 32)) & 1u) != 0u;
             if (sw) {
-                const uint32_t b = (uint32_t)k * (uint32_t)W8_ROW;
+                const uint32_t b = (uint32_t)k * (uint32_t)LDPC_ROW;
                 R[k][0] = lxc(b + a0, R[k][0]); R[k][1] = lxc(b + a0 + A1, R[k][1]); R[k][2] = lxc(b + a0 + A2, R[k][2]);
             }
         }
     };
-#if W8_KEEP_NOWAIT
     auto bar_inner = [&]() __attribute__((always_inline)) { __builtin_amdgcn_s_barrier(); };      // inside a layer: no wait for the exchanges in flight (nobody looks at the rows being swapped before the layer's end barrier)
-#else
-    auto bar_inner = [&]() __attribute__((always_inline)) { __syncthreads(); };
-#endif
     auto layer_barriers = [&](int r) __attribute__((always_inline)) {              // the barriers of one min-sum layer, as the working waves take them
         const const_u32 T = tab + r * LDPC_FAST_STRIDE;
         const uint32_t cinfo = T[LT_CINFO];
@@ -300,7 +180,7 @@ __device__ __forceinline__ void w8_park_server(const LdpcKParams &p, lds_int *co
         // outputs: the parked rows go through LDS positions 0 .. NR-1 once the working waves have read the LDS rows
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < NR; k++) if (on) { const uint32_t b = (uint32_t)k * (uint32_t)W8_ROW; lst(b + a0, R[k][0]); lst(b + a0 + A1, R[k][1]); lst(b + a0 + A2, R[k][2]); }
+        for (int k = 0; k < NR; k++) if (on) { const uint32_t b = (uint32_t)k * (uint32_t)LDPC_ROW; lst(b + a0, R[k][0]); lst(b + a0 + A1, R[k][1]); lst(b + a0 + A2, R[k][2]); }
         __syncthreads();
         __syncthreads();                            // the image is reused by the next frame
         qp = s_misc[9];
@@ -384,9 +264,13 @@ ldpc_wg8_kernel(const LdpcKParams p)
     auto gst = [&](uint32_t voff, uint32_t soff, float v) __attribute__((always_inline)) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs, voff, soff, 0); };
     auto gld1 = [&](uint32_t voff, uint32_t soff) __attribute__((always_inline)) { if (W8_ABL & 2) { float r; asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(voff | 0x3F000000u)); return r; } return gld(voff, soff); };
     auto gst2 = [&](uint32_t voff, uint32_t soff, float v) __attribute__((always_inline)) { if (W8_ABL & 1) { asm volatile("" :: "v"(v), "v"(voff), "s"(soff)); return; } gst(voff, soff, v); };
-    auto mld = [&](uint32_t voff, uint32_t soff) __attribute__((always_inline)) { if (SPA_ABL & 2) return __uint_as_float(voff & 0x3F000000u); return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, SPA_AUX)); };      // SPA messages
-    auto mst = [&](uint32_t voff, uint32_t soff, float v) __attribute__((always_inline)) { if (SPA_ABL & 1) { asm volatile("" :: "v"(v)); return; } __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs, voff, soff, SPA_AUX); };
-    // SPA_MSG4: the messages of a layer as [slot / 4][360][4 slots] (the last group holds DEG mod 4 of them): a lane's messages of four consecutive slots are 16
+    auto mld = [&](uint32_t voff, uint32_t soff) __attribute__((always_inline)) { if (SPA_ABL & 2) return __uint_as_float(voff & 0x3F000000u); return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0)); };      // SPA messages
+    auto mst = [&](uint32_t voff, uint32_t soff, float v) __attribute__((always_inline)) { if (SPA_ABL & 1) { asm volatile("" :: "v"(v)); return; } __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs, voff, soff, 0); };
+    // Cache policy of the message STORES alone: non-temporal (aux = 2) where the image does not fit LDS, i.e. for the long codes, whose message
+    // store (512 x 778 KB for N = 64800) is larger than the Infinity Cache and is read back one whole iteration later -- same-box A/B 64.9 -> 61.1 ms per 16384
+    // normal frames, 16.6 -> 15.0 ms per 4096; for N = 16200 (512 x 194 KB: cache-resident) the default policy is 7 % faster, and non-temporal LOADS lose on both.
+    constexpr int SPA_AUX_ST = MODE == 0 ? 0 : 2;
+    // the messages of a layer as [slot / 4][360][4 slots] (the last group holds DEG mod 4 of them): a lane's messages of four consecutive slots are 16
     // consecutive bytes, a wave's access 1 KB -- whole lines written and read by ONE instruction instead of four 256-byte pieces of four rows
     // (the per-edge message stream, HBM by construction, is what the sum-product kernel is bound by: docs/negative_results.md's ablations).  Same bytes per layer.
     typedef uint32_t m_u32x4 __attribute__((ext_vector_type(4)));
@@ -397,27 +281,30 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
         for (int g = 0; g < MG4; g++) {
             m_u32x4 v = {0u, 0u, 0u, 0u};
-            if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b128(rs, tb * 4u, lbase + (uint32_t)g * (W8_ROW * 4u), SPA_AUX);
+            if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b128(rs, tb * 4u, lbase + (uint32_t)g * (LDPC_ROW * 4u), 0);
             dst[4 * g] = __uint_as_float(v.x); dst[4 * g + 1] = __uint_as_float(v.y); dst[4 * g + 2] = __uint_as_float(v.z); dst[4 * g + 3] = __uint_as_float(v.w);
         }
-        const uint32_t tbase = lbase + (uint32_t)MG4 * (W8_ROW * 4u);
-        if (MR == 3) { m_u32x3 v = {0u, 0u, 0u}; if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b96(rs, tb * 3u, tbase, SPA_AUX);
+        const uint32_t tbase = lbase + (uint32_t)MG4 * (LDPC_ROW * 4u);
+        if (MR == 3) { m_u32x3 v = {0u, 0u, 0u}; if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b96(rs, tb * 3u, tbase, 0);
                        dst[4 * MG4] = __uint_as_float(v.x); dst[4 * MG4 + 1] = __uint_as_float(v.y); dst[4 * MG4 + 2] = __uint_as_float(v.z); }
-        if (MR == 2) { m_u32x2 v = {0u, 0u}; if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b64(rs, tb * 2u, tbase, SPA_AUX);
+        if (MR == 2) { m_u32x2 v = {0u, 0u}; if (!(SPA_ABL & 2)) v = __builtin_amdgcn_raw_buffer_load_b64(rs, tb * 2u, tbase, 0);
                        dst[4 * MG4] = __uint_as_float(v.x); dst[4 * MG4 + 1] = __uint_as_float(v.y); }
         if (MR == 1) dst[4 * MG4] = mld(tb, tbase);
     };
     auto mone_ld = [&](uint32_t slot, uint32_t tb, uint32_t lbase) __attribute__((always_inline)) -> float {             // one message (wave-uniform slot): the duplicate edges' old values
         const uint32_t g = slot >> 2, k = slot & 3u;
-        return g < (uint32_t)MG4 ? mld(tb * 4u, lbase + g * (W8_ROW * 4u) + k * 4u) : mld(tb * (uint32_t)(MR ? MR : 1), lbase + (uint32_t)MG4 * (W8_ROW * 4u) + k * 4u);
+        return g < (uint32_t)MG4 ? mld(tb * 4u, lbase + g * (LDPC_ROW * 4u) + k * 4u) : mld(tb * (uint32_t)(MR ? MR : 1), lbase + (uint32_t)MG4 * (LDPC_ROW * 4u) + k * 4u);
     };
     auto lld = [&](uint32_t a) __attribute__((always_inline)) -> float { return *w8_lds(a); };
     auto lst = [&](uint32_t a, float v) __attribute__((always_inline)) { *w8_lds(a) = v; };
     const int nl_info = p.w8.nl_info, nl = p.w8.nl, ng_info = p.w8.ng_info, ng = p.w8.ng;
-    const uint32_t grow0 = 2u * W8_ROW;                      // global image: [junk row][+inf row][group rows ..]
+    const uint32_t grow0 = 2u * LDPC_ROW;                      // global image: [junk row][+inf row][group rows ..]
+    // min-sum layer: the slots' addresses come from a per-lane table (L2-resident, requested behind the previous layer's last store) instead of the vector ALU
     // (LDS-only image only: on the hybrid image of the normal frames the table's loads queue behind the global rows' and the kernel is 19 % SLOWER, 6.73 against 5.65 ms)
-    constexpr bool ATAB = W8_ATAB && !SPA && (MODE == 0 || (W8_ATAB_HYB && w8_hybrid(MODE)));
-    constexpr bool AT16 = W8_SPA_AT16 && SPA && MODE == 0 && DEG <= LDPC_SPA_AT16_MAXDEG;      // (the plan builds the table for exactly this case: k_ldpc.hip, LDPC_SPA_AT16)
+    constexpr bool ATAB = !SPA && MODE == 0;
+    // sum-product layer, LDS-only image, the 11- and 13-slot codes: the slots' LDS addresses come from a per-lane table of 16-bit entries (two per register) instead of
+    // being formed on the vector ALU (4 instructions per edge, two of them with an SGPR operand); the 27-slot layer has no registers for it (dvbs2hip_internal.h)
+    constexpr bool AT16 = SPA && MODE == 0 && DEG <= LDPC_SPA_AT16_MAXDEG;      // (the plan builds the table for exactly this case: k_ldpc.hip, emit_atab_spa16)
     constexpr int ND16 = (DEG + 1) / 2, NP16 = (ND16 + 3) / 4;
     const __amdgpu_buffer_rsrc_t rs_at = __builtin_amdgcn_make_buffer_rsrc((void *)((ATAB || AT16) ? p.w8.atab : (const uint32_t *)p.w8.tab), 0, ATAB ? p.q * ((DEG + 3) / 4) * (LDPC_AT_LANES * 16) : AT16 ? p.q * NP16 * (LDPC_AT_LANES * 16) : 0, 0x00020000);
     const uint32_t at_vo = (uint32_t)(role >= 0 ? t : 0) * 16u;
@@ -441,7 +328,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
         // ~10 64-bit pointers per lane that the layer loop has no registers for (they were spilled)
         // (same-box A/B of the branch-free input form below: LDS-only image 4.43 -> 4.40 ms per 16384 short frames, hybrid image 5.755 -> 5.81 ms per 4096 normal frames -- its
         // input phase is 14 % shorter there too, and the launch longer: the burst of 16 back-to-back loads lands on the fabric the CU's other workgroup is decoding through)
-        constexpr bool INF = W8_IN_FAST && MODE == 0;
+        constexpr bool INF = MODE == 0;      // frame input of the information rows, LDS-only image: branch-free batches through a buffer descriptor (see there)
         const int lio = (SPA || INF) ? w8_lane_now() : lane, tio = (SPA || INF) ? role * 64 + lio : t;
         const uint32_t tio4 = (SPA || INF) ? (uint32_t)tio * 4u : t4;
         __builtin_amdgcn_s_setprio(3);                       // frame I/O: short bursts of loads that the other workgroup's arithmetic should not delay
@@ -456,9 +343,9 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 constexpr int B = decltype(b_c)::value;
                 float v[B];
 #pragma unroll
-                for (int k = 0; k < B; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_llr, tio4, rows[rb + l0 + k] * (uint32_t)W8_ROW, 2));
+                for (int k = 0; k < B; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_llr, tio4, rows[rb + l0 + k] * (uint32_t)LDPC_ROW, 2));
 #pragma unroll
-                for (int k = 0; k < B; k++) { if (lds) lst((uint32_t)(l0 + k) * W8_ROW + tio4, v[k]); else gst(tio4, grow0 + (uint32_t)(l0 + k) * W8_ROW, v[k]); }
+                for (int k = 0; k < B; k++) { if (lds) lst((uint32_t)(l0 + k) * LDPC_ROW + tio4, v[k]); else gst(tio4, grow0 + (uint32_t)(l0 + k) * LDPC_ROW, v[k]); }
             };
             auto in_seg = [&](int rb, int n, bool lds) __attribute__((always_inline)) {
                 int l0 = 0;
@@ -478,14 +365,14 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                 for (int k = 0; k < W8_IO; k++) v[k] = __builtin_nontemporal_load(&Y[(int)rows[l0 + k < nl_info ? l0 + k : nl_info - 1] * LDPC_Z + tio]);
 #pragma unroll
-                for (int k = 0; k < W8_IO; k++) if (l0 + k < nl_info) lst((uint32_t)(l0 + k) * W8_ROW + tio4, v[k]);
+                for (int k = 0; k < W8_IO; k++) if (l0 + k < nl_info) lst((uint32_t)(l0 + k) * LDPC_ROW + tio4, v[k]);
             }
             for (int l0 = 0; l0 < ng_info; l0 += W8_IO) {
                 float v[W8_IO];
 #pragma unroll
                 for (int k = 0; k < W8_IO; k++) v[k] = __builtin_nontemporal_load(&Y[(int)rows[nl + (l0 + k < ng_info ? l0 + k : ng_info - 1)] * LDPC_Z + tio]);
 #pragma unroll
-                for (int k = 0; k < W8_IO; k++) if (l0 + k < ng_info) gst(tio4, grow0 + (uint32_t)(l0 + k) * W8_ROW, v[k]);
+                for (int k = 0; k < W8_IO; k++) if (l0 + k < ng_info) gst(tio4, grow0 + (uint32_t)(l0 + k) * LDPC_ROW, v[k]);
             }
         }
         if (role >= 0) {
@@ -517,7 +404,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
         if (act) {
             // the c->v state is NOT zeroed: a layer's state is first read one iteration after it was first written, and the
             // reads of the first iteration are replaced by zeros where they happen (nx* / dl[] below)
-            if (p.w8.pad) { if (MODE == 0) lst(ljunk + W8_ROW + t4, INFINITY); else gst(t4, W8_ROW, INFINITY); }     // what NULL slots read
+            if (p.w8.pad) { if (MODE == 0) lst(ljunk + LDPC_ROW + t4, INFINITY); else gst(t4, LDPC_ROW, INFINITY); }     // what NULL slots read
             if (AT16 && t == 0) lst(ljunk + 4u, INFINITY);      // ... through the 16-bit address table: one word inside the first 64 KB (the junk row is written at its word 0 only)
         }
         if (p.packed && (SPA ? wave == 0 && lio == 0 : threadIdx.x == 0) && (p.K & 31)) p.packed[(size_t)f * ((p.K + 31) / 32) + p.K / 32] = 0u;     // the bits behind K in the last word
@@ -534,26 +421,17 @@ ldpc_wg8_kernel(const LdpcKParams p)
         for (int j = 0; j < (SPA ? DEG : 1); j++) onx[j] = 0.f;
         // layer table of the NEXT layer, fetched under the end-of-layer barrier: 27 slots | prim | conflict info | 2 conflict entries
         uint32_t TE[32];
-        constexpr bool TEV = SPA && W8_SPA_TEV;      // sum-product kernel: the next layer's table in ONE vector register (lane j = entry j, read back with v_readlane) instead of 32 scalars carried across the layer's barriers (k_ldpc_cu1.hip: the compiler parked them in vector registers)
 #pragma unroll
-        for (int j = 0; j < 32; j++) TE[j] = TEV ? 0u : tab[j];
-        uint32_t tev = TEV ? p.w8.tab[w8_lane_now() & 31] : 0u;
+        for (int j = 0; j < 32; j++) TE[j] = tab[j];
         // (round 4) the slots' addresses of the NEXT layer, 16 bytes (four slots) per load from the per-lane table
         constexpr int NW4 = (DEG + 3) / 4;
         uint32_t w[4 * NW4];                        // (loop-carried: the addresses of the current layer until its stores have been issued, then the next layer's)
-        constexpr int AT_NS = MODE == 0 ? DEG : (MODE == 3 ? W8_NL : w8_parked(MODE) ? ldpc_park_nl(MODE) : 0);      // slots whose address the table supplies (hybrid: the LDS slots, the first ones)
         auto at_request = [&](int rl) __attribute__((always_inline)) {
             typedef uint32_t at_u32x4 __attribute__((ext_vector_type(4)));
-            typedef uint32_t at_u32x3 __attribute__((ext_vector_type(3)));
-            typedef uint32_t at_u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-            for (int g4 = 0; g4 < (AT_NS + 3) / 4; g4++) {
+            for (int g4 = 0; g4 < NW4; g4++) {
                 const uint32_t so = (uint32_t)((rl * NW4 + g4) * (LDPC_AT_LANES * 16));
-                const int left = AT_NS - 4 * g4;          // (the last piece loads only what the table supplies: the registers behind it hold global slots' offsets)
-                if (left >= 4 || MODE == 0) { const at_u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(rs_at, at_vo, so, 0); w[4 * g4] = q4.x; w[4 * g4 + 1] = q4.y; w[4 * g4 + 2] = q4.z; w[4 * g4 + 3] = q4.w; }
-                else if (left == 3) { const at_u32x3 q3 = __builtin_amdgcn_raw_buffer_load_b96(rs_at, at_vo, so, 0); w[4 * g4] = q3.x; w[4 * g4 + 1] = q3.y; w[4 * g4 + 2] = q3.z; }
-                else if (left == 2) { const at_u32x2 q2 = __builtin_amdgcn_raw_buffer_load_b64(rs_at, at_vo, so, 0); w[4 * g4] = q2.x; w[4 * g4 + 1] = q2.y; }
-                else w[4 * g4] = __builtin_amdgcn_raw_buffer_load_b32(rs_at, at_vo, so, 0);
+                const at_u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(rs_at, at_vo, so, 0); w[4 * g4] = q4.x; w[4 * g4 + 1] = q4.y; w[4 * g4 + 2] = q4.z; w[4 * g4 + 3] = q4.w;
             }
         };
 #pragma unroll
@@ -582,9 +460,8 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 const const_u32 T = tab + r * LDPC_FAST_STRIDE;
                 uint32_t E[DEG];
 #pragma unroll
-                for (int j = 0; j < DEG; j++) E[j] = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, j) : TE[j];
-                const uint32_t prim = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_PRIM) : TE[LT_PRIM], cinfo = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CINFO) : TE[LT_CINFO],
-                               ce0 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF0) : TE[LT_CONF0], ce1 = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_CONF1) : TE[LT_CONF1];
+                for (int j = 0; j < DEG; j++) E[j] = TE[j];
+                const uint32_t prim = TE[LT_PRIM], cinfo = TE[LT_CINFO], ce0 = TE[LT_CONF0], ce1 = TE[LT_CONF1];
                 const int ncf = (int)(cinfo & LT_CINFO_NCF_MASK);
                 const bool mask0 = (r == 0) && (t == 0);        // p_{c-1} of check 0 does not exist
                 if (SPA) {
@@ -599,15 +476,15 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     // magnitude so that the sum seen by the WEAKEST edge is representable; should the weakest edge itself then overflow
                     // (min2 - min1 > 60), the other edges' outputs are min1 to within e^-57.  Per edge: 1 exp + 1 rcp on the way in, 1 rcp + 1 log
                     // on the way out and ~20 full-rate operations, against 2.8 boxplus x (2 exp + 2 log + 12) of the forward / backward form.
-                    constexpr uint32_t mpitch = W8_ROW;      // message rows packed like the image's (a run-time pitch costs two scalar instructions per access; 1536-byte rows -- whole lines -- measured SLOWER, docs/negative_results.md)
+                    constexpr uint32_t mpitch = LDPC_ROW;      // message rows packed like the image's (a run-time pitch costs two scalar instructions per access; 1536-byte rows -- whole lines -- measured SLOWER, docs/negative_results.md)
                     const uint32_t mrow = st_base + (uint32_t)(r * DEG) * mpitch;       // messages of this layer: [slot][360 of mpitch / 4]
-                    const uint32_t dupmask = TEV ? (uint32_t)__builtin_amdgcn_readlane((int)tev, LT_DUPMASK) : TE[LT_DUPMASK];
+                    const uint32_t dupmask = TE[LT_DUPMASK];
                     // the circulant offsets are formed twice, for the loads and again for the stores (an opaque copy of t4 keeps the compiler
                     // from holding 27 of them across the arithmetic: registers, not instructions, are what this layer is short of)
                     uint32_t t4s = t4, MAGM = 0x7FFFFFFFu;
                     asm volatile("" : "+s"(MAGM));                // the magnitude mask as an SGPR operand (VOP3 takes no literal)
-                    auto woff = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
-                    auto woff_s = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4s - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
+                    auto woff = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW); };
+                    auto woff_s = [&](int j) __attribute__((always_inline)) { const uint32_t d = t4s - (E[j] & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW); };
                     // (round 5, LDS-only image) ... or read from the per-lane table: slot j's LDS address is one half of a register (a v_and with 0xFFFF or a shift by 16)
                     uint32_t M16 = 0xFFFFu;
                     asm volatile("" : "+v"(M16));                 // in a vector register: the plain two-register v_and_b32 issues every 2.07 cycles, with a literal 2.6, with an SGPR 4.25
@@ -641,17 +518,9 @@ ldpc_wg8_kernel(const LdpcKParams p)
                             else x[j] = w8_slot_lds(MODE, j) ? lld(wj + base) : gld(wj, base);
                         }
                         if (it > 0) {
-#if !SPA_PREFETCH
-#if SPA_MSG4
-                            mgrp_ld(onx, t4, mrow);
-#else
-#pragma unroll
-                            for (int j = 0; j < DEG; j++) onx[j] = mld(t4, mrow + (uint32_t)j * mpitch);     // old message
-#endif
-#endif
                             if (!OD_STATIC) {
 #pragma unroll
-                                for (int i = 0; i < LDPC_SPA_MAXC; i++) if (i < ncf) od[i] = SPA_MSG4 ? mone_ld(dup_slot(i), t4, mrow) : mld(t4, mrow + dup_slot(i) * mpitch);
+                                for (int i = 0; i < LDPC_SPA_MAXC; i++) if (i < ncf) od[i] = mone_ld(dup_slot(i), t4, mrow);
                             }
                         }
                         __builtin_amdgcn_s_setprio(0);
@@ -720,7 +589,6 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     if (ncf > 0) __syncthreads();         // every read of the layer precedes its writes
                     if (act) {
                         float A = 0.f;
-                        const bool anykey = __ballot(key == key) != 0ull;      // (NaN stands for "no overflow in this check")
                         float mq[4] = {0.f, 0.f, 0.f, 0.f};
                         if (DEG > 13) asm volatile("" : "+v"(t4s));      // (the short codes keep their offsets: 70 registers in all)
                         if (AT16 && DEG > 13) {      // (the halves are taken apart again for the stores: 27 addresses kept across the arithmetic do not fit)
@@ -764,13 +632,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                             // cancellation; same deviation from the oracle, 3.3e-6 max(1, |L|) at most; short frames +1.0-1.6 %, same-box A/B)
                             const float lg = (SPA_ABL & 8) ? Q : __builtin_amdgcn_logf(__builtin_fmaf(2.f, __builtin_amdgcn_rcpf(Q), -kap));
                             float o = __builtin_fmaf(lg, 0.693147180559945309f, cln);
-#if W8_SPA_ANYKEY
-                            // (round 5) the overflow rule behind a wave-uniform branch: it applies to a check whose two smallest magnitudes differ by more than 60, which no
-                            // wave of a frame near the waterfall holds; as two compares, an or and a select per slot it was 4 of the layer's ~34 vector instructions per edge
-                            if (anykey) { asm volatile("" ::: "memory"); o = __builtin_islessgreater(fabsf(x[j]), key) ? mn1 : o; }
-#else
-                            o = (fabsf(x[j]) < key || fabsf(x[j]) > key) ? mn1 : o;
-#endif
+                            o = (fabsf(x[j]) < key || fabsf(x[j]) > key) ? mn1 : o;      // (key = NaN stands for "no overflow in this check": both compares false)
                             o = fminf(o, p.spa_cap);      // (`--dec-implem SPA`: clipped where the messages of AFF3CT's tanh-product rule saturate; SPA_EXACT: +inf)
                             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(nw) : "s"(MAGM), "v"(o), "v"(sx ^ __float_as_uint(x[j])));
                             A = __builtin_fmaf(u[j], wA, A);
@@ -794,22 +656,18 @@ ldpc_wg8_kernel(const LdpcKParams p)
                                 else gst(vo, sb, x[j] + nw);
                             }
                             }
-#if SPA_MSG4
-                            mq[j & 3] = nw;                     // four slots' messages leave as one 16-byte piece (the last group: what is left)
+                            mq[j & 3] = nw;                    // four slots' messages leave as one 16-byte piece (the last group: what is left)
                             if (!(SPA_ABL & 1)) {
                                 if ((j & 3) == 3)
                                     __builtin_amdgcn_raw_buffer_store_b128(m_u32x4{__float_as_uint(mq[0]), __float_as_uint(mq[1]), __float_as_uint(mq[2]), __float_as_uint(mq[3])}, rs,
-                                                                           wide_off(t4s * 4u, mrow + (uint32_t)(j >> 2) * (W8_ROW * 4u)), 0u, SPA_AUX_ST);
+                                                                           wide_off(t4s * 4u, mrow + (uint32_t)(j >> 2) * (LDPC_ROW * 4u)), 0u, SPA_AUX_ST);
                                 else if (j == DEG - 1) {
-                                    const uint32_t tbase = mrow + (uint32_t)MG4 * (W8_ROW * 4u);
+                                    const uint32_t tbase = mrow + (uint32_t)MG4 * (LDPC_ROW * 4u);
                                     if (MR == 3) __builtin_amdgcn_raw_buffer_store_b96(m_u32x3{__float_as_uint(mq[0]), __float_as_uint(mq[1]), __float_as_uint(mq[2])}, rs, wide_off(t4s * 3u, tbase), 0u, SPA_AUX_ST);
                                     if (MR == 2) __builtin_amdgcn_raw_buffer_store_b64(m_u32x2{__float_as_uint(mq[0]), __float_as_uint(mq[1])}, rs, t4s * 2u, tbase, SPA_AUX_ST);
                                     if (MR == 1) mst(t4s, tbase, mq[0]);
                                 }
                             } else asm volatile("" :: "v"(nw));
-#else
-                            mst(t4s, mrow + (uint32_t)j * mpitch, nw);
-#endif
                             if (OD_STATIC) { if (j < LDPC_SPA_MAXC) od[j] = nw - od[j]; }
                             else if ((dupmask >> j) & 1u) {          // wave-uniform
 #pragma unroll
@@ -820,23 +678,16 @@ ldpc_wg8_kernel(const LdpcKParams p)
                             __builtin_amdgcn_sched_barrier(0);
                             at16_request(r + 1 < q ? r + 1 : 0);
                         }
-#if SPA_PREFETCH
                         // the messages of the next layer do not depend on this one: their loads (HBM misses, the message store is
                         // streamed through once per iteration) go out now and travel while this layer's stores drain at the barriers
                         __builtin_amdgcn_sched_barrier(0);      // not earlier: x[], u[], B[] have to be dead first (registers)
                         if ((it > 0 || r + 1 == q) && !(r + 1 == q && it + 1 >= p.n_ite)) {
                             const uint32_t mnext = st_base + (uint32_t)((r + 1 < q ? r + 1 : 0) * DEG) * mpitch;
-#if SPA_MSG4
                             mgrp_ld(onx, t4s, mnext);
-#else
-#pragma unroll
-                            for (int j = 0; j < DEG; j++) onx[j] = mld(t4s, mnext + (uint32_t)j * mpitch);
-#endif
                         } else {
 #pragma unroll
                             for (int j = 0; j < DEG; j++) onx[j] = 0.f;
                         }
-#endif
                         __builtin_amdgcn_s_setprio(0);
                     }
                     // duplicate edges: level by level behind a barrier, as in the min-sum layer
@@ -849,13 +700,12 @@ ldpc_wg8_kernel(const LdpcKParams p)
                         if (lvl != prev_lvl) { __syncthreads(); prev_lvl = lvl; }
                         if (act) {
                             const uint32_t d = t4 - (e & LT_SHIFT_MASK);
-                            const uint32_t off = min(d, d + (uint32_t)W8_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
+                            const uint32_t off = min(d, d + (uint32_t)LDPC_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             if (MODE != 1) { const float Lv = lld(off + base); lst(off + base, Lv + od[i]); }
                             else { const float Lv = gld(off, base); gst(off, base, Lv + od[i]); }
                         }
                     }
-                    if (TEV) tev = p.w8.tab[(r + 1 < q ? r + 1 : 0) * LDPC_FAST_STRIDE + (w8_lane_now() & 31)];
-                    else {
+                    {
                         const const_u32 Tn = tab + (r + 1 < q ? r + 1 : 0) * LDPC_FAST_STRIDE;
 #pragma unroll
                         for (int j = 0; j < 32; j++) TE[j] = Tn[j];
@@ -864,19 +714,24 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     continue;
                 }
                 float v[DEG];
-                // (LDS-only image only -- same-box A/B: short frames 4.51 -> 4.44 ms per 16384, the hybrid image of the normal frames 5.77 -> 5.85 per 4096 with them)
+                // LDS-only image: the layer's "every read precedes the writes" barrier (duplicate edges) sits right behind pass 1a -- the loads are back within ~100 cycles of the layer's
+                // start, when the waves have just left the end barrier together -- instead of behind pass 1b, 3000 contended cycles later (QPSK-S 8/9 +2 %, 32APSK-S 3/4 +1.3 %, 3/5 -0.5 %)
                 // (LDS-only image only.  On the hybrid images -- global slots' loads first, LDS slots' behind them, barrier once the LDS data are back -- it is 2.5-5.7 % SLOWER, same-box
                 // A/B 5.94-6.04 against 5.62-5.70 ms: a barrier at the layer's start keeps the waves in phase, and in-phase waves want the issue port at the same moment)
-                constexpr bool EARLY_B1 = W8_EARLY_B1 && MODE == 0;
+                constexpr bool EARLY_B1 = MODE == 0;
                 // (the early barrier is an s_barrier inside the block of the active lanes, matched by a hand-written one for the waves without checks: every WORKING wave has to have
                 //  an active lane -- a wave whose lanes are all idle would skip the block, and the barrier with it)
-                static_assert(LDPC_Z > 64 * 5 && LDPC_Z <= 64 * 6, "six working waves, the last one with active lanes (W8_EARLY_B1's barrier sits inside `if (act)`)");
-                constexpr bool ABSF = W8_ABS_FOLD && MODE == 0, SGNA = W8_SIGN_ADD && MODE == 0;
+                static_assert(LDPC_Z > 64 * 5 && LDPC_Z <= 64 * 6, "six working waves, the last one with active lanes (EARLY_B1's barrier sits inside `if (act)`)");
+                // pass 1b: ABSF: min1 = v_min_f32(min1, |x|) with the modifier in the instruction; `fminf(m, fabsf(x))` costs a v_max_f32 |x|, |x| in front of it (IEEE mode: the compiler
+                // quiets a signalling NaN first), one instruction of 17 per slot at the 4.25-cycle price (tools/probe_issue4.hip).  SGNA: the old message's sign bit moves up by p += p
+                // (v_add_u32: 2.1 SIMD cycles) instead of a shift per slot (v_lshlrev_b32: 4.25)
+                // (LDS-only image only -- same-box A/B: short frames 4.51 -> 4.44 ms per 16384, the hybrid image of the normal frames 5.77 -> 5.85 per 4096 with them)
+                constexpr bool ABSF = MODE == 0, SGNA = MODE == 0;
                 constexpr int KD = MODE == 0 ? ldpc_w8_kd(DEG) : DEG;       // LDS-only image: duplicate edges sit in slots < KD (plan), the others are primary
                 // (round 4) LDS-only image: conflict entry i is slot i < KDD (plan), so what a duplicate edge adds in the replay, new - old message, is kept from the passes
                 // (one subtraction per slot) instead of being rebuilt from the packed states behind the barrier (two unpacks = 8 vector instructions per entry on the
                 // critical path between the layer's last two barriers: the replay was 18 % of a short-frame launch).  The hybrid images have no registers for it.
-                constexpr bool DREG = W8_DELTA_REG && MODE == 0;
+                constexpr bool DREG = MODE == 0;
                 constexpr int KDD = ldpc_w8_kd(DEG);
                 float dold[KDD];
 #pragma unroll
@@ -896,16 +751,15 @@ ldpc_wg8_kernel(const LdpcKParams p)
 #pragma unroll
                     for (int j = 0; j < DEG; j++) {
                         const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
-                        if (ATAB && (MODE == 0 || w8_slot_lds(MODE, j))) {
-                            // (round 4) the address comes from the per-lane table (requested behind the previous layer's last store): an LDS slot's entry is the whole
-                            // LDS address, a global slot's the rotated offset inside its row -- no vector instruction per slot (they were 21 % of the layer's vector issue
-                            // cycles: three instructions per slot, two of them at the 4.25-cycle price of an SGPR operand, four for an LDS slot, every iteration again)
-                            if (FWD && j == DEG - 1) { if (r > 0) v[j] = pfw; else v[j] = gld1(w[j], base); }
-                            else v[j] = w8_slot_lds(MODE, j) ? lld(w[j]) : gld1(w[j], base);
+                        if (ATAB) {
+                            // (round 4) the address comes from the per-lane table (requested behind the previous layer's last store): the entry is the whole LDS
+                            // address -- no vector instruction per slot (they were 21 % of the layer's vector issue cycles: three instructions per slot, two of them
+                            // at the 4.25-cycle price of an SGPR operand, four for an LDS slot, every iteration again)
+                            v[j] = lld(w[j]);
                             continue;
                         }
                         const uint32_t d = t4 - (E[j] & LT_SHIFT_MASK);
-                        w[j] = min(d, d + (uint32_t)W8_ROW);
+                        w[j] = min(d, d + (uint32_t)LDPC_ROW);
                         if (FWD && j == DEG - 1) { if (r > 0) v[j] = pfw; else v[j] = gld1(w[j], base); }      // p_{c-1}: handed over by layer r - 1
                         else if (w8_slot_lds(MODE, j)) {
                             const uint32_t a = w[j] + base;
@@ -941,7 +795,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                             sacc = __builtin_amdgcn_alignbit(sacc, __float_as_uint(x), 31);
                         }
                     } else {
-                    uint32_t psh = pko << (32u - DEG);      // (W8_SIGN_ADD) sign bit of slot j in bit 31 at slot j
+                    uint32_t psh = pko << (32u - DEG);      // (SGNA) sign bit of slot j in bit 31 at slot j
 #pragma unroll
                     for (int j = 0; j < DEG; j++) {
                         const float mag = (idxo == (uint32_t)j) ? c1o : c2o;
@@ -973,41 +827,26 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     float m1s = __uint_as_float(__float_as_uint(cst1) | (tot << 31));        // output magnitudes carrying the total sign
                     float m2s = __uint_as_float(__float_as_uint(cst2) | (tot << 31));
                     asm volatile("" : "+v"(m1s), "+v"(m2s));      // keep the sign folded in: one select + one bit-op per edge
-                    constexpr int P2_ROT = (W8_P2_GFIRST && w8_hybrid(MODE) && !ATAB) ? (MODE == 3 ? W8_NL : ldpc_park_nl(MODE)) : 0;      // first slot of pass 2 (the first global one)
+                    // hybrid images: the global slots first, the LDS slots behind them -- a wave sits out its stores' acknowledgements (s_waitcnt vmcnt(0)) in front of the layer's
+                    // barrier; issued first they come back under the LDS slots' work (the ablation: no global store in pass 2 is worth 11 % of the launch)
+                    constexpr int P2_ROT = w8_hybrid(MODE) ? (MODE == 3 ? W8_NL : ldpc_park_nl(MODE)) : 0;      // first slot of pass 2 (the first global one)
 #pragma unroll
                     for (int jj = 0; jj < DEG; jj++) {
                         const int j = jj + P2_ROT < DEG ? jj + P2_ROT : jj + P2_ROT - DEG;
                         const float x = v[j];
-#if W8_IDX_E32
-                        // A SIMD issues a VOP3-encoded instruction every ~4.1 cycles and a VOP2 / VOPC one every ~2.1, whatever the number of waves (tools/probe_issue2.hip):
-                        // the two selects on the comparison are written so that both take the 32-bit encoding (D = vcc ? src1 : src0 with src1 a register: the test is
-                        // "not the minimum", the slot number the inline constant in src0); the compiler's form of the second one is v_cndmask_b32_e64.
-                        float mag;
-                        asm("v_cmp_neq_f32_e64 vcc, |%2|, %3\n\tv_cndmask_b32_e32 %0, %4, %5, vcc\n\tv_cndmask_b32_e32 %1, %6, %1, vcc"
-                            : "=&v"(mag), "+v"(idxn) : "v"(x), "v"(mn1), "v"(m1s), "v"(m2s), "n"(j) : "vcc");
-                        const float nw = __uint_as_float(__float_as_uint(mag) ^ (__float_as_uint(x) & SB));
-#else
                         const bool ismin = (W8_ABL & 8) ? j == 3 : fabsf(x) == mn1;
                         const float mag = ismin ? m1s : m2s;
                         const float nw = __uint_as_float(__float_as_uint(mag) ^ (__float_as_uint(x) & SB));
                         idxn = ismin ? (uint32_t)j : idxn;
                         asm("" : "+v"(idxn));                     // select now: the comparison mask dies here instead of piling up 27 SGPR pairs
-#endif
                         if (DREG && j < KDD) dold[j] = nw - dold[j];
                         const bool pr = ((prim >> j) & 1u) != 0u;                             // wave-uniform
                         const uint32_t base = (E[j] >> LT_BASE_SHIFT) & LT_BASE_MASK;
-                        if (w8_slot_lds(MODE, j) && ATAB) {      // (hybrid images: every LDS slot is covered by the table's pieces)
+                        if (ATAB) {
                             // the table's address is where the value came from; a duplicate edge's plain store (redirected to the junk row without the table) is left out
                             uint32_t a = w[j];
                             if (j == DEG - 1 && mask0) a = ljunk;
-                            if ((MODE == 0 && j >= KD) || pr) lst(a, x + nw);
-                            if (MODE != 0 && j == AT_NS - 1 && role >= 0) {
-                                // hybrid image: the next layer's LDS addresses are requested HERE, behind the last LDS slot's store and in front of the global slots' stores --
-                                // their registers are free, and the wait for them does not have to sit out the stores' acknowledgements (vmcnt counts in order)
-                                __builtin_amdgcn_sched_barrier(0);
-                                at_request(r + 1 < q ? r + 1 : 0);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
+                            if (j >= KD || pr) lst(a, x + nw);
                         } else if (w8_slot_lds(MODE, j)) {
                             uint32_t a = j >= KD ? w[j] : w[j] + (pr ? base : ljunk);
                             if (j == DEG - 1 && mask0) a = ljunk;
@@ -1024,12 +863,12 @@ ldpc_wg8_kernel(const LdpcKParams p)
                     {
                         typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
                         u32x3 sv; sv.x = __float_as_uint(cst1); sv.y = __float_as_uint(cst2); sv.z = pkn;
-                        __builtin_amdgcn_raw_buffer_store_b96(sv, rs, wide_off(t4 * 3u, st_base + (uint32_t)(r * LDPC_Z) * 12u), 0u, NMS_AUX_ST);
+                        __builtin_amdgcn_raw_buffer_store_b96(sv, rs, wide_off(t4 * 3u, st_base + (uint32_t)(r * LDPC_Z) * 12u), 0u, 0);
                     }
                     if (q == 1) { nx1 = cst1; nx2 = cst2; nxk = __uint_as_float(pkn); }
                     __builtin_amdgcn_s_setprio(MODE == 0 ? 1 : 0);
                 }
-                if (ATAB && MODE == 0 && role >= 0) {      // the next layer's addresses: requested now (this layer's stores have read theirs), they travel under the replay and the end barrier
+                if (ATAB && role >= 0) {      // the next layer's addresses: requested now (this layer's stores have read theirs), they travel under the replay and the end barrier
                     __builtin_amdgcn_sched_barrier(0);
                     at_request(r + 1 < q ? r + 1 : 0);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1038,8 +877,8 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 // ---- duplicate edges of a bit-group inside this layer: ordered delta updates, level by level.  The
                 //      first two (nearly always all of them, both of level 1) travel with the layer table.
                 if (ncf > 0) {
-                    auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)W8_ROW); };
-                    auto delta_of = [&](uint32_t j) __attribute__((always_inline)) { return w8_unpack<DEG>(cst1, cst2, pkn, j, SB) - w8_unpack<DEG>(c1o, c2o, pko, j, SB); };
+                    auto addr_of = [&](uint32_t e) __attribute__((always_inline)) { const uint32_t d = t4 - (e & LT_SHIFT_MASK); return min(d, d + (uint32_t)LDPC_ROW); };
+                    auto delta_of = [&](uint32_t j) __attribute__((always_inline)) { return ldpc_unpack<DEG>(cst1, cst2, pkn, j, SB) - ldpc_unpack<DEG>(c1o, c2o, pko, j, SB); };
                     const uint32_t j0 = (cinfo >> LT_CINFO_SLOT0_SHIFT) & LT_SLOT_MASK, j1 = (cinfo >> LT_CINFO_SLOT1_SHIFT) & LT_SLOT_MASK, lvl1 = (cinfo >> LT_CINFO_LVL1_SHIFT) & LT_LVL_MASK;
                     const bool two = ncf > 1 && lvl1 == 1u;         // entry 1 commutes with entry 0 (another bit-group)
                     // (round 4, LDS-only image) addresses and deltas of the first two entries are ready BEFORE the barrier: behind it only load, add, store remain
@@ -1117,7 +956,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                         for (int j = 0; j < DEG; j++) {
                             const uint32_t e = T[j];
                             const uint32_t d = t4 - (e & LT_SHIFT_MASK);
-                            const uint32_t wo = min(d, d + (uint32_t)W8_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
+                            const uint32_t wo = min(d, d + (uint32_t)LDPC_ROW), base = (e >> LT_BASE_SHIFT) & LT_BASE_MASK;
                             Lv[j] = w8_slot_lds(MODE, j) ? lld(wo + base) : gld(wo, base);
                         }
                         if (r == 0 && t == 0) Lv[DEG - 1] = 0.f;                               // absent edge
@@ -1196,7 +1035,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
         const uint32_t pk_vo = (role >= 0 && lo < nb_w) ? (uint32_t)(role * 8 + lo) : W8_OOB, pk_sh = (uint32_t)(lo & 3) * 8u;
         const bool pk_hi = lo >= 4;
         auto emit_plain = [&](int g, float Lv) __attribute__((always_inline)) {       // bits socket alone (dvbs2hip_ldpc_decode_siho*, the bench line)
-            __builtin_amdgcn_raw_buffer_store_b32(Lv < 0.f ? 1u : 0u, rs_bits, vo_out, (uint32_t)g * (uint32_t)W8_ROW, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(Lv < 0.f ? 1u : 0u, rs_bits, vo_out, (uint32_t)g * (uint32_t)LDPC_ROW, 2);
         };
         auto emit_chain = [&](int g, float Lv) __attribute__((always_inline)) {       // fused chain: packed hard decisions for the BCH stage + descrambled information bits as int32 (rows of information groups only)
             const unsigned long long m = __ballot(Lv < 0.f);                      // (inactive lanes hold 0.f)
@@ -1205,7 +1044,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
             uint32_t bit;
             asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(bit) : "s"(d));             // this lane's bit of the descrambled word (the 64-bit mask is the select's condition)
             // (the whole offset in the vector register: the range check that drops the bits behind K_info then sees all of it)
-            if (!(W8_ABL & 32)) __builtin_amdgcn_raw_buffer_store_b32(bit, rs_info, vo_out + (uint32_t)g * (uint32_t)W8_ROW, 0u, 2);
+            if (!(W8_ABL & 32)) __builtin_amdgcn_raw_buffer_store_b32(bit, rs_info, vo_out + (uint32_t)g * (uint32_t)LDPC_ROW, 0u, 2);
             const uint32_t half = pk_hi ? (uint32_t)(m >> 32) : (uint32_t)m;
             if (!(W8_ABL & 16)) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(half >> pk_sh), rs_pack, pk_vo, (uint32_t)g * (uint32_t)(LDPC_Z / 8), 0);
         };
@@ -1214,14 +1053,14 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 for (int l0 = 0; l0 < nl_out; l0 += W8_IO) {
                     float v[W8_IO];
 #pragma unroll
-                    for (int k = 0; k < W8_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < nl_out ? l0 + k : nl_out - 1) * W8_ROW + t4) : 0.f;
+                    for (int k = 0; k < W8_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < nl_out ? l0 + k : nl_out - 1) * LDPC_ROW + t4) : 0.f;
 #pragma unroll
                     for (int k = 0; k < W8_IO; k++) if (l0 + k < nl_out) em((int)rows[l0 + k], v[k]);
                 }
                 for (int l0 = 0; l0 < ng_out; l0 += W8_IO) {
                     float v[W8_IO];
 #pragma unroll
-                    for (int k = 0; k < W8_IO; k++) v[k] = act ? gld(t4, grow0 + (uint32_t)(l0 + k < ng_out ? l0 + k : ng_out - 1) * W8_ROW) : 0.f;
+                    for (int k = 0; k < W8_IO; k++) v[k] = act ? gld(t4, grow0 + (uint32_t)(l0 + k < ng_out ? l0 + k : ng_out - 1) * LDPC_ROW) : 0.f;
 #pragma unroll
                     for (int k = 0; k < W8_IO; k++) if (l0 + k < ng_out) em((int)rows[nl + l0 + k], v[k]);
                 }
@@ -1235,7 +1074,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 for (int l0 = 0; l0 < NRP; l0 += W8_IO) {
                     float v[W8_IO];
 #pragma unroll
-                    for (int k = 0; k < W8_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRP ? l0 + k : NRP - 1) * W8_ROW + t4) : 0.f;
+                    for (int k = 0; k < W8_IO; k++) v[k] = act ? lld((uint32_t)(l0 + k < NRP ? l0 + k : NRP - 1) * LDPC_ROW + t4) : 0.f;
 #pragma unroll
                     for (int k = 0; k < W8_IO; k++) if (l0 + k < NRP && srow[l0 + k] != ROWS_NONE) em((int)srow[l0 + k], v[k]);
                 }
@@ -1351,11 +1190,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
         };
         const uint32_t t4o = SPA ? (uint32_t)to * 4u : t4;      // (sum-product kernel: re-formed from the opaque lane index, like the frame input's -- t4 kept alive across the layer loop costs the register it does not have)
         auto out_bar = [&]() __attribute__((always_inline)) {      // a barrier of the output phase: LDS traffic only (what the row-keeping waves hand over); the stores in flight are not waited for
-#if W8_OUT_BAR_LGKM
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-            __syncthreads();
-#endif
         };
         auto run_out_fast = [&](auto nw_c) __attribute__((always_inline)) {
             constexpr int NW = decltype(nw_c)::value;                  // words of the BCH remainder: 0 (bits socket alone: no verification), 4 or 6
@@ -1374,7 +1209,7 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 constexpr int B = decltype(b_c)::value;
                 float v[B];
 #pragma unroll
-                for (int k = 0; k < B; k++) v[k] = kind == 1 ? gld(t4g, grow0 + (uint32_t)(l0 + k) * W8_ROW) : lld((uint32_t)(l0 + k) * W8_ROW + t4l);
+                for (int k = 0; k < B; k++) v[k] = kind == 1 ? gld(t4g, grow0 + (uint32_t)(l0 + k) * LDPC_ROW) : lld((uint32_t)(l0 + k) * LDPC_ROW + t4l);
                 o_u32x4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
                 uint32_t pw = 0u;
                 if (SYN) {      // the batch's records (lane l mod 16: row l) and this lane's PRBS bits of its rows
@@ -1401,17 +1236,10 @@ ldpc_wg8_kernel(const LdpcKParams p)
                 }
             };
             if (role >= 0) {
-#if W8_OUT_GFIRST
                 seg(1, ng_info);      // the global rows first: their loads are issued while nothing of this phase is in the wave's memory queue yet
                 PROF_MARK_O(0);
                 seg(0, nl_info);
                 PROF_MARK_O(1);
-#else
-                seg(0, nl_info);
-                PROF_MARK_O(1);
-                seg(1, ng_info);
-                PROF_MARK_O(0);
-#endif
             }
             if (w8_parked(MODE)) {
                 out_bar();      // every LDS row has been read
@@ -1422,13 +1250,12 @@ ldpc_wg8_kernel(const LdpcKParams p)
             }
             if constexpr (SYN) { if (role >= 0) fold_syn(nw_c); }
         };
+        // (the fused chain trusts the per-frame BCH flags (dvbs2hip_api.hip: ldpc_verifies_bch), which only the run_out_fast<4|6> output loops write)
         bool fast_out = false;
-#if W8_FAST_OUT
         if (out_plain) { run_out_fast(std::integral_constant<int, 0>{}); fast_out = true; }
         else if (out_syn && syn6) { run_out_fast(std::integral_constant<int, 6>{}); fast_out = true; }
         else if (out_syn) { run_out_fast(std::integral_constant<int, 4>{}); fast_out = true; }
         else if (out_chain) { run_out(emit_chain); fast_out = true; }
-#endif
         if (!fast_out) run_out(emit);
         PROF_MARK_O(4);
         if (first) s_misc[9] = p.cu_ctr ? (int)(atomicAdd(&p.cu_ctr[LDPC_FRAME_CTR], 1u) + gridDim.x) : qp + (int)gridDim.x;

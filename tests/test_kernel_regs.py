@@ -24,7 +24,7 @@ def test_no_kernel_spills_vector_registers():
     assert not bad, bad
     # private memory only where a kernel calls a non-inlined device function (the delay line's general walk)
     scratch = [(k["name"], k["scratch"]) for k in ks if k["scratch"] > 0]
-    # ... and a 20-byte slot the backend reserves in the LDS-only min-sum kernels since their layer loop carries the address table's 28 registers (W8_ATAB; gone with -DW8_ATAB=0):
+    # ... and a 20-byte slot the backend reserves in the LDS-only min-sum kernels since their layer loop carries the address table's 28 registers (k_ldpc_wg8.hip, ATAB):
     # no instruction of the kernels touches it -- checked here in the disassembly -- so it is a frame-size entry, not a spill
     dead = [n for n, b in scratch if "ldpc_wg8_kernel<" in n and ", 0, 0>" in n and b <= 32]
     assert all("sync_vdelay_batch_kernel" in n or n in dead for n, _ in scratch), scratch

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development: builds tools/bin/lib_<name>.so = libdvbs2hip.so with ONE translation unit recompiled with extra flags
-# (CPU container; the .so travels to the GPU box, DVBS2HIP_LIB selects it):  tools/build_variant.sh NAME k_ldpc_wg8 -DSPA_BS=2 ...
+# (CPU container; the .so travels to the GPU box, DVBS2HIP_LIB selects it):  tools/build_variant.sh NAME k_ldpc_wg8 -DW8_ABL=15 ...
 set -e
 cd "$(dirname "$0")/.."
 name=$1; tu=$2; shift 2
