@@ -1,10 +1,11 @@
 // C ABI, the pilot-aided noise estimator (k_est_pilots.hip): sigma, Eb/N0 and Es/N0 of aligned PL frames from their header and pilot symbols.  An extension with no
 // reference task; beside the M2M4 estimator (dvbs2hip_estimate, dvbs2hip_api.hip), which stays the default.  Stateless unless dvbs2hip_estimate_pilots_set_alpha > 0.
 #include "dvbs2hip_handle.h"
+#include "rx_device.h"      // the PL frame's layout: PL_M, PL_P, PL_GAP
 
 using namespace dvbs2;
 
-static int estp_known(const dvbs2hip_t *h) { return 90 + (h->pl_frame - 90 - h->n_sym); }      // L = 90 + 36 N_pilots: what a PL frame holds beside its data symbols
+static int estp_known(const dvbs2hip_t *h) { return PL_M + (h->pl_frame - PL_M - h->n_sym); }      // L = PL_M + PL_P N_pilots: what a PL frame holds beside its data symbols
 
 // X_N1 with `stride` complex samples from frame to frame (compact: the L known symbols alone), or the located table SRC
 static int estp_dev(dvbs2hip_t *h, const float *X_N1, const float *const *SRC, size_t stride, int compact, int32_t scrambled, float *SIG, float *EB, float *ES, int32_t F)
@@ -13,7 +14,7 @@ static int estp_dev(dvbs2hip_t *h, const float *X_N1, const float *const *SRC, s
     if (!X_N1 && !SRC) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     if (scrambled != 0 && scrambled != 1) return fail(h, DVBS2HIP_EINVAL, "'scrambled' has to be 0 or 1");
     const int L = estp_known(h), NS = h->bw.S;
-    if (L < 90 || L > 14 * 64) return fail(h, DVBS2HIP_EUNSUPPORTED, "the pilot-aided estimator holds at most 896 known symbols of a frame");
+    if (L < PL_M || L > 14 * 64) return fail(h, DVBS2HIP_EUNSUPPORTED, "the pilot-aided estimator holds at most 896 known symbols of a frame");
     const float alpha = h->estp.alpha;
     float *AN = nullptr;
     if (alpha > 0.f) {
@@ -56,13 +57,13 @@ int dvbs2hip_estimate_pilots(dvbs2hip_t *h, const float *X_N1, int32_t scrambled
     int r = check_frames(h, F); if (r) return r;
     if (!X_N1) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     const int L = estp_known(h);
-    if (L < 90) return fail(h, DVBS2HIP_EUNSUPPORTED, "the PL frame is shorter than its header and data symbols");
+    if (L < PL_M) return fail(h, DVBS2HIP_EUNSUPPORTED, "the PL frame is shorter than its header and data symbols");
     const size_t cb = sizeof(float) * 2, pitch = cb * (size_t)L, fpitch = cb * (size_t)h->pl_frame, nf4 = sizeof(float) * (size_t)F;
     void *sym, *out;
     if ((r = ensure(h, B_ESTP_SYM, pitch * (size_t)F, &sym)) || (r = ensure(h, B_ESTP_OUT, 3 * nf4, &out))) return r;
-    HIPCHK(h, hipMemcpy2DAsync(sym, pitch, X_N1, fpitch, cb * 90, (size_t)F, hipMemcpyHostToDevice, h->stream));
-    for (int b = 0; b < (L - 90) / 36; b++)
-        HIPCHK(h, hipMemcpy2DAsync((char *)sym + cb * (size_t)(90 + 36 * b), pitch, (const char *)X_N1 + cb * (size_t)(90 + 36 * b + 1440 * (b + 1)), fpitch, cb * 36, (size_t)F,
+    HIPCHK(h, hipMemcpy2DAsync(sym, pitch, X_N1, fpitch, cb * PL_M, (size_t)F, hipMemcpyHostToDevice, h->stream));
+    for (int b = 0; b < (L - PL_M) / PL_P; b++)
+        HIPCHK(h, hipMemcpy2DAsync((char *)sym + cb * (size_t)(PL_M + PL_P * b), pitch, (const char *)X_N1 + cb * (size_t)(PL_M + PL_P * b + PL_GAP * (b + 1)), fpitch, cb * PL_P, (size_t)F,
                                    hipMemcpyHostToDevice, h->stream));
     float *d_sig = (float *)out, *d_eb = d_sig + F, *d_es = d_sig + 2 * (size_t)F;
     if ((r = estp_dev(h, (const float *)sym, nullptr, (size_t)L, 1, scrambled, SIG ? d_sig : nullptr, EB ? d_eb : nullptr, ES ? d_es : nullptr, F))) return r;

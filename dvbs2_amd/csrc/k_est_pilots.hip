@@ -7,7 +7,7 @@
 // p[k] the known value (scrambled = 1: the pilots first PL-descrambled, the swap / sign change of pl_descramble_kernel, exact):
 //   c = (1/L) sum_k y[k] conj(p[k])      N = sum_k |y[k] - c p[k]|^2 / (L - 1)      A = |c|^2      S = A - N / L      Es_N0 = 10 log10(S / N)
 // the residual form: no small number is the difference of two large ones.  S <= 0: -100 dB; N = 0, or a ratio above 100 dB: +100 dB (an fp32 frame without noise
-// leaves N near 1e-14 A, not 0).  SIG and Eb_N0 from Es_N0 by the expressions of m2m4_finish (k_front.hip), repeated here so that that file's code stays as it is.
+// leaves N near 1e-14 A, not 0).  SIG and Eb_N0 from Es_N0 as the M2M4 estimator forms them (esn0_to_sigma_ebn0, rx_device.h).
 // The estimate is coherent over the frame: a constant phase does not move it, a residual carrier lowers S -- it belongs behind the fine synchronizers, or on a baseband
 // loop without a carrier error; removing the carrier is not this task's job.
 //
@@ -16,49 +16,22 @@
 // bpermute), so every lane ends with the same c and N.  fp32 in this order: bit-exact with nothing, held to float64 by tests/test_est_pilots_gpu.py.
 // alpha > 0 (averaging over a stream's frames): the launch leaves (A, N) per frame, est_pilots_walk_kernel takes each stream's frames in order, one lane per stream.
 #include "dvbs2hip_internal.h"
+#include "rx_device.h"
 
 namespace dvbs2 {
 
 constexpr int ESTP_WAVES = 4;                    // frames (= waves) per workgroup; the waves never meet
-constexpr int ESTP_M = 90, ESTP_P = 36, ESTP_GAP = 16 * 90;      // header, pilot block, data symbols between two pilot blocks
 
 namespace {
 
-// the value of lane (l ^ M)
-template <int M> __device__ __forceinline__ float estp_xor(float v)
-{
-    const int x = __builtin_bit_cast(int, v);
-    int r;
-    if constexpr (M == 1) r = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);            // quad_perm [1,0,3,2]
-    else if constexpr (M == 2) r = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);       // quad_perm [2,3,0,1]
-    else if constexpr (M == 8) r = __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);      // row_ror:8
-    else if constexpr (M == 4 || M == 16) r = __builtin_amdgcn_ds_swizzle(x, 0x1F | (M << 10));   // bit mode: and 0x1F, or 0, xor M, inside each half of the wave
-    else r = __builtin_amdgcn_ds_bpermute((int)((__lane_id() ^ M) << 2), x);
-    return __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float estp_wave_sum(float v)
-{
-    v = v + estp_xor<1>(v); v = v + estp_xor<2>(v); v = v + estp_xor<4>(v); v = v + estp_xor<8>(v); v = v + estp_xor<16>(v); v = v + estp_xor<32>(v);
-    return v;
-}
-
-// times conj(exp(j pi/2 R)): pl_derotate of k_front.hip (Scrambler_PL.hxx:66-76 with scr_flag = false)
-__device__ __forceinline__ float2 estp_derotate(float2 x, int R)
-{
-    const bool sw = (R & 1) != 0;
-    const float a = sw ? x.y : x.x, b = sw ? x.x : x.y;
-    return make_float2(__uint_as_float(__float_as_uint(a) ^ (((uint32_t)R << 30) & 0x80000000u)), __uint_as_float(__float_as_uint(b) ^ (((uint32_t)(R + 1) << 30) & 0x80000000u)));
-}
-
-// (A, N) -> the three outputs.  The last two lines are m2m4_finish's
+// (A, N) -> the three outputs
 __device__ __forceinline__ void estp_finish(float A, float N, float rL, float rate_bps, float &sigma, float &ebn0, float &esn0)
 {
     const float S = A - N * rL;
     esn0 = 10.f * 0.301029995663981f * __builtin_amdgcn_logf(S * __builtin_amdgcn_rcpf(N));       // 10 log10(S / N)
     if (!(S > 0.f)) esn0 = -100.f;
     else if (N == 0.f || !(esn0 < 100.f)) esn0 = 100.f;
-    sigma = __builtin_amdgcn_sqrtf(__builtin_amdgcn_rcpf(2.0f * __builtin_amdgcn_exp2f(esn0 * 0.332192809488736f)));      // sqrt(1 / (2 10^(esn0 / 10)))
-    ebn0 = esn0 - 10.f * 0.301029995663981f * __builtin_amdgcn_logf(rate_bps);
+    esn0_to_sigma_ebn0(esn0, rate_bps, sigma, ebn0);
 }
 
 }  // namespace
@@ -87,11 +60,11 @@ est_pilots_kernel(const EstpKParams p)
         const int k = lane + 64 * j;
         const bool valid = k < p.L;
         const int kk = valid ? k : 0;
-        const bool pil = kk >= ESTP_M;
-        const int pos = pil ? kk + ESTP_GAP * ((kk - ESTP_M) / ESTP_P + 1) : kk;
+        const bool pil = kk >= PL_M;
+        const int pos = pl_known_index(kk);
         float2 v = r[p.compact ? kk : pos];
-        const int R = pil && p.scrambled ? (int)p.seq[pos - ESTP_M] : 0;
-        v = estp_derotate(v, R);
+        const int R = pil && p.scrambled ? (int)p.seq[pos - PL_M] : 0;
+        v = pl_derotate(v, R);
         float2 q = make_float2(a, a);
         if (j < 2) { if (!pil) q = p.plh[kk]; }
         if (!valid) { v = make_float2(0.f, 0.f); q = v; }
@@ -100,7 +73,7 @@ est_pilots_kernel(const EstpKParams p)
         cr += v.x * q.x + v.y * q.y;
         ci += v.y * q.x - v.x * q.y;
     }
-    cr = estp_wave_sum(cr) * p.rL; ci = estp_wave_sum(ci) * p.rL;
+    cr = wave_sum(cr) * p.rL; ci = wave_sum(ci) * p.rL;
     float n = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
@@ -109,7 +82,7 @@ est_pilots_kernel(const EstpKParams p)
         const float er = y[j].x - (cr * q.x - ci * q.y), ei = y[j].y - (cr * q.y + ci * q.x);
         n += er * er + ei * ei;
     }
-    const float N = estp_wave_sum(n) * p.rL1, A = cr * cr + ci * ci;
+    const float N = wave_sum(n) * p.rL1, A = cr * cr + ci * ci;
     if (lane != 0) return;
     if (p.AN) { p.AN[2 * f] = A; p.AN[2 * f + 1] = N; return; }
     float sigma, ebn0, esn0;

@@ -16,30 +16,13 @@
 // arithmetic folded into the load and the store, and the only HBM write is the LLR frame the
 // LDPC kernel consumes.
 #include "dvbs2hip_internal.h"
+#include "rx_device.h"
 #include <cstdlib>
 
 namespace dvbs2 {
 
 constexpr int FRONT_THREADS = 256;
-constexpr int PL_M = 90, PL_P = 36, PL_SLOTS = 16;
-
-// xfec symbol k -> index of the same symbol inside the PL frame (Framer.hxx:330-343)
-__device__ __forceinline__ int pl_index(int k, int n_pilots)
-{
-    int b = k / (PL_SLOTS * PL_M);
-    b = b < n_pilots ? b : n_pilots;
-    return PL_M + k + PL_P * b;
-}
-
-// multiply by conj(exp(j pi/2 R)) (Scrambler_PL.hxx:66-76 with scr_flag = false)
-__device__ __forceinline__ float2 pl_derotate(float2 x, int R)
-{
-    // R = 0: (x, y)   1: (y, -x)   2: (-x, -y)   3: (-y, x) -- branch-free (a switch becomes four exec-masked paths per wave, every wave holds all four values):
-    // odd R swaps the parts, bit 1 of R negates the first output, bit 1 of R + 1 the second
-    const bool sw = (R & 1) != 0;
-    const float a = sw ? x.y : x.x, b = sw ? x.x : x.y;
-    return make_float2(__uint_as_float(__float_as_uint(a) ^ (((uint32_t)R << 30) & 0x80000000u)), __uint_as_float(__float_as_uint(b) ^ (((uint32_t)(R + 1) << 30) & 0x80000000u)));
-}
+// (the PL frame's layout, pl_index and pl_derotate: rx_device.h)
 
 // position of interleaved LLR i = k*bps + b in the natural (code) order
 __device__ __forceinline__ int deitl_index(int k, int b, int bps, int cols, int order, int n_rows)
@@ -68,34 +51,20 @@ __device__ __forceinline__ int deitl_index(int k, int b, int bps, int cols, int 
 // relative precision unless the whole subset lies 2^-220 below the maximum (|LLR| beyond ~150: sum < 2^-100); such a
 // symbol takes the per-subset form, every term relative to its own subset's maximum.
 // |LLR error| vs the pairwise form stays below 1e-4 * max(1, |LLR|) (tests/test_front_gpu.py).
-#ifndef FRONT_TAB_SCALAR   // 1: the general demapper takes the frame's constellation table from scalar registers (demap_symbols_s), 0: from LDS (demap_symbols)
-#define FRONT_TAB_SCALAR 1
-#endif
-#ifndef FRONT_BUF_ST
-#define FRONT_BUF_ST 1
-#endif
-#ifndef FRONT_REG_TS       // the register-resident 8PSK kernels: scalar-side table and buffer stores as in front_kernel
-#define FRONT_REG_TS 1
-#endif
-#ifndef FRONT_TAB_VGPR
-#define FRONT_TAB_VGPR 0
-#endif
-#ifndef FRONT_PK           // demap_symbols_s: two points per v_pk_fma_f32 / v_pk_add_f32
-#define FRONT_PK 1
-#endif
-#ifndef FRONT_U_APSK
-#define FRONT_U_APSK 1
-#endif
-#ifndef FRONT_ANALYTIC_REF
-#define FRONT_ANALYTIC_REF 1
-#endif
+// What the round-4 A/B runs settled (docs/negative_results.md; each was a build knob until its outcome stood): 8+ points per symbol take the frame's constellation table from
+// scalar registers (demap_symbols_s, two points per v_pk_fma_f32 / v_pk_add_f32), in the register-resident 8PSK kernels too; 1 and 2 bits per symbol keep the LDS form
+// (demap_symbols); the exponent's reference is k |y|^2, no running maximum; LLRs leave through a buffer descriptor.  A_s, B_s stay in SGPR pairs: replicated in vector
+// registers as well, 16APSK-S ran 0.102 against 0.091 ms and 32APSK-S 0.133 against 0.119 (163 VGPRs: three waves per SIMD).
 constexpr float FRONT_LOG2E = 1.44269504088896341f, FRONT_LN2 = 0.693147180559945309f;
+// Symbols a lane of front_kernel demaps per trip of its loop (= per read of the constellation table); front_dispatch cuts a frame into slices of whole trips with the same
+// number.  Two per lane for the APSK constellations: 16APSK-N 0.396 against 0.402 ms, 32APSK-S 0.179 against 0.129 (registers).
+__host__ __device__ __forceinline__ constexpr int front_syms_per_trip(int bps) { return bps <= 3 ? 4 : 1; }
 
 // per-frame table of the constellation, thread s < 2^bps:  tab[s] = c log2(e) (2 re, 2 im, -|s|^2, 0)
 __device__ __forceinline__ float4 demap_table_entry(const float *cstl, int s, float inv2s2)
 {
     const float k = inv2s2 * FRONT_LOG2E, sr = cstl[2 * s], si = cstl[2 * s + 1];
-    return make_float4(2.0f * k * sr, 2.0f * k * si, -k * (sr * sr + si * si), k);      // .w: the scale itself (FRONT_ANALYTIC_REF)
+    return make_float4(2.0f * k * sr, 2.0f * k * si, -k * (sr * sr + si * si), k);      // .w: the scale itself (the exponent's reference k |y|^2)
 }
 
 template <int BPS>
@@ -125,9 +94,6 @@ __device__ __forceinline__ void demap_symbols(const float2 (&y)[U], const float4
 {
     constexpr int P = 1 << BPS;
     float u[U][P], mx[U];
-#pragma unroll
-    for (int i = 0; i < U; i++) mx[i] = -INFINITY;
-#if FRONT_ANALYTIC_REF
     // (round 4) the reference exponent without a running maximum over the points: u_s = k (|y|^2 - |y - s|^2) <= k |y|^2, so k |y|^2 bounds every term from above
     // (v_max_f32 per point and symbol is a 4.25-cycle instruction: 32 of them were ~10 % of the 32APSK demapper's issue cycles).  The largest term is then
     // 2^(120 - k d_min^2) instead of 2^120 (d_min: distance to the nearest point, k d_min^2 a few units at the noise levels the decoder works at), the sums keep their
@@ -135,16 +101,12 @@ __device__ __forceinline__ void demap_symbols(const float2 (&y)[U], const float4
     const float kq = tab[0].w;
 #pragma unroll
     for (int i = 0; i < U; i++) mx[i] = kq * fmaf(y[i].x, y[i].x, y[i].y * y[i].y);
-#endif
 #pragma unroll
     for (int s = 0; s < P; s++) {
         if ((s & 7) == 0) asm volatile("" ::: "memory");          // at most 8 table rows in flight (registers)
         const float4 t = tab[s];
 #pragma unroll
-        for (int i = 0; i < U; i++) {
-            u[i][s] = fmaf(y[i].x, t.x, fmaf(y[i].y, t.y, t.z));
-            if (!FRONT_ANALYTIC_REF) mx[i] = fmaxf(mx[i], u[i][s]);
-        }
+        for (int i = 0; i < U; i++) u[i][s] = fmaf(y[i].x, t.x, fmaf(y[i].y, t.y, t.z));
     }
 #pragma unroll
     for (int i = 0; i < U; i++) {
@@ -187,10 +149,9 @@ __device__ __forceinline__ void demap_tab_scalar(DemapTabS<BPS> &T, const float4
     for (int s = 0; s < P; s++) {
         const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t.x), s)), b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t.y), s));
         const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t.z), s));
-        // replicated in vector registers, opaquely: left to itself the compiler keeps the lane-0 copy and re-reads all 2 P values with v_readlane in every iteration of
-        // the symbol loop (102 + 48 moves per 32APSK symbol), the operands of the packed instructions being register pairs
-        if (FRONT_TAB_VGPR) { asm volatile("v_mov_b32 %0, %1" : "=v"(T.A[s]) : "s"(a)); asm volatile("v_mov_b32 %0, %1" : "=v"(T.B[s]) : "s"(b)); }
-        else { T.A[s] = a; T.B[s] = b; }
+        T.A[s] = a; T.B[s] = b;
+        // D_s replicated in vector registers, opaquely: left to itself the compiler keeps the lane-0 copy and re-reads the values with v_readlane in every iteration of
+        // the symbol loop, the operands of the packed instructions being register pairs
         asm volatile("v_mov_b32 %0, %1" : "=v"(T.D[s]) : "s"(d));
     }
     T.k = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t.w), 0));
@@ -203,7 +164,6 @@ __device__ __forceinline__ void demap_symbols_s(const float2 (&y)[U], const Dema
 #pragma unroll
     for (int i = 0; i < U; i++) {
         const float c0 = fmaf(-T.k, fmaf(y[i].x, y[i].x, y[i].y * y[i].y), 120.0f);
-#if FRONT_PK
         const front_v2 yr = {y[i].x, y[i].x}, yi = {y[i].y, y[i].y}, cc = {c0, c0};
 #pragma unroll
         for (int s = 0; s < P; s += 2) {
@@ -211,10 +171,6 @@ __device__ __forceinline__ void demap_symbols_s(const float2 (&y)[U], const Dema
             const front_v2 e = __builtin_elementwise_fma(yr, a, __builtin_elementwise_fma(yi, b, cc)) + d;
             u[i][s] = __builtin_amdgcn_exp2f(e.x); u[i][s + 1] = __builtin_amdgcn_exp2f(e.y);
         }
-#else
-#pragma unroll
-        for (int s = 0; s < P; s++) u[i][s] = __builtin_amdgcn_exp2f(fmaf(y[i].x, T.A[s], fmaf(y[i].y, T.B[s], c0)) + T.D[s]);
-#endif
         float lo = 1.0f;
 #pragma unroll
         for (int b = 0; b < BPS; b++) {
@@ -231,6 +187,7 @@ __device__ __forceinline__ void demap_symbols_s(const float2 (&y)[U], const Dema
     }
 }
 
+// (the register-resident kernels sum both moments behind one barrier, written out in each: a shared helper did not compile to equal code)
 __device__ __forceinline__ float block_sum(float v, float *red)
 {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -256,8 +213,7 @@ __device__ __forceinline__ void m2m4_finish(float m2, float m4, int n_sym, float
     const float Ne = fabsf(m2 - Se);
     esn0 = 10.f * 0.301029995663981f * __builtin_amdgcn_logf(Se * __builtin_amdgcn_rcpf(Ne));      // 10 log10(Se / Ne); Ne = 0: +inf
     if (fabsf(esn0) == INFINITY) esn0 = 100.f;
-    sigma = __builtin_amdgcn_sqrtf(__builtin_amdgcn_rcpf(2.0f * __builtin_amdgcn_exp2f(esn0 * 0.332192809488736f)));      // sqrt(1 / (2 10^(esn0 / 10)))
-    ebn0 = esn0 - 10.f * 0.301029995663981f * __builtin_amdgcn_logf(code_rate * (float)bps);
+    esn0_to_sigma_ebn0(esn0, code_rate * (float)bps, sigma, ebn0);
 }
 
 // separable 2-bit constellation (every reference QPSK mapping): bit b is carried by one axis alone with two levels
@@ -276,7 +232,7 @@ template <int BPS, bool FROM_PL, bool DEITL>
 __global__ void __launch_bounds__(FRONT_THREADS)
 front_kernel(const FrontKParams p)
 {
-    constexpr int U = BPS <= 3 ? 4 : FRONT_U_APSK;          // symbols a lane demaps per read of the constellation table
+    constexpr int U = front_syms_per_trip(BPS);
     __shared__ float4 tab[1 << BPS];
     __shared__ float red[FRONT_THREADS / 64];
     __shared__ float s_sigma;
@@ -307,7 +263,7 @@ front_kernel(const FrontKParams p)
     const float inv2s2 = 1.0f / (2.0f * sigma * sigma);
     if (tid < (1 << BPS)) tab[tid] = demap_table_entry(p.cstl, tid, inv2s2);
     __syncthreads();
-    constexpr bool TS = FRONT_TAB_SCALAR && BPS >= 3;
+    constexpr bool TS = BPS >= 3;
     DemapTabS<TS ? BPS : 0> T;
     if constexpr (TS) demap_tab_scalar<BPS>(T, tab);
     float *llr = p.llr + (size_t)f * n_sym * BPS;
@@ -354,7 +310,7 @@ front_kernel(const FrontKParams p)
         for (int i = 0; i < U; i++) {
             const int k = k0 + i * FRONT_THREADS;
             if (k >= n_sym) continue;
-            if (FRONT_BUF_ST && st_fast) {
+            if (st_fast) {
                 // LLR b of symbol k sits at  k * kstride + boff[b]  (no interleaver: k bps + b; as many columns as bits: column (b or cols - 1 - b), row k): one vector offset
                 // per symbol, the bit's part in the instruction's scalar offset -- the generic index below costs three wave-uniform branches and a 64-bit address per LLR
 #pragma unroll
@@ -423,13 +379,13 @@ front_reg_kernel(const FrontKParams p)
         if (tid < (1 << BPS)) tab[tid] = demap_table_entry(p.cstl, tid, inv2s2);
         __syncthreads();
     }
-    constexpr bool TS = FRONT_TAB_SCALAR && FRONT_REG_TS && BPS >= 3 && !SEP;
+    constexpr bool TS = BPS >= 3 && !SEP;
     DemapTabS<TS ? BPS : 0> T;
     if constexpr (TS) demap_tab_scalar<BPS>(T, tab);
     float *llr = p.llr + (size_t)f * n_sym * BPS;
     const int n_rows = (n_sym * BPS) / (p.itl_cols > 1 ? p.itl_cols : 1);
     const bool pairs = BPS == 2 && p.itl_cols <= 1;
-    const bool st_fast = FRONT_REG_TS && !pairs && (p.itl_cols <= 1 || p.itl_cols == BPS), st_rows = p.itl_cols == BPS;
+    const bool st_fast = !pairs && (p.itl_cols <= 1 || p.itl_cols == BPS), st_rows = p.itl_cols == BPS;
     const uint32_t kstride = st_rows ? 4u : 4u * BPS;
     uint32_t boff[BPS];
 #pragma unroll
@@ -562,7 +518,7 @@ static hipError_t front_dispatch(const FrontKParams &p_in, hipStream_t s)
     p.slice_chunk = 0;
     dim3 g(p.n_frames), b(FRONT_THREADS);
     if (p.n_frames < 512) {      // fewer workgroups than the chip holds: several per frame
-        const int trip = (p.bps <= 3 ? 4 : FRONT_U_APSK) * FRONT_THREADS;      // symbols a workgroup takes per trip of its loop (front_kernel's U)
+        const int trip = front_syms_per_trip(p.bps) * FRONT_THREADS;      // symbols a workgroup takes per trip of its loop
         int slices = (p.n_sym + trip - 1) / trip;
         const int cap = 1024 / p.n_frames;
         if (slices > cap) slices = cap;

@@ -18,6 +18,7 @@
 //   6. arg max over the wave on the squared value, one square root.
 // fp32, every sum a tree of its own order: the result is held to float64 by tests/test_pls_gpu.py, bit-exact with nothing.
 #include "dvbs2hip_internal.h"
+#include "rx_device.h"
 
 namespace dvbs2 {
 
@@ -32,32 +33,19 @@ template <int N> constexpr unsigned long long pls_mask(const int (&b)[N]) { unsi
 constexpr unsigned long long PLS_SCR_M = pls_mask(PLS_SCR);
 constexpr uint32_t PLS_SOF_M = (uint32_t)pls_mask(PLS_SOF), PLS_G0_M = (uint32_t)pls_mask(PLS_G0);
 
-// the value of lane (l ^ M)
-template <int M> __device__ __forceinline__ float pls_xor(float v)
-{
-    const int x = __builtin_bit_cast(int, v);
-    int r;
-    if constexpr (M == 1) r = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);            // quad_perm [1,0,3,2]
-    else if constexpr (M == 2) r = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);       // quad_perm [2,3,0,1]
-    else if constexpr (M == 8) r = __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);      // row_ror:8
-    else if constexpr (M == 4 || M == 16) r = __builtin_amdgcn_ds_swizzle(x, 0x1F | (M << 10));   // bit mode: and 0x1F, or 0, xor M, inside each half of the wave
-    else r = __builtin_amdgcn_ds_bpermute((int)((__lane_id() ^ M) << 2), x);
-    return __builtin_bit_cast(float, r);
-}
-template <int M> __device__ __forceinline__ uint32_t pls_xor_u(uint32_t v) { return __builtin_bit_cast(uint32_t, pls_xor<M>(__builtin_bit_cast(float, v))); }
-
-template <int M> __device__ __forceinline__ void pls_sum3(float &a, float &b, float &c) { a = a + pls_xor<M>(a); b = b + pls_xor<M>(b); c = c + pls_xor<M>(c); }
+// (wave_xor<M>, the value of lane l ^ M: rx_device.h)
+template <int M> __device__ __forceinline__ void pls_sum3(float &a, float &b, float &c) { a = a + wave_xor<M>(a); b = b + wave_xor<M>(b); c = c + wave_xor<M>(c); }
 // one stage of the Hadamard transform on the lane's two complex values: the lane without bit M takes own + other, the lane with it other - own
 template <int M> __device__ __forceinline__ void pls_bfly(float (&u)[4], int lane)
 {
     const bool hi = lane & M;
 #pragma unroll
-    for (int c = 0; c < 4; c++) { const float o = pls_xor<M>(u[c]); u[c] = o + (hi ? -u[c] : u[c]); }
+    for (int c = 0; c < 4; c++) { const float o = wave_xor<M>(u[c]); u[c] = o + (hi ? -u[c] : u[c]); }
 }
 // the larger squared metric, the smaller value among equal ones
 template <int M> __device__ __forceinline__ void pls_max(float &m2, uint32_t &v)
 {
-    const float om = pls_xor<M>(m2); const uint32_t ov = pls_xor_u<M>(v);
+    const float om = wave_xor<M>(m2); const uint32_t ov = wave_xor<M>(v);
     if (om > m2 || (om == m2 && ov < v)) { m2 = om; v = ov; }
 }
 
@@ -82,7 +70,7 @@ pls_decode_kernel(const float2 *__restrict__ x, const float2 *const *__restrict_
     const float dsg = (PLS_SCR_M >> lane) & 1ull ? -1.f : 1.f;
     const float dre = dsg * (odd ? q.y - q.x : q.x + q.y), dim = dsg * (odd ? -q.x - q.y : q.y - q.x);
     // even lane 2i: d[2i] + d[2i+1]; odd lane 2i+1: d[2i] - d[2i+1]
-    float zre = pls_xor<1>(dre) + (odd ? -dre : dre), zim = pls_xor<1>(dim) + (odd ? -dim : dim);
+    float zre = wave_xor<1>(dre) + (odd ? -dre : dre), zim = wave_xor<1>(dim) + (odd ? -dim : dim);
     // lane 32 p + i takes z_p[i] from lane 2 i + p
     const int from = ((lane & 31) << 1 | lane >> 5) << 2;
     zre = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, zre)));

@@ -243,12 +243,7 @@ __device__ __forceinline__ void sy_wave_umax4(uint32_t &a, uint32_t &b, uint32_t
 // Every workgroup leaves its key of every frame in keys[frame][workgroup] (plain stores: agent-scope atomics on one word per frame from 521
 // workgroups were what this kernel waited for); sync_finalize_kernel takes their maximum.  A frame without a value above 0 gets key 0.
 constexpr int SYM_UF = 24;
-#ifndef SYNC_ARGMAX10      // 1: the ten-wave form of the average / arg max stage (loaders, chain, arg-max waves), 0: the four-wave form of round 3
-#define SYNC_ARGMAX10 1
-#endif
-#ifndef SYNC_UF96_MAX_WG
-#define SYNC_UF96_MAX_WG 256
-#endif
+constexpr int SYNC_UF96_MAX_WG = 256;      // calls with at most this many workgroups (one per CU) take the thirteen-wave form below, longer frames the four-wave form of round 3
 __device__ __forceinline__ void sy_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __global__ void __launch_bounds__(256)
@@ -343,9 +338,7 @@ sync_metric_argmax4_kernel(float *__restrict__ cv, const float *__restrict__ cor
 //     the wave-wide DPP ladders.
 // Same operations in the same order per position: al * c, om * m, their sum, each rounded once.  Used when the call has few positions (one workgroup per CU at
 // most: 100 KB of LDS); long frames, where the stage is bound by its 4 bytes per sample anyway, keep the four-wave form.
-#ifndef SYM_NC             // chain waves per workgroup (1, 2 or 4: 64 / NC positions each; measured 47.8 / 49.8 / 52.1 us -- an LDS piece does not get cheaper with fewer active lanes)
-#define SYM_NC 1
-#endif
+constexpr int SYM_NC = 1;  // chain waves per workgroup (1, 2 or 4: 64 / NC positions each; measured 47.8 / 49.8 / 52.1 us -- an LDS piece does not get cheaper with fewer active lanes)
 #ifndef SYM_ABL            // timing-only ablations (wrong results): 1 no loads, 2 no arg max, 4 no chain arithmetic
 #define SYM_ABL 0
 #endif
@@ -419,7 +412,7 @@ sync_metric_argmax_kernel(float *__restrict__ cv, const float *__restrict__ corr
     typedef float sy_f4 __attribute__((ext_vector_type(4)));
     typedef uint32_t sy_u4 __attribute__((ext_vector_type(4)));
     if (wv < NC) {
-        // ---- chain (NC = 1: one wave; the split over NC waves of 64 / NC positions each is kept as a knob, it measured slower)
+        // ---- chain (NC = 1: one wave; the split over NC waves of 64 / NC positions each measured slower)
         __builtin_amdgcn_s_setprio(3);
         const int pc = (64 / NC) * wv + (lane & (64 / NC - 1)), ic = blockIdx.x * 64 + pc;
         const bool mine = lane < 64 / NC, actc = ic < n;
@@ -1178,7 +1171,7 @@ static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, fl
     // few positions (short frames): the thirteen-wave form, one workgroup per CU at most; long frames: round 3's four-wave form (the stage is bound by its 4 bytes per
     // sample there: QPSK-N 1024 frames 42-45 us in the four-wave form, 65 us in this one)
     static const bool four = getenv("DVBS2HIP_SYNC_ARGMAX4") != nullptr;      // development: round 3's kernel for every frame length
-    if (SYNC_ARGMAX10 && !four && nwg <= SYNC_UF96_MAX_WG) {
+    if (!four && nwg <= SYNC_UF96_MAX_WG) {
         // segments of the call's frames side by side while they fit the chip (one workgroup per CU) and stay long enough to be worth a seam (>= 768 frames each)
         static const int cap = getenv("DVBS2HIP_SYNC_SEGMENTS") ? atoi(getenv("DVBS2HIP_SYNC_SEGMENTS")) : SYNC_MAX_SEG;      // (development: 1 = the single walk)
         int nseg = cap <= 1 || !t.seg ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);

@@ -8,6 +8,8 @@
 // given payloads and sigma = 0 (tests/test_tx_gpu.py).  Noise: Philox4x32-10 + Box-Muller,
 // counter = (symbol, frame, stream), so results do not depend on the launch geometry.
 #include "dvbs2hip_internal.h"
+#include "rx_device.h"
+#include "tx_encoders.h"
 
 namespace dvbs2 {
 
@@ -50,156 +52,48 @@ tx_src_kernel(const TxKParams p)
 }
 
 // ---------------------------------------------------------------- BCH parity (Encoder_BCH_DVBS2.cpp:28-43)
-// The systematic encoder is a polynomial division: parity = (u(x) x^r) mod g(x), serial along the frame.  The division is
-// linear, so the frame is cut into TX_BCH_SEG consecutive segments, one LANE each (a frame per 16 lanes): the lane divides
-// its segment a byte per step through a 256-entry table of (v(x) x^r) mod g(x) held in LDS (r = N - K <= 192 parity bits
-// in three 64-bit words), moves its remainder to the segment's place -- times x^(8 * bytes behind the segment) mod g, a
-// linear map applied bit by bit from a host-made table of x^(b + 8 after_s) mod g -- and the 16 remainders are XORed.
-// (One lane per whole frame, the first version, left 4096 lanes with 7184 dependent steps each: 0.90 ms of the 2.36 ms TX.)
+// The segmented division: tx_bch_remainder (tx_encoders.h).  Lane seg == 0 of a frame appends the parity at bit K of the packed frame.
 __global__ void __launch_bounds__(64)
 tx_bchpar_kernel(const TxKParams p)
 {
     __shared__ unsigned long long T[256][3];
     __shared__ uint8_t brev[256];
-    for (int i = threadIdx.x; i < 256; i += 64) {
-        T[i][0] = p.bch_tab[3 * i]; T[i][1] = p.bch_tab[3 * i + 1]; T[i][2] = p.bch_tab[3 * i + 2];
-        uint32_t r = 0; for (int b = 0; b < 8; b++) if (i >> b & 1) r |= 1u << (7 - b);
-        brev[i] = (uint8_t)r;
-    }
-    __syncthreads();
-    const int seg = threadIdx.x & (TX_BCH_SEG - 1);
-    const int f = blockIdx.x * (64 / TX_BCH_SEG) + (threadIdx.x / TX_BCH_SEG);
-    const bool live = f < p.n_frames;
+    const TxBchRem R = tx_bch_remainder(p, T, brev);
+    if (!R.live || R.seg != 0) return;
     const int K = p.K_bch, r = p.K_ldpc - p.K_bch;
     const int nw_out = (p.K_ldpc + 31) / 32;
-    uint32_t *cw = p.bch_cw + (size_t)(live ? f : 0) * nw_out;
-    unsigned long long s0 = 0, s1 = 0, s2 = 0;
-    const int tw = (r - 8) >> 6, ts = (r - 8) & 63;            // where the top byte of the remainder sits
-    const unsigned long long m1 = r >= 128 ? ~0ull : r > 64 ? (1ull << (r - 64)) - 1ull : 0ull;
-    const unsigned long long m2 = r >= 192 ? ~0ull : r > 128 ? (1ull << (r - 128)) - 1ull : 0ull;
-    const int nbytes = K / 8, L = (nbytes + TX_BCH_SEG - 1) / TX_BCH_SEG;
-    const int b0 = min(seg * L, nbytes), b1 = min(b0 + L, nbytes);
-    if (live && b1 > b0) {
-        // the message words of the segment, 8 at a time and one batch ahead: the division is a dependent chain (table look-up
-        // -> XOR -> next look-up) and must not also wait for a global load every four bytes
-        constexpr int WB = 8;
-        const int w0 = b0 >> 2, w1 = (b1 - 1) >> 2;           // first / last word touched
-        uint32_t nxt[WB];
-#pragma unroll
-        for (int k = 0; k < WB; k++) nxt[k] = cw[min(w0 + k, w1)];
-        for (int wb = w0; wb <= w1; wb += WB) {
-            uint32_t cur[WB];
-#pragma unroll
-            for (int k = 0; k < WB; k++) cur[k] = nxt[k];
-#pragma unroll
-            for (int k = 0; k < WB; k++) nxt[k] = cw[min(wb + WB + k, w1)];
-#pragma unroll
-            for (int k = 0; k < WB; k++) {
-#pragma unroll
-                for (int bb = 0; bb < 4; bb++) {
-                    const int by = 4 * (wb + k) + bb;
-                    if (by < b0 || by >= b1) continue;
-                    const uint32_t raw = (cur[k] >> (bb * 8)) & 0xFFu;
-                    const uint32_t top = (uint32_t)((tw == 0 ? s0 : tw == 1 ? s1 : s2) >> ts) & 0xFFu;
-                    const uint32_t idx = top ^ brev[raw];
-                    s2 = ((s2 << 8) | (s1 >> 56)) & m2; s1 = ((s1 << 8) | (s0 >> 56)) & m1; s0 <<= 8;
-                    if (r <= 64) s0 &= (r == 64 ? ~0ull : (1ull << r) - 1ull);
-                    s0 ^= T[idx][0]; s1 ^= T[idx][1]; s2 ^= T[idx][2];
-                }
-            }
-        }
-    }
-    // to the segment's place: sum over the set bits b of the remainder of x^(b + 8 (nbytes - b1)) mod g
-    if (b1 < nbytes) {
-        const unsigned long long *P = p.bch_shift + (size_t)seg * r * 3;
-        unsigned long long a0 = 0, a1 = 0, a2 = 0;
-        for (int b0 = 0; b0 < r; b0 += 8) {               // r is a multiple of 8 (m t, m = 14 or 16); 24 table loads in flight
-            unsigned long long q0[8], q1[8], q2[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) { q0[k] = P[3 * (b0 + k)]; q1[k] = P[3 * (b0 + k) + 1]; q2[k] = P[3 * (b0 + k) + 2]; }
-            const unsigned long long sw = b0 < 64 ? s0 >> b0 : b0 < 128 ? s1 >> (b0 - 64) : s2 >> (b0 - 128);      // 8 bits of the remainder (b0 is a multiple of 8)
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const unsigned long long m = 0ull - ((sw >> k) & 1ull);
-                a0 ^= q0[k] & m; a1 ^= q1[k] & m; a2 ^= q2[k] & m;
-            }
-        }
-        s0 = a0; s1 = a1; s2 = a2;
-    }
-    for (int o = TX_BCH_SEG / 2; o > 0; o >>= 1) { s0 ^= __shfl_xor(s0, o); s1 ^= __shfl_xor(s1, o); s2 ^= __shfl_xor(s2, o); }
-    if (!live || seg != 0) return;
-    // parity, coefficient of x^(r-1) first (DVB-S2 order), appended at bit K of the packed frame
+    uint32_t *cw = p.bch_cw + (size_t)R.f * nw_out;
     uint32_t outw = (K & 31) ? cw[K >> 5] : 0u;
     for (int j = 0; j < r; j++) {
-        const int d = r - 1 - j, k = K + j;
-        const uint32_t b = d < 64 ? (uint32_t)(s0 >> d) & 1u : d < 128 ? (uint32_t)(s1 >> (d - 64)) & 1u : (uint32_t)(s2 >> (d - 128)) & 1u;
-        outw |= b << (k & 31);
+        const int k = K + j;
+        outw |= tx_bch_parity_bit(R, r, j) << (k & 31);
         if ((k & 31) == 31) { cw[k >> 5] = outw; outw = 0; }
     }
     if ((p.K_ldpc & 31) != 0) cw[nw_out - 1] = outw;
 }
 
 // ---------------------------------------------------------------- LDPC IRA encoder (ETSI EN 302 307 5.3.2)
-// One workgroup per frame.  parity accumulator address (a + m q) mod M <=> check (r, t): the same circulant structure the decoder
-// uses, i.e. accumulator row r (its 360 bits t) = XOR over the row's edges (bit-group g, shift t0) of bit-group g ROTATED by t0.
-// Rows are 12 packed words: a lane forms one word of one row, an edge costs it two funnel shifts out of the packed info bits (the
-// wrap of the 360-bit circle splits a window in two) instead of 32 single-bit gathers -- 1 / 16 of the instructions of one lane per check.
-// Then p_c ^= p_{c-1} over c = q t + r: a running XOR of the rows (prefix over r inside a column) and an exclusive prefix over t of
-// the column totals, both on packed words.
-constexpr int ENC_W = (LDPC_Z + 31) / 32;                            // 12 words per 360-bit row, the last one holds 8 bits
-__device__ __forceinline__ uint32_t enc_window(const uint32_t *info, int pos)      // 32 bits of the packed info from bit `pos` on
-{
-    return __funnelshift_r(info[pos >> 5], info[(pos >> 5) + 1], pos & 31);
-}
+// One workgroup per frame: the packed information bits and the layer table into LDS, tx_ldpc_rows (tx_encoders.h) forms the parity rows and the column prefix there, and a
+// lane packs one word of the code word.
 __global__ void __launch_bounds__(LDPC_THREADS)
 tx_ldpc_kernel(const TxKParams p)
 {
     extern __shared__ uint32_t sm[];
-    const int K = p.K_ldpc, M = p.N_ldpc - p.K_ldpc, q = M / LDPC_Z;
+    const int K = p.K_ldpc, q = (p.N_ldpc - p.K_ldpc) / LDPC_Z;
     const int nw_in = (K + 31) / 32, nw_out = (p.N_ldpc + 31) / 32;
-    uint32_t *info = sm;                                     // nw_in words + one of padding (a window may start in the last word)
-    uint32_t *prow = sm + nw_in + 1;                         // [r][ENC_W] packed parity rows
-    uint32_t *excl = prow + q * ENC_W;                       // ENC_W words: exclusive prefix over t of the column totals
-    uint32_t *tab = excl + ENC_W;                            // the layer table (t0 | group << 9 per entry): no global round trip per entry
+    const TxLdpcLds L = tx_ldpc_lds(sm, p);
     const int t = threadIdx.x, f = blockIdx.x;
-    for (int w = t; w < q * p.enc_stride; w += LDPC_THREADS) tab[w] = p.enc_tab[w];
+    for (int w = t; w < q * p.enc_stride; w += LDPC_THREADS) L.tab[w] = p.enc_tab[w];
     const uint32_t *src = p.bch_cw + (size_t)f * nw_in;
-    for (int w = t; w <= nw_in; w += LDPC_THREADS) info[w] = w < nw_in ? src[w] : 0u;
+    for (int w = t; w <= nw_in; w += LDPC_THREADS) L.info[w] = w < nw_in ? src[w] : 0u;
     __syncthreads();
-    for (int task = t; task < q * ENC_W; task += LDPC_THREADS) {
-        const int r = task / ENC_W, l = task - r * ENC_W;
-        const int deg = p.enc_deg[r];
-        const uint32_t *T = tab + r * p.enc_stride;
-        uint32_t acc = 0u;
-#pragma unroll 4
-        for (int j = 0; j < deg; j++) {
-            const uint32_t e = T[j];                                  // t0 | group << 9
-            int m0 = 32 * l - (int)(e & 0x1FFu); m0 += m0 < 0 ? LDPC_Z : 0;      // source index of the word's first bit: (32 l - t0) mod 360
-            const int base = (int)(e >> 9) * LDPC_Z, n1 = LDPC_Z - m0;              // n1 bits are left before the circle wraps
-            uint32_t w = enc_window(info, base + m0);
-            if (n1 < 32) w = (w & ((1u << n1) - 1u)) | (enc_window(info, base) << n1);
-            acc ^= w;
-        }
-        prow[task] = l == ENC_W - 1 ? acc & ((1u << (LDPC_Z - 32 * (ENC_W - 1))) - 1u) : acc;
-    }
-    __syncthreads();
-    if (t < ENC_W) {
-        // prefix over r inside every column (12 lanes, one word of every row each), then the exclusive prefix over t of the column totals
-        uint32_t x = 0u;
-        for (int r = 0; r < q; r++) { x ^= prow[r * ENC_W + t]; prow[r * ENC_W + t] = x; }
-        uint32_t incl = x;
-        incl ^= incl << 1; incl ^= incl << 2; incl ^= incl << 4; incl ^= incl << 8; incl ^= incl << 16;      // inclusive prefix XOR inside the word
-        uint32_t par = incl >> 31;                                    // parity of the whole word (full words only matter: the last one has no successor)
-        uint32_t carry = 0u;
-        for (int l = 0; l < ENC_W; l++) { const uint32_t pl = (uint32_t)__shfl((int)par, l); if (l < t) carry ^= pl; }
-        excl[t] = (incl << 1) ^ (carry ? 0xFFFFFFFFu : 0u);
-    }
+    tx_ldpc_rows(p, L, t);
     __syncthreads();
     uint32_t *dst = p.ldpc_cw + (size_t)f * nw_out;
     for (int w = t; w < nw_out; w += LDPC_THREADS) {
         uint32_t word = 0;
         const int i0 = 32 * w;
-        if (i0 + 32 <= K) word = info[w];                     // systematic part, word-aligned
+        if (i0 + 32 <= K) word = L.info[w];                   // systematic part, word-aligned
         else {
             // parity bit c = i - K sits at (r = c mod q, tt = c / q): stepped, one division per word
             int c = i0 >= K ? i0 - K : 0, tt = c / q, r = c - tt * q;
@@ -207,8 +101,8 @@ tx_ldpc_kernel(const TxKParams p)
                 const int i = i0 + b;
                 if (i >= p.N_ldpc) break;
                 uint32_t bit;
-                if (i < K) bit = (info[i >> 5] >> (i & 31)) & 1u;
-                else { bit = ((prow[r * ENC_W + (tt >> 5)] ^ excl[tt >> 5]) >> (tt & 31)) & 1u; if (++r == q) { r = 0; tt++; } }
+                if (i < K) bit = (L.info[i >> 5] >> (i & 31)) & 1u;
+                else { bit = tx_ldpc_parity_bit(L, r, tt); if (++r == q) { r = 0; tt++; } }
                 word |= bit << b;
             }
         }
@@ -229,9 +123,9 @@ __device__ __forceinline__ float2 tx_symbol(const TxKParams &p, const float *cs,
     // right value selected at the end) -- a wave nearly always holds one kind only, but every branch costs the scalar unit a
     // save / restore of the execution mask, and there were seventy of those per pair of symbols.
     // inverse of the RX map: position i-90 inside [16 slots data | 36 pilots] blocks
-    const int j = i >= 90 ? i - 90 : 0, blk = j / (1440 + 36), off = j - blk * (1440 + 36);
-    const bool pilot = blk < n_pil && off >= 1440;
-    int k = blk < n_pil ? blk * 1440 + off : n_pil * 1440 + (j - n_pil * (1440 + 36));
+    const int j = i >= PL_M ? i - PL_M : 0, blk = j / (PL_GAP + PL_P), off = j - blk * (PL_GAP + PL_P);
+    const bool pilot = blk < n_pil && off >= PL_GAP;
+    int k = blk < n_pil ? blk * PL_GAP + off : n_pil * PL_GAP + (j - n_pil * (PL_GAP + PL_P));
     float2 y;
     if (BPS > 0) {
         k = pilot ? 0 : k;                                           // (any valid symbol: its value is not used)
@@ -262,9 +156,9 @@ __device__ __forceinline__ float2 tx_symbol(const TxKParams &p, const float *cs,
     const int R = p.pl_seq[j] & 3;
     const float a = (R & 1) ? -y.y : y.x, b = (R & 1) ? y.x : y.y;
     y = (R & 2) ? make_float2(-a, -b) : make_float2(a, b);
-    const int ih = i < 90 ? i : 0;
+    const int ih = i < PL_M ? i : 0;
     const float2 h = make_float2(p.plh[2 * ih], p.plh[2 * ih + 1]);   // the PL header is neither scrambled nor modulated here
-    return i < 90 ? h : y;
+    return i < PL_M ? h : y;
 }
 
 constexpr int TX_MOD_U = 4;                               // pairs of PL symbols per lane (independent: their loads overlap)
@@ -276,7 +170,7 @@ tx_mod_kernel(const TxKParams p)
     const int f = blockIdx.y;
     if (threadIdx.x < (2 << p.bps)) cs[threadIdx.x] = p.cstl[threadIdx.x];
     __syncthreads();
-    const int n_pil = p.n_sym / 1440;
+    const int n_pil = p.n_sym / PL_GAP;
     const uint32_t *cw = p.ldpc_cw + (size_t)f * ((p.N_ldpc + 31) / 32);
     const float sg = p.sigma ? p.sigma[f] : 0.f;
 #pragma unroll
@@ -333,9 +227,7 @@ hipError_t tx_launch(const TxKParams &p, hipStream_t s)
     hipLaunchKernelGGL(tx_bchpar_kernel, dim3((p.n_frames + 64 / TX_BCH_SEG - 1) / (64 / TX_BCH_SEG)), dim3(64), 0, s, p);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const size_t q_enc = (size_t)((p.N_ldpc - p.K_ldpc) / LDPC_Z);
-    const size_t lds = ((size_t)((p.K_ldpc + 31) / 32) + 1 + (q_enc + 1) * ((LDPC_Z + 31) / 32) + q_enc * p.enc_stride) * 4;      // info (+1) | rows | prefix | table
-    hipLaunchKernelGGL(tx_ldpc_kernel, dim3(p.n_frames), dim3(LDPC_THREADS), lds, s, p);
+    hipLaunchKernelGGL(tx_ldpc_kernel, dim3(p.n_frames), dim3(LDPC_THREADS), tx_ldpc_lds_bytes(p), s, p);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const dim3 g(((p.pl_frame + 1) / 2 + 256 * TX_MOD_U - 1) / (256 * TX_MOD_U), p.n_frames), b(256);

@@ -4,11 +4,12 @@
 //   Encoder_BCH_DVBS2::encode (Encoder_BCH_DVBS2.cpp:28-43) -> LDPC encode (DVBS2.cpp:427) -> Interleaver::interleave (DVBS2.cpp:451-476)
 //   -> Modem::modulate (Modem_generic) -> Framer::generate (Framer.hxx:232-293) -> Scrambler_PL::scramble (Scrambler_PL.hxx:61-78)
 // (Scrambler_BB::scramble is the XOR of its inverse: bb_descramble_kernel, k_front.hip).  The arithmetic is the fused TX mirror's (k_tx.hip; the
-// encoders' is restated in tx_encoders.h, a duplicate of that file's two kernel bodies); what is new is the socket form.  Every task is a streaming pass: the input is read once, the output written once,
+// encoders' is tx_encoders.h, which both files call); what is new is the socket form.  Every task is a streaming pass: the input is read once, the output written once,
 // 16 bytes per lane where the socket's address and the frame size allow it (`vec`, decided by the launcher for the whole grid) and 4 / 8 bytes per
 // access otherwise.  Two input sides are 4-byte loads whatever the alignment: the interleaver's gather (a lane's four bits lie in different columns) and the
 // modulator's bits (2 bps of them per lane, 16-byte aligned only for bps 2 and 4); their stores are 16 bytes.  Grids as the stand-alone front-end kernels of k_front.hip: 256 lanes per workgroup along the frame, the frame in blockIdx.y.
 #include "dvbs2hip_internal.h"
+#include "rx_device.h"
 #include "tx_encoders.h"
 
 namespace dvbs2 {
@@ -62,7 +63,7 @@ __device__ __forceinline__ uint32_t txt_pack256(txt_i4 b, int lane)
 
 // ---------------------------------------------------------------- BCH encode, 1 of 2: U_K -> X_N[0 .. K) and the packed message
 // One wave per 256 message bits: the systematic part goes out as it came in, and the packed copy (ceil(K_ldpc / 32) words per frame, zero behind bit
-// K: the layout tx_bch_parity divides) is the 32nd part of it on top.
+// K: the layout tx_bch_remainder divides) is the 32nd part of it on top.
 __global__ void __launch_bounds__(256)
 txt_bch_pack_kernel(const int32_t *__restrict__ U, int32_t *__restrict__ X, uint32_t *__restrict__ packed, int K, int N, int vin, int vout)
 {
@@ -81,7 +82,12 @@ txt_bchpar_kernel(const TxKParams p, int32_t *X)
 {
     __shared__ unsigned long long T[256][3];
     __shared__ uint8_t brev[256];
-    tx_bch_parity(p, T, brev, X);
+    const TxBchRem R = tx_bch_remainder(p, T, brev);
+    // the 16 lanes of a frame write parity bit j = seg, seg + 16, .. , one int32 per bit, to X[f][K .. K + r) of a socket with K_ldpc elements per frame
+    if (!R.live) return;
+    const int r = p.K_ldpc - p.K_bch;
+    int32_t *o = X + (size_t)R.f * p.K_ldpc + p.K_bch;
+    for (int j = R.seg; j < r; j += TX_BCH_SEG) o[j] = (int32_t)tx_bch_parity_bit(R, r, j);
 }
 hipError_t tx_bch_encode_launch(const TxKParams &p, const int32_t *U, int32_t *X, hipStream_t s)
 {
@@ -222,11 +228,11 @@ hipError_t tx_modulate_launch(const int32_t *X, float *Y, const float *cstl, int
 // PL frame = 90 header symbols | [16 slots of data | 36 pilots] x n_pil | the remaining data.  A lane writes a pair of PL symbols.  `vec` (the
 // launcher: both frame sizes even, both sockets 16-byte aligned): 90, 1440 and 36 are even, so a pair never straddles two kinds and its two data symbols are
 // neighbours in the XFEC frame -- one 16-byte load, one 16-byte store.
-__device__ __forceinline__ int txt_pl_source(int i, int n_pil, bool &pilot)      // PL symbol i >= 90 -> XFEC symbol (inverse of k_front.hip's pl_index)
+__device__ __forceinline__ int txt_pl_source(int i, int n_pil, bool &pilot)      // PL symbol i >= 90 -> XFEC symbol (inverse of pl_index, rx_device.h)
 {
-    const int j = i - 90, blk = j / (1440 + 36), off = j - blk * (1440 + 36);
-    pilot = blk < n_pil && off >= 1440;
-    return blk < n_pil ? blk * 1440 + off : n_pil * 1440 + (j - n_pil * (1440 + 36));
+    const int j = i - PL_M, blk = j / (PL_GAP + PL_P), off = j - blk * (PL_GAP + PL_P);
+    pilot = blk < n_pil && off >= PL_GAP;
+    return blk < n_pil ? blk * PL_GAP + off : n_pil * PL_GAP + (j - n_pil * (PL_GAP + PL_P));
 }
 __global__ void __launch_bounds__(256)
 txt_framer_kernel(const float *__restrict__ X, float *__restrict__ Y, const float *__restrict__ plh, int n_sym, int pl_frame, int vec)
@@ -236,12 +242,12 @@ txt_framer_kernel(const float *__restrict__ X, float *__restrict__ Y, const floa
     if (i0 >= pl_frame) return;
     const float2 *src = reinterpret_cast<const float2 *>(X + (size_t)f * 2 * n_sym);
     float2 *out = reinterpret_cast<float2 *>(Y + (size_t)f * 2 * pl_frame) + i0;
-    const int n_pil = n_sym / 1440;                                               // the count dvbs2hip_create sizes pl_frame with (DVBS2.cpp:351-355): a block follows the last 16 slots too when n_sym is a multiple of 1440
+    const int n_pil = n_sym / PL_GAP;                                               // the count dvbs2hip_create sizes pl_frame with (DVBS2.cpp:351-355): a block follows the last 16 slots too when n_sym is a multiple of 1440
     const float2 pil = make_float2(0.70710678118654752440f, 0.70710678118654752440f);     // Framer.hxx:252-260
     if (vec) {
         float4 y;
         bool pilot = false;
-        if (i0 < 90) y = *reinterpret_cast<const float4 *>(plh + 2 * i0);
+        if (i0 < PL_M) y = *reinterpret_cast<const float4 *>(plh + 2 * i0);
         else {
             const int k = txt_pl_source(i0, n_pil, pilot);
             y = pilot ? make_float4(pil.x, pil.y, pil.x, pil.y) : *reinterpret_cast<const float4 *>(src + k);
@@ -252,7 +258,7 @@ txt_framer_kernel(const float *__restrict__ X, float *__restrict__ Y, const floa
     for (int u = 0; u < 2 && i0 + u < pl_frame; u++) {
         const int i = i0 + u;
         float2 y;
-        if (i < 90) y = make_float2(plh[2 * i], plh[2 * i + 1]);
+        if (i < PL_M) y = make_float2(plh[2 * i], plh[2 * i + 1]);
         else {
             bool pilot;
             const int k = txt_pl_source(i, n_pil, pilot);
@@ -286,14 +292,14 @@ txt_pl_scramble_kernel(const float *__restrict__ X, float *__restrict__ Y, const
     if (vec) {                                                                      // pl_frame is even: the pair is whole
         const float4 v = *reinterpret_cast<const float4 *>(src);
         float2 y0 = make_float2(v.x, v.y), y1 = make_float2(v.z, v.w);
-        if (i0 >= 90) { y0 = txt_rotate(y0, seq[i0 - 90] & 3); y1 = txt_rotate(y1, seq[i0 - 89] & 3); }       // (90 is even: header or data, both)
+        if (i0 >= PL_M) { y0 = txt_rotate(y0, seq[i0 - PL_M] & 3); y1 = txt_rotate(y1, seq[i0 + 1 - PL_M] & 3); }       // (90 is even: header or data, both)
         *reinterpret_cast<float4 *>(out) = make_float4(y0.x, y0.y, y1.x, y1.y);
         return;
     }
     for (int u = 0; u < 2 && i0 + u < pl_frame; u++) {
         const int i = i0 + u;
         float2 y = src[u];
-        if (i >= 90) y = txt_rotate(y, seq[i - 90] & 3);
+        if (i >= PL_M) y = txt_rotate(y, seq[i - PL_M] & 3);
         out[u] = y;
     }
 }

@@ -1,7 +1,7 @@
-// The arithmetic of the two TX encoders as device functions for the task-boundary kernels (k_tx_tasks.hip: one int32 per bit in the sockets).
-// It DUPLICATES the bodies of tx_bchpar_kernel and tx_ldpc_kernel in k_tx.hip (packed bits in, packed bits out), which does not include this header:
-// a change to the division or to the parity rows has to be made in both places.  tests/test_tx_tasks_gpu.py holds the two to the same oracle and to each other.
-// Device code only.
+// The arithmetic of the two TX encoders as device functions: the BCH division and the LDPC parity rows, once, for the fused TX mirror (k_tx.hip: packed bits in,
+// packed bits out) and for the task-boundary kernels (k_tx_tasks.hip: one int32 per bit in the sockets).  What differs between the two is how the bits arrive and leave,
+// and that stays with the kernels.  tests/test_tx_gpu.py and tests/test_tx_tasks_gpu.py hold both forms to the same oracle and to each other.
+// Device code, and tx_ldpc_lds_bytes, the launchers' size of the LDS that tx_ldpc_lds lays out.
 #pragma once
 #include "dvbs2hip_internal.h"
 
@@ -14,9 +14,10 @@ namespace dvbs2 {
 // in three 64-bit words), moves its remainder to the segment's place -- times x^(8 * bytes behind the segment) mod g, a
 // linear map applied bit by bit from a host-made table of x^(b + 8 after_s) mod g -- and the 16 remainders are XORed.
 // (One lane per whole frame, the first version, left 4096 lanes with 7184 dependent steps each: 0.90 ms of the 2.36 ms TX.)
-// One wave of 64 lanes = 64 / TX_BCH_SEG frames; T and brev are the workgroup's LDS tables.  The message is read from the packed frame p.bch_cw, which is
-// only read; the parity goes, one int32 per bit, to sock[f][K .. K + r) of a socket with K_ldpc elements per frame.
-__device__ __forceinline__ void tx_bch_parity(const TxKParams &p, unsigned long long (*T)[3], uint8_t *brev, int32_t *sock)
+// One wave of 64 lanes = 64 / TX_BCH_SEG frames; T and brev are the workgroup's LDS tables.  The message is read from the packed frame p.bch_cw, which this
+// function only reads.  Behind the butterfly every lane of frame f holds the whole remainder (s0, s1, s2: coefficient of x^d at bit d); live: the frame exists.
+struct TxBchRem { unsigned long long s0, s1, s2; int seg, f; bool live; };
+__device__ __forceinline__ TxBchRem tx_bch_remainder(const TxKParams &p, unsigned long long (*T)[3], uint8_t *brev)
 {
     for (int i = threadIdx.x; i < 256; i += 64) {
         T[i][0] = p.bch_tab[3 * i]; T[i][1] = p.bch_tab[3 * i + 1]; T[i][2] = p.bch_tab[3 * i + 2];
@@ -84,14 +85,13 @@ __device__ __forceinline__ void tx_bch_parity(const TxKParams &p, unsigned long 
         s0 = a0; s1 = a1; s2 = a2;
     }
     for (int o = TX_BCH_SEG / 2; o > 0; o >>= 1) { s0 ^= __shfl_xor(s0, o); s1 ^= __shfl_xor(s1, o); s2 ^= __shfl_xor(s2, o); }
-    // every lane of the frame holds the whole remainder behind the butterfly: the 16 of them write parity bit j = seg, seg + 16, ..
-    // (coefficient of x^(r-1) first, DVB-S2 order)
-    if (!live) return;
-    int32_t *o = sock + (size_t)f * p.K_ldpc + K;
-    for (int j = seg; j < r; j += TX_BCH_SEG) {
-        const int d = r - 1 - j;
-        o[j] = (int32_t)(d < 64 ? (uint32_t)(s0 >> d) & 1u : d < 128 ? (uint32_t)(s1 >> (d - 64)) & 1u : (uint32_t)(s2 >> (d - 128)) & 1u);
-    }
+    return TxBchRem{s0, s1, s2, seg, f, live};
+}
+// parity bit j of r (coefficient of x^(r-1) first, DVB-S2 order)
+__device__ __forceinline__ uint32_t tx_bch_parity_bit(const TxBchRem &R, int r, int j)
+{
+    const int d = r - 1 - j;
+    return d < 64 ? (uint32_t)(R.s0 >> d) & 1u : d < 128 ? (uint32_t)(R.s1 >> (d - 64)) & 1u : (uint32_t)(R.s2 >> (d - 128)) & 1u;
 }
 
 // ---------------------------------------------------------------- LDPC IRA encoder (ETSI EN 302 307 5.3.2)
@@ -122,7 +122,7 @@ __device__ __forceinline__ TxLdpcLds tx_ldpc_lds(uint32_t *sm, const TxKParams &
 inline size_t tx_ldpc_lds_bytes(const TxKParams &p)                  // info (+1) | rows | prefix | table
 {
     const size_t q_enc = (size_t)((p.N_ldpc - p.K_ldpc) / LDPC_Z);
-    return ((size_t)((p.K_ldpc + 31) / 32) + 1 + (q_enc + 1) * ((LDPC_Z + 31) / 32) + q_enc * p.enc_stride) * 4;
+    return ((size_t)((p.K_ldpc + 31) / 32) + 1 + (q_enc + 1) * ENC_W + q_enc * p.enc_stride) * 4;
 }
 // from the packed info bits in s.info and the table in s.tab (both complete: the caller has synchronised) to the parity rows and the column prefix;
 // the caller synchronises again before it reads them

@@ -21,7 +21,7 @@ TASKS = ["bb_scramble", "bch_encode", "ldpc_encode", "interleave", "modulate", "
 # what a task that is not a pure streaming pass waits for (printed for the tasks whose ratio to the copy-rate time is above 2)
 WAITS = {
     "bb_scramble": "4 bytes per lane in and out (the kernel dvbs2hip_bb_descramble uses, unchanged): the memory pipeline's request rate, not its bandwidth.",
-    "bch_encode": "the parity launch: a dependent chain of LDS table look-ups, a byte of the message per step and 16 lanes per frame (tx_bch_parity) -- latency of the division, "
+    "bch_encode": "the parity launch: a dependent chain of LDS table look-ups, a byte of the message per step and 16 lanes per frame (tx_bch_remainder) -- latency of the division, "
                   "as in the fused TX's tx_bchpar_kernel; the pack-and-copy launch in front of it is a streaming pass.",
     "ldpc_encode": "one 6-wave workgroup per frame with three barriers: packing into LDS, the parity rows (funnel shifts out of LDS) and the output are phases that do not overlap inside a "
                    "workgroup, and the output phase takes one bit per LDS read; the loads of a frame are not in flight while its rows are formed.",

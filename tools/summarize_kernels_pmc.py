@@ -41,7 +41,7 @@ for d in ("pk_fetch", "pk_write", "pk_sq1", "pk_sq2", "pk_sq3"):
         k = short(r["Kernel_Name"])
         if any(w in k for w in want):
             pmc[(k, r["Grid_Size"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
-STAMPED = ("k_front.hip", "k_bch.hip", "k_sync.hip", "k_sync_mfma.hip", "k_fir.hip", "k_fir_mfma.hip", "k_tx.hip")
+STAMPED = ("k_front.hip", "k_bch.hip", "k_sync.hip", "k_sync_mfma.hip", "k_fir.hip", "k_fir_mfma.hip", "k_tx.hip", "rx_device.h", "tx_encoders.h")      # the last two: device code that k_front / k_tx include
 
 
 def sources_sha():
