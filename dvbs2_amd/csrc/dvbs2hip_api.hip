@@ -253,6 +253,7 @@ int dvbs2hip_reset(dvbs2hip_t *h)
     int r = dvbs2hip_filter_reset(h);
     if (r) return r;
     if ((r = dvbs2hip_estimate_pilots_reset(h))) return r;
+    if ((r = dvbs2hip_bbframe_reset(h))) return r;
     return dvbs2hip_monitor_reset(h);
 }
 

@@ -107,6 +107,15 @@ struct dvbs2hip_handle {
     int lr_timeouts = 0;               // launches whose rotation had to be repeated (dvbs2hip_sync_lr_timeouts)
     // pilot-aided noise estimator (api_est_pilots.hip): the averaging factor and, once a call has run with alpha > 0, {Abar, Nbar, started} per stream (n_alloc streams)
     struct { float alpha = 0.f; float *st = nullptr; int n_alloc = 0; } estp;
+    // BBFRAME layer (api_bbframe.hip): the parameters, and once a call has run the two tasks' states (ping-pong) and the five counters, one allocation: a reset is one memset
+    struct {
+        int matype1 = 0xF2, matype2 = 0, upl_bits = 1504, sync = 0x47, mark_tei = 0;
+        void *all = nullptr;
+        size_t bytes = 0;
+        dvbs2::PingPong<int32_t> tx;
+        dvbs2::PingPong<uint8_t> rx;
+        unsigned long long *ctr = nullptr;
+    } bbf;
     // L&R, recurrence and rotation in one launch (k_sync.hip, sff_lr_fused_kernel): the error word a rotating workgroup sets when it gives up waiting for the
     // recurrence -- host-mapped memory, so the host reads it at its synchronisation points without a copy
     // (round 5) every outstanding L&R call has its OWN error word and its OWN estimate buffer (LR_SLOTS in rotation): a later L&R or pilot-phase call
@@ -195,7 +204,8 @@ inline int fail(dvbs2hip_t *h, int code, const std::string &msg)
 
 enum BufId { B_IN = 0, B_OUT, B_AUX0, B_AUX1, B_AUX2, B_AUX3, B_LLR, B_PACKED, B_EST, B_CWD0, B_CWD1, B_INFO, B_SIG, B_TXBCH, B_TXLDPC,
              B_SFM_CORR, B_SFM_MET, B_SFM_SOF, B_SFM_PLSC, B_SFM_DLY, B_SFM_DTAB, B_SFF_TMP, B_SFF_OUT, B_FLT2, B_MON_BE, B_MON_OUT, B_BCHFLAG, B_ORDER, B_LR_TMP0, B_LR_TMP1, B_LR_TMP2, B_LR_TMP3, B_SFM_SCR, B_SFM_NEED,
-             B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY, B_SMF_DEL, B_SMF_FRQ, B_PLS_HDR, B_PLS_OUT, B_ESTP_SYM, B_ESTP_OUT, B_ESTP_AN };
+             B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY, B_SMF_DEL, B_SMF_FRQ, B_PLS_HDR, B_PLS_OUT, B_ESTP_SYM, B_ESTP_OUT, B_ESTP_AN,
+             B_BBF_UP, B_BBF_STAT, B_BBF_NOUT, B_BBF_HDR, B_BBF_HDRW, B_BBF_PLAN, B_BBF_VALID };
 
 inline int ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
 {

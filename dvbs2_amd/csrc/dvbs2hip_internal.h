@@ -325,6 +325,24 @@ hipError_t est_pilots_launch(const float *X, const float *const *SRC, size_t str
                              float code_rate, int bps, float *AN, float *SIG, float *EB, float *ES, int F, hipStream_t s);
 hipError_t est_pilots_walk_launch(const float *AN, float *state, float alpha, int L, float code_rate, int bps, float *SIG, float *EB, float *ES, int Fs, int S, hipStream_t s);
 
+// ---------------------------------------------------------------- BBFRAME layer (k_bbframe.hip)
+struct BbfParams {
+    int32_t K;               // K_bch
+    int32_t uplb;            // user packet length in bytes
+    int32_t sync;            // the packets' sync byte
+    int32_t matype;          // MATYPE-1 << 8 | MATYPE-2
+    int32_t mark_tei;        // a transport packet with a wrong CRC-8 gets its transport_error_indicator set
+};
+// the states between calls, all zero = reset.  Transmitter, four int32: {pos, the CRC-8 running over the current packet, the CRC-8 of the last complete packet, 0}.
+// Receiver: four int32 {have, bytes of the pending packet, 0, 0}, then the pending packet's bytes
+constexpr int BBF_TX_STATE = 16, BBF_RX_HEAD = 16;
+// U: F frames of K int32 bits (16-byte aligned) from the next n_bytes bytes of the packet stream, (F - 1) D < n_bytes <= F D with D = (K - 80) / 8
+hipError_t bbframe_build_launch(const uint8_t *UP, long long n_bytes, int32_t *U, const int32_t *st_in, int32_t *st_out, const BbfParams &p, int F, hipStream_t s);
+// V: F descrambled frames (16-byte aligned); VALID, HDR may be null; hdr: 8 F int32 and plan: 4 F int32 of workspace (16-byte aligned); UP, STATUS: room for `cap` packets;
+// ctr: the five counters of dvbs2hip_bbframe_get_stats.  Three launches
+hipError_t bbframe_parse_launch(const int32_t *V, const int8_t *VALID, int32_t *hdr, int32_t *HDR, int32_t *plan, const uint8_t *st_in, uint8_t *st_out, uint8_t *UP,
+                                uint8_t *STATUS, int32_t *N_OUT, unsigned long long *ctr, const BbfParams &p, int cap, int F, hipStream_t s);
+
 // ---------------------------------------------------------------- symbol-timing recovery and the channel's delay tasks (k_timing.hip)
 // one stream's state of Synchronizer_Gardner_fast_osf2 between calls (all zeros = _reset): the Farrow history x[n-1], x[n-2], x[n-3], the TED buffer {T0, T1}, mu (the Farrow
 // taps follow from it), the NCO, the loop filter, the last symbol, the strobe flags

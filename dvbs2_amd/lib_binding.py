@@ -84,6 +84,16 @@ ABI = {
     "dvbs2hip_estimate_pilots_located_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
     "dvbs2hip_estimate_pilots_set_alpha": (C.c_int, [_vp, _f]),
     "dvbs2hip_estimate_pilots_reset": (C.c_int, [_vp]),
+    "dvbs2hip_bbframe_set_params": (C.c_int, [_vp, _i, _i, _i, _i, _i]),
+    "dvbs2hip_bbframe_reset": (C.c_int, [_vp]),
+    "dvbs2hip_bbframe_get_stats": (C.c_int, [_vp, _vp]),
+    "dvbs2hip_bbframe_max_packets": (C.c_int, [_vp, _i, C.POINTER(C.c_int32)]),
+    "dvbs2hip_bbframe_build": (C.c_int, [_vp, _vp, C.c_int64, _vp, _i]),
+    "dvbs2hip_bbframe_build_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, _i]),
+    "dvbs2hip_bbframe_parse": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_bbframe_parse_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_rx_bb_up": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_rx_bb_up_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_sync_frame_get_metric": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "dvbs2hip_set_ldpc_params": (C.c_int, [_vp, _i, _f, _i]),
     "dvbs2hip_get_stream": (_vp, [_vp]),

@@ -668,6 +668,68 @@ class Dvbs2Hip:
     def estimate_pilots_reset(self):
         self._chk(self.L.dvbs2hip_estimate_pilots_reset(self.h))
 
+    # ------------------------------------------------------------------ BBFRAME layer (an extension: include/dvbs2hip.h)
+    def bbframe_set_params(self, matype1=0xF2, matype2=0, upl_bits=1504, sync=0x47, mark_tei=False):
+        """the BBHEADER's fixed fields and the user packet length; resets both tasks"""
+        self._chk(self.L.dvbs2hip_bbframe_set_params(self.h, int(matype1), int(matype2), int(upl_bits), int(sync), 1 if mark_tei else 0))
+        self.uplb = int(upl_bits) // 8
+
+    def bbframe_reset(self):
+        self._chk(self.L.dvbs2hip_bbframe_reset(self.h))
+
+    def bbframe_stats(self):
+        """-> {frames_taken, frames_dropped, packets_ok, packets_bad, bytes_discarded} since the last reset"""
+        out = np.zeros(5, dtype=np.uint64)
+        self._chk(self.L.dvbs2hip_bbframe_get_stats(self.h, _ptr(out)))
+        return dict(zip(("frames_taken", "frames_dropped", "packets_ok", "packets_bad", "bytes_discarded"), (int(v) for v in out)))
+
+    def bbframe_max_packets(self, n_frames) -> int:
+        cap = C.c_int32()
+        self._chk(self.L.dvbs2hip_bbframe_max_packets(self.h, int(n_frames), C.byref(cap)))
+        return cap.value
+
+    def bbframe_build(self, stream, n_frames):
+        """the next bytes of the packet stream (uint8, more than n_frames - 1 and at most n_frames data fields) -> BBFRAMEs int32[n_frames, K_bch], not yet scrambled"""
+        s = np.ascontiguousarray(stream, dtype=np.uint8).ravel()
+        U = np.empty((int(n_frames), self.K_bch), dtype=np.int32)
+        self._chk(self.L.dvbs2hip_bbframe_build(self.h, _ptr(s), s.size, _ptr(U), int(n_frames)))
+        return U
+
+    def bbframe_build_dev(self, UP, n_bytes, U_K, n_frames):
+        self._chk(self.L.dvbs2hip_bbframe_build_dev(self.h, _ptr(UP), int(n_bytes), _ptr(U_K), n_frames))
+
+    def _bbframe_out(self, F):
+        cap = self.bbframe_max_packets(F)
+        return np.empty((cap, getattr(self, "uplb", 188)), np.uint8), np.empty(cap, np.uint8), np.zeros(1, np.int32), np.empty((F, 8), np.int32)
+
+    def bbframe_parse(self, bits, valid=None):
+        """descrambled frames int32[F, K_bch] (valid: int8[F], 0 = do not trust the frame) -> (packets uint8[n, UPLB], status uint8[n], hdr int32[F, 8])"""
+        V, F = self._frames(bits, self.K_bch, np.int32)
+        va = None if valid is None else np.ascontiguousarray(valid, dtype=np.int8).ravel()
+        if va is not None and va.size != F:
+            raise ValueError("valid holds %d flags for %d frames" % (va.size, F))
+        UP, ST, n, HDR = self._bbframe_out(F)
+        self._chk(self.L.dvbs2hip_bbframe_parse(self.h, _ptr(V), _ptr(va), _ptr(UP), _ptr(ST), _ptr(n), _ptr(HDR), F))
+        return UP[:n[0]], ST[:n[0]], HDR
+
+    def bbframe_parse_dev(self, V_K, VALID, UP, STATUS, N_OUT, HDR, n_frames):
+        """device addresses (VALID, HDR may be None), stream-ordered; UP and STATUS hold bbframe_max_packets(n_frames) packets"""
+        self._chk(self.L.dvbs2hip_bbframe_parse_dev(self.h, _ptr(V_K), _ptr(VALID), _ptr(UP), _ptr(STATUS), _ptr(N_OUT), _ptr(HDR), n_frames))
+
+    def rx_bb_up(self, pl_frames, sigma=None):
+        """the fused chain and the BBFRAME parser in one call -> (packets uint8[n, UPLB], status uint8[n], hdr int32[F, 8], cwd_ldpc int8[F], cwd_bch int8[F])"""
+        X, F = self._frames(pl_frames, 2 * self.pl_frame, np.float32)
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float32).ravel(), (F,)))
+        UP, ST, n, HDR = self._bbframe_out(F)
+        c0, c1 = np.zeros(F, dtype=np.int8), np.zeros(F, dtype=np.int8)
+        self._chk(self.L.dvbs2hip_rx_bb_up(self.h, _ptr(X), _ptr(sg), _ptr(UP), _ptr(ST), _ptr(n), _ptr(HDR), _ptr(c0), _ptr(c1), F))
+        return UP[:n[0]], ST[:n[0]], HDR, c0, c1
+
+    def rx_bb_up_dev(self, pl_frames, sigma, UP, STATUS, N_OUT, HDR, cwd_ldpc, cwd_bch, n_frames):
+        self._chk(self.L.dvbs2hip_rx_bb_up_dev(self.h, _ptr(pl_frames), _ptr(sigma), _ptr(UP), _ptr(STATUS), _ptr(N_OUT), _ptr(HDR), _ptr(cwd_ldpc), _ptr(cwd_bch), n_frames))
+
     def set_filter_kernel(self, kernel):
         """B.FIR_AUTO (default: matrix cores for <= 81 taps), B.FIR_VALU or B.FIR_MFMA"""
         self._chk(self.L.dvbs2hip_set_filter_kernel(self.h, int(kernel)))

@@ -20,7 +20,7 @@ import numpy as np
 from . import params as P
 from .iqfile import ProcessingAborted, RadioUserBinary
 from .rx_sequence import LockTracker, RxSequence, add_timing_args
-from .srcfile import SinkUserBinary, load_src
+from .srcfile import SinkTS, SinkUserBinary, load_src
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -47,6 +47,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--smf-kernel", choices=["LANE", "WAVE"], default=None, help="with --wl-phases: the form of the coarse-frequency loop (LANE: one lane per stream, the library's "
                                                                                  "default; WAVE: one wave per stream, the faster one here; the same results); default: not set")
     ap.add_argument("--snk-path", default="", help="decoded payload of every frame, eight bits per byte (the reference's Sink_user_binary: a file sent with dvbs2_tx --src-type USER_BIN comes out as it went in)")
+    ap.add_argument("--snk-type", default="BITS", choices=["BITS", "TS"], help="BITS: --snk-path gets every frame's K_bch bits; TS (an extension): the frames are DVB-S2 BBFRAMEs (dvbs2_tx --src-type TS) "
+                                                                               "and --snk-path gets the transport packets of the frames whose BBHEADER checks -- nothing before the lock, nothing of a broken frame")
     ap.add_argument("--timing-offset", type=int, default=-1, help="sample index of the first symbol after the matched filter (default: two group delays)")
     ap.add_argument("--sync-fine", action="store_true", help="run the pilot-aided phase synchronizer before the chain")
     ap.add_argument("--est-type", default="DVBS2", choices=["DVBS2", "PILOTS"], help="the noise estimator: DVBS2 is the reference's M2M4 (biased low on 16APSK and 32APSK: it takes every point to have "
@@ -78,6 +80,9 @@ def run(args, out=sys.stdout) -> dict:
     if not args.rad_rx_no_loop and not args.max_frames:
         raise ValueError("a looping input needs --max-frames")
     pattern = load_src(args.src_path, mc.K_bch) if args.src_type == "USER" and args.src_path else None
+    ts = getattr(args, "snk_type", "BITS") == "TS"
+    if ts and pattern is not None:
+        raise ValueError("--snk-type TS hands out packets, not bits: there is nothing to count against a pattern (--src-type NONE)")
     rx = Dvbs2Hip(mc.name, max_frames=F, n_ite=args.dec_ite, alpha=args.dec_alpha, early_stop=True, implem=args.dec_implem, device=args.device)
     if args.sim_stats:
         rx.timing_enable(True)
@@ -105,12 +110,14 @@ def run(args, out=sys.stdout) -> dict:
         rx.sync_timing_set_type("ULTRA", args.stm_hold_size)
         learn = sum(args.wl_frames) if args.stm_learn_frames is None else args.stm_learn_frames
     rcv = RadioUserBinary(n * osf, input_filename=args.rad_rx_file_path, auto_reset=not args.rad_rx_no_loop, n_frames=F)
-    snk = SinkUserBinary(args.snk_path, mc.K_bch) if args.snk_path else None
+    snk = (SinkTS(args.snk_path) if ts else SinkUserBinary(args.snk_path, mc.K_bch)) if args.snk_path else None
     # the task sequence (rx_sequence.py); --wl-phases: the frozen coarse estimate in front, and L&R as learning phase 3 has trained it, for what that estimate leaves
     seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq or wl), timing=args.stm_type, learn_frames=learn,
                      timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf,      # two group delays of grp_delay * osf samples
-                     fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check, estimator=getattr(args, "est_type", "DVBS2"))
+                     fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check, estimator=getattr(args, "est_type", "DVBS2"), packets=ts)
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
+    if ts:
+        st.update(bbframes_dropped=0, packets=0, crc8_errors=0)
     if pls_check:
         st["pls_mismatches"] = 0
         pls_want, pls_locked, pls_seen = rx.pls_expected(), 0, collections.Counter()
@@ -133,6 +140,11 @@ def run(args, out=sys.stdout) -> dict:
                 continue
             delay, flags, tri, aligned = seq.align(sym)
             bits = seq.decode(aligned)
+            if ts:                                                                 # the batch's packets, its frames' statuses: counted here from what the one call returned
+                packets, status, hdr = bits
+                st["bbframes_dropped"] += int((hdr[:, 0] != 0).sum()); st["packets"] += len(packets); st["crc8_errors"] += int((status != 0).sum())
+                if snk:
+                    snk.send(packets)
             for f in range(len(sym)):
                 locked = lock.update(delay[f]) >= 2                                # the delay line has settled on this alignment
                 if pls_check and locked:
@@ -141,7 +153,7 @@ def run(args, out=sys.stdout) -> dict:
                     pls_seen[v] += v != pls_want
                     if pls_locked >= 16 and 2 * st["pls_mismatches"] > pls_locked:
                         raise ValueError("stream carries %s; the receiver was built for %s (PLS %d)" % (_pls_text(pls_seen.most_common(1)[0][0]), mc.name, pls_want))
-                if snk:
+                if snk and not ts:
                     snk.send(bits[f])
                 if pattern is not None and locked:
                     e = min(int((bits[f] != p).sum()) for p in pattern)
@@ -157,7 +169,8 @@ def run(args, out=sys.stdout) -> dict:
     st["ber"] = st["be"] / max(1, st["locked_frames"] * mc.K_bch)
     st["fer"] = st["fe"] / max(1, st["locked_frames"])
     print("# frames %(frames)d | in lock %(locked_frames)d | BE %(be)d | FE %(fe)d | BER %(ber).2e | FER %(fer).2e | delay %(delay)s" % st +
-          (" | PLS mismatches %d" % st["pls_mismatches"] if pls_check else ""), file=out)
+          (" | PLS mismatches %d" % st["pls_mismatches"] if pls_check else "") +
+          (" | BBFRAMEs dropped %(bbframes_dropped)d | packets %(packets)d | CRC-8 errors %(crc8_errors)d" % st if ts else ""), file=out)
     return st
 
 

@@ -18,16 +18,17 @@ class RxSequence:
     timing_offset, needs pl_frame), "FAST" or "ULTRA" (the Gardner loop the handle has been set to; ULTRA holds once learn_frames frames have been fed); fine: the fine
     synchronizers and the chain task by task, lr: L&R among them; fused (None: unless fine): rx_bb, the fused chain; sigma: the channel's, None for the estimator's;
     pls_check: align() also reads the aligned frames' PLHEADERs and leaves (PLS, MET, ENE) of its last call in self.pls (off: the call sequence has no such task);
-    estimator: "DVBS2" (M2M4, the reference's; the call sequence is as it was) or "PILOTS" (estimate_pilots: unbiased for 16APSK and 32APSK too), used when sigma is None."""
+    estimator: "DVBS2" (M2M4, the reference's; the call sequence is as it was) or "PILOTS" (estimate_pilots: unbiased for 16APSK and 32APSK too), used when sigma is None;
+    packets: decode() hands out the user packets of the frames' BBFRAMEs instead of their bits (rx_bb_up in place of rx_bb, or bbframe_parse behind bb_descramble)."""
 
     def __init__(self, rx, F, osf=2, pl_frame=None, agc=True, coarse=False, timing="PERFECT", timing_offset=0, learn_frames=0, fine=False, lr=False, sigma=None, fused=None, pls_check=False,
-                 estimator="DVBS2"):
+                 estimator="DVBS2", packets=False):
         if estimator not in ("DVBS2", "PILOTS"):
             raise ValueError("estimator is DVBS2 or PILOTS")
         if fused == fine:
             raise ValueError("the fused chain has no fine synchronizer in it, the tasks one by one start with them: fine or fused, not both or neither")
         self.rx, self.F, self.osf, self.n, self.agc, self.coarse, self.timing, self.learn_frames, self.fine, self.lr, self.sigma = rx, F, osf, pl_frame, agc, coarse, timing, learn_frames, fine, lr, sigma
-        self.pls_check, self.pls, self.estimator = pls_check, None, estimator
+        self.pls_check, self.pls, self.estimator, self.packets = pls_check, None, estimator, packets
         self.fed = 0                                                               # frames the timing loop has taken
         self.skip = timing_offset
         self.tail = np.zeros((0, 2), np.float32)                                   # PERFECT: matched-filter samples not yet turned into symbols
@@ -70,11 +71,12 @@ class RxSequence:
         return self.rx.sync_freq_phase_synchronize(desc)[2]
 
     def decode(self, aligned):
-        """-> bits [frames, K_bch]"""
+        """-> bits [frames, K_bch]; packets: (packets [n, UPLB], status [n], hdr [frames, 8]) instead, the BBFRAME parser behind the chain"""
         rx = self.rx
         pilots = self.estimator == "PILOTS" and self.sigma is None
         if not self.fine:
-            return rx.rx_bb(aligned, sigma=rx.estimate_pilots(aligned, scrambled=True)[0] if pilots else self.sigma)[0]
+            sigma = rx.estimate_pilots(aligned, scrambled=True)[0] if pilots else self.sigma
+            return rx.rx_bb_up(aligned, sigma=sigma)[:3] if self.packets else rx.rx_bb(aligned, sigma=sigma)[0]
         desc = self.fine_sync(aligned)
         xf = rx.remove_plh(desc)
         if pilots:
@@ -82,7 +84,8 @@ class RxSequence:
         else:
             sig = rx.estimate(xf)[0] if self.sigma is None else np.full(len(aligned), self.sigma, np.float32)
         vk, _ = rx.decode_siho(rx.demodulate(sig, xf, deinterleave=True))
-        return rx.bb_descramble(rx.decode_hiho(vk)[0])
+        bits = rx.bb_descramble(rx.decode_hiho(vk)[0])
+        return rx.bbframe_parse(bits) if self.packets else bits
 
 
 class LockTracker:

@@ -7,7 +7,10 @@
   Source_AZCW         all-zero payloads (DVBS2.cpp:371)
   Sink_user_binary    `--snk-path out.ts` (README.md:210): the decoded payload packed the same way, frame after frame (DVBS2.cpp:385)
 
-A file sent with USER_BIN and received into the sink is the file again, byte for byte, whatever the bit order -- both ends use the same one."""
+A file sent with USER_BIN and received into the sink is the file again, byte for byte, whatever the bit order -- both ends use the same one.
+
+An extension beside them: SourceTS / SinkTS (`--src-type TS`, `--snk-type TS`), a transport stream as the packet stream of the BBFRAME layer (Dvbs2Hip.bbframe_build /
+bbframe_parse / rx_bb_up): the frames on air are DVB-S2 BBFRAMEs, and the sink gets whole packets of the frames whose BBHEADER checks."""
 from __future__ import annotations
 
 import numpy as np
@@ -84,6 +87,63 @@ class SourceUserBinary:
     def frames_left(self) -> int | None:
         """whole or partial frames still to come (None: a looping source never ends)"""
         return None if self.auto_reset else -(-(self.data.size - self.pos) * 8 // self.K)
+
+
+TS_PACKET, TS_SYNC = 188, 0x47
+TS_NULL = np.concatenate([np.array([TS_SYNC, 0x1F, 0xFF, 0x10], np.uint8), np.full(TS_PACKET - 4, 0xFF, np.uint8)])       # PID 0x1FFF, payload only
+
+
+class SourceTS:
+    """An MPEG transport stream as the BBFRAME layer's packet stream (`--src-type TS`): generate(F) -> (the next bytes of the stream, the frames they fill), what
+    Dvbs2Hip.bbframe_build takes; D = (K_bch - 80) / 8 bytes go into a full frame.  The file has to be whole packets of 188 bytes that start with 0x47.  It loops over the
+    file (packets keep straddling frames across the wrap); auto_reset = False sends it once, followed by one null packet that gives the file's last packet the CRC slot
+    behind it -- the last frame is then short -- and then by one call of no frames at all (the transmitter pads it), which pushes the last frames through a receiver's
+    delays."""
+
+    def __init__(self, path: str, D: int, auto_reset: bool = True):
+        import os
+        size = os.path.getsize(path)
+        if size == 0:
+            raise ValueError("'%s' is empty" % path)
+        self.data = np.memmap(path, dtype=np.uint8, mode="r")
+        if size % TS_PACKET:
+            raise ValueError("'%s' is not a transport stream: %d bytes are not whole packets of 188 (offset %d)" % (path, size, size - size % TS_PACKET))
+        bad = np.flatnonzero(np.asarray(self.data[::TS_PACKET]) != TS_SYNC)
+        if bad.size:
+            raise ValueError("'%s' is not a transport stream: no sync byte 0x47 at offset %d" % (path, int(bad[0]) * TS_PACKET))
+        self.D, self.pos, self.auto_reset, self.done, self.flushed = int(D), 0, auto_reset, False, False
+        self.size = size if auto_reset else size + TS_PACKET
+
+    def generate(self, F: int):
+        nb = F * self.D
+        if self.auto_reset:
+            idx = (self.pos + np.arange(nb)) % self.size
+            self.pos = int((self.pos + nb) % self.size)
+            return np.asarray(self.data[idx]), F
+        if self.done:
+            if self.flushed:
+                raise SourceDone("the whole file has been sent")
+            self.flushed = True
+            return np.zeros(0, np.uint8), 0
+        end = min(self.pos + nb, self.size)
+        chunk = np.concatenate([np.asarray(self.data[self.pos:min(end, self.data.size)]), TS_NULL[max(self.pos, self.data.size) - self.data.size:max(end, self.data.size) - self.data.size]])
+        self.pos = end
+        self.done = end >= self.size
+        return chunk, -(-chunk.size // self.D)
+
+
+class SinkTS:
+    """send(packets[n, 188]) appends the packets the BBFRAME parser emitted (`--snk-type TS`)"""
+
+    def __init__(self, path: str):
+        self.f = open(path, "wb")
+
+    def send(self, packets) -> None:
+        self.f.write(np.ascontiguousarray(packets, dtype=np.uint8).tobytes())
+        self.f.flush()
+
+    def close(self) -> None:
+        self.f.close()
 
 
 class SourceAZCW:

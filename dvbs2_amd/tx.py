@@ -11,18 +11,22 @@ import argparse
 import sys
 import time
 
+import numpy as np
+
 from . import params as P
 from .iqfile import RadioUserBinary
-from .srcfile import SourceAZCW, SourceDone, SourceUser, SourceUserBinary
+from .srcfile import SourceAZCW, SourceDone, SourceTS, SourceUser, SourceUserBinary
 
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="dvbs2_tx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mod-cod", default="QPSK-S_8/9")
     ap.add_argument("-F", "--src-fra", type=int, default=1, dest="n_frames_batch")
-    ap.add_argument("--src-type", default="RAND", choices=["RAND", "USER", "USER_BIN", "AZCW"])      # DVBS2.cpp:66
+    ap.add_argument("--src-type", default="RAND", choices=["RAND", "USER", "USER_BIN", "AZCW", "TS"],      # DVBS2.cpp:66
+                    help="TS (an extension): --src-path is an MPEG transport stream, sent as DVB-S2 BBFRAMEs (BBHEADER, CRC-8 per packet; the receiver's --snk-type TS)")
     ap.add_argument("--src-path", default="")
-    ap.add_argument("--src-no-loop", action="store_true", help="USER_BIN: send the file once (the last frame zero-padded) instead of over and over")
+    ap.add_argument("--src-no-loop", action="store_true", help="USER_BIN: send the file once (the last frame zero-padded) instead of over and over; TS: once, then one null packet (the last frame "
+                    "short), the batch and one more padded with all-zero frames, which a BBFRAME parser drops")
     ap.add_argument("--shp-osf", type=int, default=2, dest="osf", choices=[2], help="samples per symbol (the GPU shaping filter is built for 2)")
     ap.add_argument("--rad-type", default="USER_BIN", choices=["USER_BIN"])
     ap.add_argument("--rad-tx-file-path", required=True)
@@ -32,7 +36,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sim-stats", action="store_true", help="per-kernel-group device time at the end (the reference's --sim-stats)")
     ap.add_argument("--tx-tasks", action="store_true", help="make the PL frames by the seven TX tasks, one C-ABI call per task in the reference's order, instead of the fused tx_bb "
-                    "(payload sources USER, USER_BIN and AZCW; same frames)")
+                    "(payload sources USER, USER_BIN, AZCW and TS; same frames)")
     return ap
 
 
@@ -75,16 +79,17 @@ def run(args, out=sys.stdout) -> int:
     """-> number of frames written"""
     from .receiver import Dvbs2Hip
     mc = P.get_modcod(args.mod_cod)
-    once = args.src_type == "USER_BIN" and args.src_no_loop
+    once = args.src_type in ("USER_BIN", "TS") and args.src_no_loop
     if not args.n_frames and not args.tx_time_limit and not once:
         raise ValueError("one of --n-frames / --tx-time-limit is needed to end the transmission")
-    if args.src_type in ("USER", "USER_BIN") and not args.src_path:
+    if args.src_type in ("USER", "USER_BIN", "TS") and not args.src_path:
         raise ValueError("--src-type %s needs --src-path" % args.src_type)
     if args.tx_tasks and args.src_type == "RAND":
-        raise ValueError("--tx-tasks needs a payload source (USER, USER_BIN or AZCW): the random source lives inside the fused tx_bb")
+        raise ValueError("--tx-tasks needs a payload source (USER, USER_BIN, AZCW or TS): the random source lives inside the fused tx_bb")
     F = args.n_frames_batch
     src = (SourceUser(args.src_path, mc.K_bch) if args.src_type == "USER" else SourceUserBinary(args.src_path, mc.K_bch, auto_reset=not args.src_no_loop) if args.src_type == "USER_BIN"
-           else SourceAZCW(mc.K_bch) if args.src_type == "AZCW" else None)
+           else SourceAZCW(mc.K_bch) if args.src_type == "AZCW" else SourceTS(args.src_path, (mc.K_bch - 80) // 8, auto_reset=not args.src_no_loop) if args.src_type == "TS" else None)
+    ts = args.src_type == "TS"
     rx = Dvbs2Hip(mc.name, max_frames=F, device=args.device)
     if args.sim_stats:
         rx.timing_enable(True)
@@ -97,6 +102,11 @@ def run(args, out=sys.stdout) -> int:
                 info = src.generate(F) if src else None
             except SourceDone:
                 break
+            if ts:                                                          # the packet stream's next bytes -> BBFRAMEs on the GPU; frames the stream does not fill stay zero
+                stream, n = info
+                info = np.zeros((F, mc.K_bch), np.int32)
+                if n:
+                    info[:n] = rx.bbframe_build(stream, n)
             if tasks:
                 pl = tasks.run(info)
             else:

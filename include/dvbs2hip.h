@@ -642,6 +642,65 @@ int dvbs2hip_estimate_pilots_located_dev(dvbs2hip_t *h, const float *const *SRC,
 int dvbs2hip_estimate_pilots_set_alpha(dvbs2hip_t *h, float alpha);
 int dvbs2hip_estimate_pilots_reset(dvbs2hip_t *h);
 
+/* ------------------------------------------------------------------ BBFRAME layer (extension: the reference has no such task; its chain begins and ends in K_bch
+ * anonymous bits per frame.  EN 302 307-1 clause 5.1, mode adaptation, for one packetised stream)
+ * Bit i of a frame is element i of the int32_t[K_bch] socket; byte k of a frame is bits 8k .. 8k+7, bit 8k the byte's bit 7; multi-bit fields most significant bit first.
+ * BBFRAME = BBHEADER (80 bits) | DATA FIELD (DFL bits) | K_bch - 80 - DFL zero bits; it then goes through the BB scrambler (dvbs2hip_bb_scramble, dvbs2hip_tx_bb's info_in).
+ * BBHEADER: MATYPE-1, MATYPE-2, UPL (2 bytes, the user packet length in bits), DFL (2 bytes), SYNC, SYNCD (2 bytes: bits from the start of the data field to the first
+ *   packet that starts in it, 65535 = none does), CRC-8 of these nine bytes.  CRC-8: g(x) = x^8 + x^7 + x^6 + x^4 + x^2 + 1, register 0 at the start, nothing reflected, no
+ *   final xor ("123456789" -> 0xBC).
+ * Packets: UPLB = UPL / 8 bytes each, byte 0 the sync byte; on air the CRC-8 of a packet's other UPLB - 1 bytes stands in the place of the NEXT packet's sync byte (its
+ *   "slot"; the very first slot carries 0), and the byte stream is cut into data fields with no regard for packet borders.
+ * set_params(matype1, matype2, upl_bits, sync, mark_tei): defaults 0xF2 (transport stream, single stream, CCM, roll-off 0.20), 0, 1504, 0x47, 0.  upl_bits has to be a
+ *   multiple of 8 in [16, K_bch - 80]: DVBS2HIP_EUNSUPPORTED otherwise (continuous streams, UPL = 0, are not provided).  It resets both tasks.
+ * reset: both tasks' state and the counters to zero; a no-op on a handle that has not used the layer; dvbs2hip_reset calls it.
+ * get_stats: uint64_t[5] = {frames taken, frames dropped, packets with a right CRC-8, packets with a wrong one, bytes discarded}, since the last reset (it synchronises).
+ *
+ * build: the next n_bytes bytes UP of the packet stream -> U_K, int32_t[n_frames * K_bch], with D = (K_bch - 80) / 8 and (n_frames - 1) D < n_bytes <= n_frames D
+ *   (DVBS2HIP_EINVAL otherwise): all frames but the last are full, the last one takes the rest (DFL = 8 rest) and is padded.  The task keeps the position in the
+ *   current packet and the CRC-8 registers from call to call, so a stream may be cut into calls anywhere.  The sync bytes of UP are not looked at.
+ *
+ * parse: V_K, int32_t[n_frames * K_bch], descrambled frames; VALID, int8_t[n_frames] or NULL: 0 = this frame is not to be trusted (e.g. the BCH flag)
+ *   -> UP: the packets, contiguous, in stream order, capacity * UPLB bytes; STATUS: uint8_t[capacity], 0 = the packet's CRC-8 is right, 1 = wrong; N_OUT: int32_t[1], how
+ *   many; HDR: int32_t[n_frames * 8] or NULL, per frame {status, MATYPE-1 << 8 | MATYPE-2, UPL, DFL, SYNC, SYNCD, CRC-8 received, CRC-8 computed}.
+ *   capacity = dvbs2hip_bbframe_max_packets(h, n_frames) = floor((n_frames D + UPLB - 1) / UPLB); N_OUT never exceeds it.
+ *   Frame status: 3 VALID[f] == 0; else 1 the header's CRC-8 is wrong; else 2 a field is refused (UPL or SYNC not the configured one, DFL > K_bch - 80 or not a multiple of
+ *   8, SYNCD not a multiple of 8, SYNCD >= DFL and not 65535); else 0, taken.
+ *   The packets are those of this rule, applied to the frames in order, `buf` (the pending packet) and `have` carried from call to call:
+ *     status != 0:                     discard buf (count its bytes); have = false; next frame
+ *     df = the DFL / 8 bytes of the data field
+ *     SYNCD == 65535:                  discard buf and df (count both); have = false; next frame
+ *     s = SYNCD / 8
+ *     have and len(buf) + s == UPLB:   emit buf + df[:s], its slot is df[s]
+ *     otherwise:                       discard buf and df[:s] (count both)
+ *     for start = s, s + UPLB, ... while start + UPLB < len(df):   emit df[start : start + UPLB], its slot is df[start + UPLB]
+ *     buf = df[last start :] (1 .. UPLB bytes: a packet that ends on df's last byte waits for its slot); have = true
+ *   emit: byte 0 becomes SYNC; STATUS = the CRC-8 over bytes 1 .. UPLB - 1 differs from the slot's byte; with mark_tei, UPL = 1504 and STATUS = 1, bit 7 of byte 1 (a
+ *   transport packet's transport_error_indicator) is set.
+ *   A frame without a packet start (SYNCD = 65535) discards what is pending instead of extending it.  That is deliberate: what a frame emits then depends on its own
+ *   header and the one before it only, so the device counts the packets of all frames at once, places them with one scan, and copies and checks every packet on its own.
+ *   While UPLB <= D every full data field holds a packet start, so only a short last frame that carries nothing but a packet's tail is lost this way.
+ *
+ * rx_bb_up: dvbs2hip_rx_bb_dev into a bit buffer of the handle, then parse with VALID = NULL, in one call; cwd_ldpc / cwd_bch: int8_t[n_frames], may be NULL.  The host
+ *   form copies back the packets, statuses, headers and flags only: about K_bch / 8 bytes of a frame where dvbs2hip_rx_bb returns 4 K_bch.
+ *
+ * n_frames in [1, max_frames].  The _dev forms take device addresses (U_K, V_K 16-byte aligned), are stream-ordered, make no host round trip and a number of launches
+ * that does not depend on n_frames; parse_dev and rx_bb_up_dev may be recorded in a graph after one call outside the capture (which allocates), and as with every task
+ * that keeps a memory each replay starts from the state of the moment of recording.  Integer arithmetic throughout: bit-exact with tests/bbframe_ref.py.
+ * Not provided: multiple input streams, ISSY, null-packet deletion, ACM, continuous generic streams.                                                                 */
+int dvbs2hip_bbframe_set_params(dvbs2hip_t *h, int32_t matype1, int32_t matype2, int32_t upl_bits, int32_t sync, int32_t mark_tei);
+int dvbs2hip_bbframe_reset(dvbs2hip_t *h);
+int dvbs2hip_bbframe_get_stats(dvbs2hip_t *h, uint64_t *stats);
+int dvbs2hip_bbframe_max_packets(dvbs2hip_t *h, int32_t n_frames, int32_t *capacity);
+int dvbs2hip_bbframe_build(dvbs2hip_t *h, const uint8_t *UP, int64_t n_bytes, int32_t *U_K, int32_t n_frames);
+int dvbs2hip_bbframe_build_dev(dvbs2hip_t *h, const uint8_t *UP, int64_t n_bytes, int32_t *U_K, int32_t n_frames);
+int dvbs2hip_bbframe_parse(dvbs2hip_t *h, const int32_t *V_K, const int8_t *VALID, uint8_t *UP, uint8_t *STATUS, int32_t *N_OUT, int32_t *HDR, int32_t n_frames);
+int dvbs2hip_bbframe_parse_dev(dvbs2hip_t *h, const int32_t *V_K, const int8_t *VALID, uint8_t *UP, uint8_t *STATUS, int32_t *N_OUT, int32_t *HDR, int32_t n_frames);
+int dvbs2hip_rx_bb_up(dvbs2hip_t *h, const float *pl_frames, const float *sigma_in, uint8_t *UP, uint8_t *STATUS, int32_t *N_OUT, int32_t *HDR, int8_t *cwd_ldpc, int8_t *cwd_bch,
+                      int32_t n_frames);
+int dvbs2hip_rx_bb_up_dev(dvbs2hip_t *h, const float *pl_frames, const float *sigma_in, uint8_t *UP, uint8_t *STATUS, int32_t *N_OUT, int32_t *HDR, int8_t *cwd_ldpc, int8_t *cwd_bch,
+                          int32_t n_frames);
+
 /* ------------------------------------------------------------------ measurement
  * Per-kernel device time, measured with hipEvents recorded on the handle's stream around
  * each launch while timing is enabled (the equivalent of `--sim-stats`,
