@@ -22,6 +22,18 @@ const char *modcod_name_by_pls(int b0_b6)
     }
     return nullptr;
 }
+
+int pl_frame_by_pls(int b0_b6)
+{
+    for (int i = 0; i < DVBS2_N_MODCODS; i++) {
+        const dvbs2_modcod_row &r = dvbs2_modcod_rows[i];
+        int v = 0;
+        for (int k = 0; k < 7; k++) v = v << 1 | (r.pls[k] & 1);
+        const int n_sym = r.N_ldpc / r.bps;
+        if (v == b0_b6) return 90 * (n_sym / 90 + 1) + (n_sym / (16 * 90)) * 36;         // DVBS2.cpp:351-355, as dvbs2hip_create
+    }
+    return 0;
+}
 }
 
 extern "C" {

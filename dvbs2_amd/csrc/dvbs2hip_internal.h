@@ -318,6 +318,12 @@ hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hi
 hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, hipStream_t s);
 // k_pls.hip: the PLHEADER of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), decoded to V = b0 128 + .. + b6 2 + p; MET, ENE may be null
 hipError_t pls_decode_launch(const float *X, const float *const *SRC, size_t stride_cplx, int32_t *PLS, float *MET, float *ENE, int F, hipStream_t s);
+// k_pls_search.hip: the same decoder at every symbol offset k of X (n_sym complex symbols, 8-byte aligned), K = n_sym - 89 outputs, bit for bit what pls_decode_launch
+// gives for a frame at X + 2 k; MET, ENE may be null.  Then the search of include/dvbs2hip.h on such outputs: LEN int32[256], work pls_search_work_bytes(n_sym) bytes,
+// RES int32[4], SCORE one float; two launches
+hipError_t pls_scan_launch(const float *X, int n_sym, int32_t *PLS, float *MET, float *ENE, hipStream_t s);
+size_t pls_search_work_bytes(int n_sym);
+hipError_t pls_search_launch(const int32_t *PLS, const float *MET, const float *ENE, const int32_t *LEN, void *work, int n_sym, int32_t *RES, float *SCORE, hipStream_t s);
 // k_est_pilots.hip: the pilot-aided noise estimate of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), from its L = 90 + 36 N_pilots known symbols
 // (compact: the frame holds those L symbols and nothing else); plh: the 90 header symbols, seq: the PL sequence (read for scrambled = 1).  AN null: SIG / EB / ES (each
 // may be null) are written; AN given: (A, N) per frame and nothing else, and est_pilots_walk_launch averages them per stream (state: 3 floats per stream) and writes the outputs

@@ -79,6 +79,11 @@ ABI = {
     "dvbs2hip_pls_decode_located_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_pls_expected": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "dvbs2hip_pls_describe": (C.c_int, [_i, C.c_char_p, _i, C.POINTER(C.c_int32)]),
+    "dvbs2hip_pls_scan": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2hip_pls_scan_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2hip_pls_search": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2hip_pls_search_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2hip_pls_frame_symbols": (C.c_int, [_i]),
     "dvbs2hip_estimate_pilots": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
     "dvbs2hip_estimate_pilots_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
     "dvbs2hip_estimate_pilots_located_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),

@@ -118,6 +118,34 @@ def pls_name(value: int):
     return None, bool(value & 1)
 
 
+def pls_frame_symbols(value: int) -> int:
+    """pl_frame of the MODCOD of the table whose PLS value, pilots on (the only frames the library builds), is `value`; 0 when there is none: dvbs2hip_pls_frame_symbols"""
+    if 0 <= value <= 255 and value & 1:
+        for m in MODCODS.values():
+            if pls_value(m, True) == value:
+                return m.pl_frame
+    return 0
+
+
+# the PLHEADER search's own length table (dvbs2hip_pls_search with LEN = NULL): PL frame symbols by PLS value
+PLS_FRAME_SYMBOLS = np.array([pls_frame_symbols(v) for v in range(256)], dtype=np.int32)
+
+# what find_modcod asks of a chain per slot: the geometric mean of the largest per-slot score of buffers without a header and the smallest of the true chain at the
+# lowest operating point, both measured with the float64 twin (results/pls_search/README.md, tools/measure_pls_search_qmin.py)
+PLS_SEARCH_Q_MIN = 0.2805          # sqrt(0.1431 x 0.5500)
+
+
+def find_modcod(res, score: float, q_min: float = None):
+    """What dvbs2hip_pls_search returned, RES = (OFFSET, VALUE, COUNT, SLOTS) and SCORE -> (ModCod, pilots, offset), or None when it is not to be believed: no start, a
+    single header (COUNT < 2), a chain that explains less than q_min of its slots' energy (SCORE < q_min SLOTS), or a value the table has no MODCOD for"""
+    q_min = PLS_SEARCH_Q_MIN if q_min is None else q_min
+    offset, value, count, slots = (int(v) for v in res)
+    if offset < 0 or count < 2 or not score >= q_min * slots:
+        return None
+    name, pilots = pls_name(value)
+    return (MODCODS[name], pilots, offset) if name else None
+
+
 def load_ldpc_table(fname: str):
     """-> (row_ptr int32[n_rows+1], addr int32[n_addr]) from dvbs2_amd/data/ldpc/<fname>."""
     rows = []

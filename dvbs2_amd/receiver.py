@@ -644,6 +644,36 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_pls_expected(self.h, C.byref(v)))
         return v.value
 
+    # ------------------------------------------------------------------ PLHEADER search (an extension: include/dvbs2hip.h)
+    def pls_scan(self, X):
+        """n_sym symbols at one sample per symbol -> (PLS, MET, ENE) at each of the n_sym - 89 offsets: what pls_decode returns for a frame that starts there"""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1)
+        n_sym = X.size // 2
+        K = max(n_sym - 89, 0)
+        PLS, MET, ENE = np.empty(K, np.int32), np.empty(K, np.float32), np.empty(K, np.float32)
+        self._chk(self.L.dvbs2hip_pls_scan(self.h, _ptr(X), n_sym, _ptr(PLS), _ptr(MET), _ptr(ENE)))
+        return PLS, MET, ENE
+
+    def pls_scan_dev(self, X, n_sym, PLS, MET, ENE):
+        """device addresses (MET, ENE may be None), stream-ordered"""
+        self._chk(self.L.dvbs2hip_pls_scan_dev(self.h, X, n_sym, PLS, MET, ENE))
+
+    def pls_search(self, X, LEN=None):
+        """n_sym symbols -> (RES = [OFFSET, VALUE, COUNT, SLOTS], SCORE): the header that repeats at the frame length its value implies (LEN: int32[256] frame lengths by
+        PLS value, None: the library's own table, params.PLS_FRAME_SYMBOLS); params.find_modcod accepts the result or not"""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1)
+        if LEN is not None:
+            LEN = np.ascontiguousarray(LEN, np.int32)
+            if LEN.size != 256:
+                raise ValueError("LEN has one entry per PLS value: 256")
+        RES, SCORE = np.zeros(4, np.int32), np.zeros(1, np.float32)
+        self._chk(self.L.dvbs2hip_pls_search(self.h, _ptr(X), X.size // 2, _ptr(LEN), _ptr(RES), _ptr(SCORE)))
+        return RES, float(SCORE[0])
+
+    def pls_search_dev(self, X, n_sym, LEN, RES, SCORE):
+        """device addresses (LEN may be None), stream-ordered, no host round trip"""
+        self._chk(self.L.dvbs2hip_pls_search_dev(self.h, X, n_sym, LEN, RES, SCORE))
+
     # ------------------------------------------------------------------ pilot-aided noise estimator (an extension: include/dvbs2hip.h)
     def estimate_pilots(self, X_N1, scrambled=True):
         """aligned PL frames -> (SIG, Eb_N0, Es_N0) per frame from the header and pilot symbols; scrambled: the frames are as the frame synchronizer delivers them

@@ -8,6 +8,9 @@ offsets): README.md:151-169 of the reference.
 
   python -m dvbs2_amd.rx --src-type USER --src-path K_14232.src --rad-rx-file-path out_tx_noisy.bin -F 8 \
          --mod-cod QPSK-S_8/9 --dec-implem NMS --dec-ite 10 --snk-path /dev/null --rad-rx-no-loop
+
+--mod-cod AUTO (an extension): the MODCOD is read from the PLHEADERs of the head of the file first (detect(): a probe handle, the same front tasks, dvbs2hip_pls_search), one
+line says what was found, and the run goes on as with that MODCOD named.  Constant coding and modulation, pilots on, no --wl-phases.
 """
 from __future__ import annotations
 
@@ -25,7 +28,8 @@ from .srcfile import SinkTS, SinkUserBinary, load_src
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="dvbs2_rx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mod-cod", default="QPSK-S_8/9")
+    ap.add_argument("--mod-cod", default="QPSK-S_8/9", help="a MODCOD of the table, or AUTO (an extension): read it from the PLHEADERs of the head of the file (constant coding and "
+                                                            "modulation, pilots on; excludes --wl-phases)")
     ap.add_argument("-F", "--src-fra", type=int, default=1, dest="n_frames_batch")
     ap.add_argument("--src-type", default="USER", choices=["USER", "NONE"], help="USER: count errors against the pattern file")
     ap.add_argument("--src-path", default="")
@@ -73,8 +77,69 @@ def _pls_text(v):
     return "%s (PLS %d, pilots %s)" % (name, v, "on" if pilots else "off") if name else "PLS %d, pilots %s" % (v, "on" if pilots else "off")
 
 
+AUTO_SYMBOLS = 2 * 33282 + 90      # --mod-cod AUTO searches at least this many symbols (or what the file holds): two frames of the longest MODCOD and a header
+
+
+def detect(args, out=sys.stdout) -> dict:
+    """--mod-cod AUTO: what the stream is and where its frames start, from the PLHEADERs of the head of the file.  A probe handle (any MODCOD: no task in front of the frame
+    synchronizer depends on it) takes the samples through RxSequence.front and RxSequence.symbols as the run itself would, the symbols go through pls_search, and
+    params.find_modcod accepts the result or not -> dict(modcod, value, pilots, offset, count, slots, score, symbols); ValueError when no chain of headers is found"""
+    from .receiver import Dvbs2Hip
+    if getattr(args, "wl_phases", False):
+        raise ValueError("--mod-cod AUTO reads the PLHEADER coherently over its 90 symbols and takes the carrier offset the PLS decoder takes; the coarse-frequency loop of "
+                         "--wl-phases needs the frame length before it can remove a larger one: name the MODCOD, or hand the offset in with --coarse-freq")
+    if not args.rad_rx_no_loop and not args.max_frames:
+        raise ValueError("a looping input needs --max-frames")
+    mc = P.get_modcod("")
+    F, n, osf = args.n_frames_batch, mc.pl_frame, args.osf
+    rx = Dvbs2Hip(mc.name, max_frames=F, device=args.device)
+    rcv = None
+    try:
+        if args.coarse_freq:
+            rx.sync_coarse_set_freq(args.coarse_freq)
+        learn = 0
+        if args.stm_type in ("FAST", "ULTRA"):
+            if osf != 2:
+                raise ValueError("--stm-type %s is the Gardner loop at two samples per symbol (--shp-osf 2)" % args.stm_type)
+            rx.sync_timing_set_params(args.stm_df, args.stm_nbw, args.stm_dg)
+        if args.stm_type == "ULTRA":
+            rx.sync_timing_set_type("ULTRA", args.stm_hold_size)
+            learn = sum(args.wl_frames) if args.stm_learn_frames is None else args.stm_learn_frames
+        rcv = RadioUserBinary(n * osf, input_filename=args.rad_rx_file_path, auto_reset=not args.rad_rx_no_loop, n_frames=F)
+        seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq), timing=args.stm_type, learn_frames=learn,
+                         timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf, fused=True)
+        got, have = [], 0
+        while have < AUTO_SYMBOLS:
+            try:
+                x = rcv.receive()
+            except ProcessingAborted:
+                break
+            sym = seq.symbols(seq.front(x))
+            if sym is not None:
+                got.append(np.asarray(sym, np.float32).reshape(-1)); have += got[-1].size // 2
+        if have < 90:
+            raise ValueError("--mod-cod AUTO: the file holds %d symbols, a PLHEADER has 90" % have)
+        res, score = rx.pls_search(np.concatenate(got))
+    finally:
+        rx.close()
+        if rcv is not None:
+            rcv.close()
+    found = P.find_modcod(res, score)
+    offset, value, count, slots = (int(v) for v in res)
+    if found is None:
+        best = "none" if offset < 0 else "%s at symbol %d, %d of %d headers, score %.2f" % (_pls_text(value), offset, count, slots, score)
+        raise ValueError("--mod-cod AUTO: no chain of PLHEADERs in the first %d symbols (searched: the %d MODCODs of the table, pilots on, at least two headers one frame "
+                         "apart explaining %.2f of their windows' energy each); best chain: %s" % (have, len(P.MODCODS), P.PLS_SEARCH_Q_MIN, best))
+    print("# AUTO: %s | header at symbol %d | %d of %d headers | score %.2f" % (_pls_text(value), offset, count, slots, score), file=out)
+    return dict(modcod=found[0].name, value=value, pilots=found[1], offset=offset, count=count, slots=slots, score=score, symbols=have)
+
+
 def run(args, out=sys.stdout) -> dict:
     from .receiver import Dvbs2Hip
+    auto = None
+    if args.mod_cod == "AUTO":
+        auto = detect(args, out)
+        args = argparse.Namespace(**dict(vars(args), mod_cod=auto["modcod"]))        # from here on exactly as --mod-cod <that name>
     mc = P.get_modcod(args.mod_cod)
     F, n, osf = args.n_frames_batch, mc.pl_frame, args.osf
     if not args.rad_rx_no_loop and not args.max_frames:
@@ -116,6 +181,8 @@ def run(args, out=sys.stdout) -> dict:
                      timing_offset=args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf,      # two group delays of grp_delay * osf samples
                      fine=bool(args.sync_fine or wl), lr=wl, pls_check=pls_check, estimator=getattr(args, "est_type", "DVBS2"), packets=ts)
     st = dict(frames=0, locked_frames=0, be=0, fe=0, delay=None)
+    if auto is not None:
+        st["auto"] = auto
     if ts:
         st.update(bbframes_dropped=0, packets=0, crc8_errors=0)
     if pls_check:

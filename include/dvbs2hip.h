@@ -611,6 +611,38 @@ int dvbs2hip_pls_decode_located_dev(dvbs2hip_t *h, const float *const *SRC, int3
 int dvbs2hip_pls_expected(dvbs2hip_t *h, int32_t *value);
 int dvbs2hip_pls_describe(int32_t value, char *name, int32_t name_len, int32_t *pilots);
 
+/* ------------------------------------------------------------------ PLHEADER search (extension: the reference has no such task; built on the PLS decoder above)
+ * What an unknown constant-coding-and-modulation stream is and where its PL frames start, from symbols at one sample per symbol, without a MODCOD being given.
+ * X: float[2 * n_sym], n_sym complex symbols, 8-byte aligned and no more; 90 <= n_sym <= DVBS2HIP_PLS_SCAN_MAX_SYM (DVBS2HIP_EINVAL otherwise).  There are
+ *   K = n_sym - 89 offsets.  Neither call depends on the handle's MODCOD or on max_frames.
+ * scan: PLS: int32_t[K], MET: float[K] (may be NULL), ENE: float[K] (may be NULL).  Output k is what dvbs2hip_pls_decode_dev returns for a frame that starts at
+ *   X + 2 k, bit for bit (dvbs2_amd/csrc/k_pls_search.hip builds the same sums in the same order with the lanes across offsets; tests/test_pls_search_gpu.py).
+ * search: LEN: int32_t[256], the PL frame length in symbols that PLS value V implies, or 0 when V is not a candidate; entries below 90 count as 0.  A host pointer in
+ *   the host form, a device pointer in the _dev form.  NULL: the library's own table, dvbs2hip_pls_frame_symbols(V) for V = 0 .. 255, uploaded once per handle.
+ *   RES: int32_t[4] = {OFFSET, VALUE, COUNT, SLOTS}; SCORE: one float.  With (PLS, MET, ENE) the scan's outputs, all arithmetic fp32, each operation rounded once:
+ *     q[k] = (MET[k] * MET[k]) / (90 * ENE[k]), and 0 when ENE[k] = 0.  By Cauchy-Schwarz q <= 1: the share of the window's energy that the best header explains,
+ *       so a gain in front changes nothing.
+ *     Offset k is a start when L = LEN[PLS[k]] > 0 and k < L.
+ *     A start's slots are k_j = k + j L < K, j = 0 .. J - 1.
+ *     Its score is C = sum over j ascending of q[k_j] where PLS[k_j] = PLS[k], and of 0 where it is not; the sum is serial from 0.  COUNT is the number of slots that
+ *       match (slot 0 always does).
+ *     The winner has the largest C; among equal C the smallest k.
+ *     OFFSET = k, VALUE = PLS[k], COUNT, SLOTS = J, SCORE = C.  OFFSET = -1 and the other outputs zero when no offset is a start.
+ *   A caller accepts the result or not (dvbs2_amd.params.find_modcod: COUNT >= 2 and SCORE >= q_min SLOTS; results/pls_search/README.md has q_min's measurement).
+ * frame_symbols: no handle; pl_frame of the MODCOD of the library's table whose PLS value (pilots on: the only frames the library builds) is `value`, 0 when there is
+ *   none -- an even value, a value outside 0..255, a row the table does not have.
+ * The search is coherent over the header's 90 symbols and tolerates what the PLS decoder tolerates (a residual carrier of 1e-3 cycles per symbol at 0 dB); it does not
+ * walk from header to header (VCM / ACM), and knows nothing of dummy frames.
+ * The _dev forms take device addresses, are stream-ordered and make no host round trip: the scan one launch, the search three (scan, chain scores, reduction), none of
+ * which waits on another workgroup.  search_dev keeps (PLS, MET, ENE) and the reduction's partial results in the handle's workspace, 12 bytes per offset: it may be
+ * recorded in a graph after one call of the same n_sym (and LEN = NULL, if that is used) outside the capture, which allocates.                                       */
+#define DVBS2HIP_PLS_SCAN_MAX_SYM (1 << 24)
+int dvbs2hip_pls_scan(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t *PLS, float *MET, float *ENE);
+int dvbs2hip_pls_scan_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t *PLS, float *MET, float *ENE);
+int dvbs2hip_pls_search(dvbs2hip_t *h, const float *X, int32_t n_sym, const int32_t *LEN, int32_t *RES, float *SCORE);
+int dvbs2hip_pls_search_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, const int32_t *LEN, int32_t *RES, float *SCORE);
+int dvbs2hip_pls_frame_symbols(int32_t value);
+
 /* ------------------------------------------------------------------ pilot-aided noise estimator (extension: the reference has no such task; its only estimator is
  * Estimator_DVBS2, dvbs2hip_estimate above, whose Se = sqrt(|2 m2^2 - m4|) takes every constellation point to have the same modulus: on 16APSK it never reads above
  * about 8.8 dB of Es/N0 and on 32APSK it stops near 5 dB, so sigma comes out 2 to 2.8 times too large)
