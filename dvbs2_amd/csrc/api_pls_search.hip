@@ -6,7 +6,9 @@ using namespace dvbs2;
 
 constexpr int32_t PLS_SCAN_MAX_SYM = DVBS2HIP_PLS_SCAN_MAX_SYM;      // the search's workspace is 12 bytes per offset: 192 MiB at the limit
 
-static int plss_check(dvbs2hip_t *h, int32_t n_sym)
+namespace dvbs2 {
+
+int plss_check(dvbs2hip_t *h, int32_t n_sym)
 {
     int r = enter(h); if (r) return r;
     if (n_sym < 90 || n_sym > PLS_SCAN_MAX_SYM)
@@ -15,7 +17,7 @@ static int plss_check(dvbs2hip_t *h, int32_t n_sym)
 }
 
 // a workspace of the handle; inside a capture it has to be there already
-static int plss_ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
+int plss_ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
 {
     if (h->capturing && h->bufs[id].bytes < bytes) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first call of this size allocates its workspace");
     return ensure(h, id, bytes, out);
@@ -32,7 +34,7 @@ static int plss_scan_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t *
 }
 
 // the library's own table, on the device
-static int plss_len(dvbs2hip_t *h, const int32_t **LEN)
+int plss_len(dvbs2hip_t *h, const int32_t **LEN)
 {
     if (!h->d_pls_len) {
         if (h->capturing) return fail(h, DVBS2HIP_EINVAL, "run the sequence once before recording it: the first search with LEN = NULL uploads the library's table");
@@ -43,6 +45,8 @@ static int plss_len(dvbs2hip_t *h, const int32_t **LEN)
     *LEN = h->d_pls_len;
     return 0;
 }
+
+}  // namespace dvbs2
 
 static int plss_search_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, const int32_t *LEN, int32_t *RES, float *SCORE)
 {

@@ -206,7 +206,7 @@ inline int fail(dvbs2hip_t *h, int code, const std::string &msg)
 enum BufId { B_IN = 0, B_OUT, B_AUX0, B_AUX1, B_AUX2, B_AUX3, B_LLR, B_PACKED, B_EST, B_CWD0, B_CWD1, B_INFO, B_SIG, B_TXBCH, B_TXLDPC,
              B_SFM_CORR, B_SFM_MET, B_SFM_SOF, B_SFM_PLSC, B_SFM_DLY, B_SFM_DTAB, B_SFF_TMP, B_SFF_OUT, B_FLT2, B_MON_BE, B_MON_OUT, B_BCHFLAG, B_ORDER, B_LR_TMP0, B_LR_TMP1, B_LR_TMP2, B_LR_TMP3, B_SFM_SCR, B_SFM_NEED,
              B_STM_X, B_STM_Y, B_STM_B, B_STM_MU, B_STM_Y2, B_STM_UFW, B_STM_RDY, B_SMF_DEL, B_SMF_FRQ, B_PLS_HDR, B_PLS_OUT, B_ESTP_SYM, B_ESTP_OUT, B_ESTP_AN,
-             B_BBF_UP, B_BBF_STAT, B_BBF_NOUT, B_BBF_HDR, B_BBF_HDRW, B_BBF_PLAN, B_BBF_VALID, B_PLSS_X, B_PLSS_OUT, B_PLSS_WORK, B_PLSS_LEN, B_PLSS_RES };
+             B_BBF_UP, B_BBF_STAT, B_BBF_NOUT, B_BBF_HDR, B_BBF_HDRW, B_BBF_PLAN, B_BBF_VALID, B_PLSS_X, B_PLSS_OUT, B_PLSS_WORK, B_PLSS_LEN, B_PLSS_RES, B_PLSW_WORK, B_PLSW_OUT };
 
 inline int ensure(dvbs2hip_t *h, int id, size_t bytes, void **out)
 {
@@ -428,6 +428,11 @@ std::string ldpc_syn_tables(const dvbs2hip_cfg &cfg, const LdpcPlan &lp, const s
 std::vector<float> plheader(const dvbs2hip_cfg &cfg);
 const char *modcod_name_by_pls(int b0_b6);                                          // dvbs2hip_api.hip: the MODCOD of the library's table whose pls row is these seven bits (b0 the most significant), or null
 int pl_frame_by_pls(int b0_b6);                                                     // dvbs2hip_api.hip: that MODCOD's PL frame in symbols, pilots on (the only frames the library builds), or 0
+// api_pls_search.hip, for the search and the walk (api_pls_walk.hip): n_sym in [90, DVBS2HIP_PLS_SCAN_MAX_SYM]; a workspace of the handle, which inside a capture has
+// to be there already; the library's own length table on the device (uploaded by the first call that asks for it, not inside a capture)
+int plss_check(dvbs2hip_t *h, int32_t n_sym);
+int plss_ensure(dvbs2hip_t *h, int id, size_t bytes, void **out);
+int plss_len(dvbs2hip_t *h, const int32_t **LEN);
 std::vector<float> unit_constellation(const dvbs2hip_cfg &cfg);
 bool separable_2bit(const std::vector<float> &cs, int ax[2], float g[2], float hh[2]);
 

@@ -324,6 +324,13 @@ hipError_t pls_decode_launch(const float *X, const float *const *SRC, size_t str
 hipError_t pls_scan_launch(const float *X, int n_sym, int32_t *PLS, float *MET, float *ENE, hipStream_t s);
 size_t pls_search_work_bytes(int n_sym);
 hipError_t pls_search_launch(const int32_t *PLS, const float *MET, const float *ENE, const int32_t *LEN, void *work, int n_sym, int32_t *RES, float *SCORE, hipStream_t s);
+// k_pls_walk.hip: the walk of include/dvbs2hip.h over the M candidates start + 18 i whose (PLS, MET, ENE) the caller has put at the head of work (M entries each);
+// K = pls_walk_levels(M, the smallest hop LEN allows in candidates, max_out) levels of jumps, work pls_walk_work_bytes(M, K) bytes; lane: one lane follows the chain
+// instead (3 + 2 K launches against 2).  LEN int32[256]; SRC may be null
+int pls_walk_levels(int M, int min_hop, int max_out);
+size_t pls_walk_work_bytes(int M, int K);
+hipError_t pls_walk_launch(const float *X, int n_sym, int start, int M, int K, bool lane, const int32_t *LEN, float q_min, int max_out, void *work, int32_t *OFF, int32_t *VAL,
+                           float *Q, const float **SRC, int32_t *IDX, int32_t *CNT, int32_t *RES, hipStream_t s);
 // k_est_pilots.hip: the pilot-aided noise estimate of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), from its L = 90 + 36 N_pilots known symbols
 // (compact: the frame holds those L symbols and nothing else); plh: the 90 header symbols, seq: the PL sequence (read for scrambled = 1).  AN null: SIG / EB / ES (each
 // may be null) are written; AN given: (A, N) per frame and nothing else, and est_pilots_walk_launch averages them per stream (state: 3 floats per stream) and writes the outputs

@@ -84,6 +84,8 @@ ABI = {
     "dvbs2hip_pls_search": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "dvbs2hip_pls_search_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "dvbs2hip_pls_frame_symbols": (C.c_int, [_i]),
+    "dvbs2hip_pls_walk": (C.c_int, [_vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dvbs2hip_pls_walk_dev": (C.c_int, [_vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dvbs2hip_estimate_pilots": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
     "dvbs2hip_estimate_pilots_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),
     "dvbs2hip_estimate_pilots_located_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i]),

@@ -146,6 +146,41 @@ def find_modcod(res, score: float, q_min: float = None):
     return (MODCODS[name], pilots, offset) if name else None
 
 
+# the PLHEADER walk's table for a VCM stream (dvbs2hip_pls_walk's LEN): the frames the library builds, and value 0, the dummy PLFRAME with pilots off -- a header and 36
+# slots of 90 symbols -- which a receiver has to step over.  Value 1 (a dummy frame with the pilot bit set) and data frames without pilots are left out: the library
+# neither builds nor decodes them, and a header that names one ends the walk as LOST
+VCM_FRAME_SYMBOLS = PLS_FRAME_SYMBOLS.copy()
+VCM_FRAME_SYMBOLS[0] = 90 + 36 * 90
+
+
+def find_vcm_start(PLS, MET, ENE, LEN=None, q_min: float = None):
+    """Acquisition of a VCM stream on the host, once per stream: (PLS, MET, ENE) of one pls_scan of the stream's head -> the offset k < max(LEN) whose walk (the walk of
+    dvbs2hip_pls_walk from k over the scanned symbols, max_out unbounded) accepts the most headers -- every frame it counts, and the header of a last frame that the
+    buffer cuts off -- the smallest k among equal counts; None when no walk accepts two."""
+    LEN = VCM_FRAME_SYMBOLS if LEN is None else LEN
+    q_min = PLS_SEARCH_Q_MIN if q_min is None else q_min
+    PLS, MET, ENE = np.asarray(PLS, np.int64), np.asarray(MET, np.float32), np.asarray(ENE, np.float32)
+    L = np.asarray(LEN, np.int64).copy()
+    L[(L < 90) | (L % 18 != 0)] = 0
+    K = PLS.size
+    n_sym = K + 89
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(ENE == 0, np.float32(0), (MET * MET) / (np.float32(90) * ENE))
+    hop = L[PLS & 255]
+    ok = np.flatnonzero((hop > 0) & (q >= np.float32(q_min)))
+    count = {}
+    for k in ok[::-1]:                                      # a walk's count from its successor's: the chain goes forward only
+        nxt = int(k + hop[k])
+        count[int(k)] = 1 + (count.get(nxt, 0) if nxt <= n_sym else 0)
+    best = None
+    for k in ok:
+        if k >= L.max():
+            break
+        if count[int(k)] >= 2 and (best is None or count[int(k)] > count[best]):
+            best = int(k)
+    return best
+
+
 def load_ldpc_table(fname: str):
     """-> (row_ptr int32[n_rows+1], addr int32[n_addr]) from dvbs2_amd/data/ldpc/<fname>."""
     rows = []

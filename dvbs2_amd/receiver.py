@@ -674,6 +674,29 @@ class Dvbs2Hip:
         """device addresses (LEN may be None), stream-ordered, no host round trip"""
         self._chk(self.L.dvbs2hip_pls_search_dev(self.h, X, n_sym, LEN, RES, SCORE))
 
+    # ------------------------------------------------------------------ PLHEADER walk (an extension: include/dvbs2hip.h)
+    def pls_walk(self, X, start, LEN=None, q_min=None, max_out=4096):
+        """n_sym symbols and the symbol of a first header -> (OFF, VAL, Q, IDX, CNT, RES = [N, NEXT, STATUS, 0]): the chain of PL frames from `start`, each frame's
+        length taken from its own header (LEN: int32[256] frame lengths by PLS value, None: the library's own table; q_min None: params.PLS_SEARCH_Q_MIN), and IDX the
+        frames grouped by value; the per-frame outputs are cut to N entries"""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1)
+        if LEN is not None:
+            LEN = np.ascontiguousarray(LEN, np.int32)
+            if LEN.size != 256:
+                raise ValueError("LEN has one entry per PLS value: 256")
+        q_min = P.PLS_SEARCH_Q_MIN if q_min is None else q_min
+        n = max(int(max_out), 0)
+        OFF, VAL, Q, IDX = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        CNT, RES = np.zeros(256, np.int32), np.zeros(4, np.int32)
+        self._chk(self.L.dvbs2hip_pls_walk(self.h, _ptr(X), X.size // 2, int(start), _ptr(LEN), float(q_min), int(max_out), _ptr(OFF), _ptr(VAL), _ptr(Q), _ptr(IDX), _ptr(CNT), _ptr(RES)))
+        N = int(RES[0])
+        return OFF[:N], VAL[:N], Q[:N], IDX[:N], CNT, RES
+
+    def pls_walk_dev(self, X, n_sym, start, LEN, q_min, max_out, OFF, VAL, Q, SRC, IDX, CNT, RES):
+        """device addresses (LEN, SRC may be None), stream-ordered, no host round trip; SRC: max_out device pointers, value v's group from sum(CNT[:v]) on"""
+        q_min = P.PLS_SEARCH_Q_MIN if q_min is None else q_min
+        self._chk(self.L.dvbs2hip_pls_walk_dev(self.h, X, int(n_sym), int(start), LEN, float(q_min), int(max_out), OFF, VAL, Q, SRC, IDX, CNT, RES))
+
     # ------------------------------------------------------------------ pilot-aided noise estimator (an extension: include/dvbs2hip.h)
     def estimate_pilots(self, X_N1, scrambled=True):
         """aligned PL frames -> (SIG, Eb_N0, Es_N0) per frame from the header and pilot symbols; scrambled: the frames are as the frame synchronizer delivers them

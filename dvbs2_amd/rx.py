@@ -9,6 +9,10 @@ offsets): README.md:151-169 of the reference.
   python -m dvbs2_amd.rx --src-type USER --src-path K_14232.src --rad-rx-file-path out_tx_noisy.bin -F 8 \
          --mod-cod QPSK-S_8/9 --dec-implem NMS --dec-ite 10 --snk-path /dev/null --rad-rx-no-loop
 
+--mod-cod VCM (an extension): variable coding and modulation -- the MODCOD changes from frame to frame (dvbs2_tx --mod-cod-seq).  The symbols go to vcm.VcmReceiver, which
+follows the PLHEADERs from frame to frame and decodes each frame as its header says; --snk-path gets every decoded frame's bits in stream order, one line sums up.  Pilots
+on, no --wl-phases, --sync-fine, --snk-type TS, --src-type USER or --pls-check.
+
 --mod-cod AUTO (an extension): the MODCOD is read from the PLHEADERs of the head of the file first (detect(): a probe handle, the same front tasks, dvbs2hip_pls_search), one
 line says what was found, and the run goes on as with that MODCOD named.  Constant coding and modulation, pilots on, no --wl-phases.
 """
@@ -29,7 +33,8 @@ from .srcfile import SinkTS, SinkUserBinary, load_src
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="dvbs2_rx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mod-cod", default="QPSK-S_8/9", help="a MODCOD of the table, or AUTO (an extension): read it from the PLHEADERs of the head of the file (constant coding and "
-                                                            "modulation, pilots on; excludes --wl-phases)")
+                                                            "modulation, pilots on; excludes --wl-phases), or VCM (an extension): follow the PLHEADERs from frame to frame and "
+                                                            "decode every frame by its own MODCOD")
     ap.add_argument("-F", "--src-fra", type=int, default=1, dest="n_frames_batch")
     ap.add_argument("--src-type", default="USER", choices=["USER", "NONE"], help="USER: count errors against the pattern file")
     ap.add_argument("--src-path", default="")
@@ -134,7 +139,92 @@ def detect(args, out=sys.stdout) -> dict:
     return dict(modcod=found[0].name, value=value, pilots=found[1], offset=offset, count=count, slots=slots, score=score, symbols=have)
 
 
+def run_vcm(args, out=sys.stdout) -> dict:
+    """--mod-cod VCM: the front tasks as detect() runs them -- a probe handle, RxSequence.front and RxSequence.symbols, then the gain stage on the symbols -- and every
+    read's symbols into vcm.VcmReceiver, which walks the PLHEADER chain and decodes every frame with a handle of the MODCOD its header names.  At the end of a file that
+    does not loop, the last read is filled up with noise of the file's own power and one read of noise follows: the matched filter and the timing task hold the
+    stream's last symbols until more samples come.  -> dict(frames, per_modcod, skipped, losses, ldpc_down, bch_down)"""
+    for flag, given, why in (
+            ("--wl-phases", getattr(args, "wl_phases", False), "the coarse-frequency loop needs one frame length, and a VCM stream has several"),
+            ("--sync-fine", args.sync_fine, "the pilot-aided phase synchronizer runs on the frame synchronizer's aligned frames of one MODCOD"),
+            ("--snk-type TS", getattr(args, "snk_type", "BITS") == "TS", "a BBFRAME's DFL changes with the MODCOD, and the parser is built for one"),
+            ("--src-type USER", args.src_type == "USER" and bool(args.src_path), "a pattern file holds frames of one K_bch"),
+            ("--pls-check", getattr(args, "pls_check", False), "it counts the headers that differ from one expected MODCOD, and here every header is followed")):
+        if given:
+            raise ValueError("--mod-cod VCM excludes %s: %s." % (flag, why))
+    if not args.rad_rx_no_loop and not args.max_frames:
+        raise ValueError("a looping input needs --max-frames")
+    from .vcm import VcmReceiver
+    mc = P.get_modcod("")                                                          # the probe: no task in front of the walk depends on the MODCOD
+    F, n, osf = args.n_frames_batch, mc.pl_frame, args.osf
+    if args.stm_type in ("FAST", "ULTRA") and osf != 2:
+        raise ValueError("--stm-type %s is the Gardner loop at two samples per symbol (--shp-osf 2)" % args.stm_type)
+    vr = VcmReceiver(max_frames=F, n_ite=args.dec_ite, alpha=args.dec_alpha, implem=args.dec_implem, estimator=getattr(args, "est_type", "DVBS2"), device=args.device)
+    rx, fh, snk = vr.base, None, None
+    st = dict(frames=0)
+    try:
+        if args.sim_stats:
+            rx.timing_enable(True)
+        if args.coarse_freq:
+            rx.sync_coarse_set_freq(args.coarse_freq)
+        learn = 0
+        if args.stm_type in ("FAST", "ULTRA"):
+            rx.sync_timing_set_params(args.stm_df, args.stm_nbw, args.stm_dg)
+        if args.stm_type == "ULTRA":
+            rx.sync_timing_set_type("ULTRA", args.stm_hold_size)
+            learn = sum(args.wl_frames) if args.stm_learn_frames is None else args.stm_learn_frames
+        skip = args.timing_offset if args.timing_offset >= 0 else 2 * 20 * osf
+        seq = RxSequence(rx, F, osf, pl_frame=n, agc=not args.no_agc, coarse=bool(args.coarse_freq), timing=args.stm_type, learn_frames=learn, timing_offset=skip, fused=True)
+        fh = open(args.rad_rx_file_path, "rb")
+        snk = open(args.snk_path, "wb") if args.snk_path else None
+        blk = 2 * n * osf * F                                                      # floats of one read
+        rng = np.random.default_rng(0)
+        samples, pushed, total, reads_left = 0, 0, None, None                      # the file's samples taken; symbols pushed; the symbols the file gives, once its end is known
+        while (not args.max_frames or st["frames"] < args.max_frames) and reads_left != 0:
+            x = np.fromfile(fh, np.float32, blk) if reads_left is None else np.zeros(0, np.float32)
+            if x.size < blk:
+                if not args.rad_rx_no_loop:
+                    if fh.tell() < 4 * blk:
+                        raise ValueError("the file holds less than one read of %d complex samples" % (blk // 2))
+                    fh.seek(0)
+                    continue
+                if reads_left is None:
+                    samples += x.size // 2
+                    total, reads_left = max(samples - (skip if args.stm_type == "PERFECT" else 0), 0) // osf, 2
+                    power = float(np.mean(np.square(x, dtype=np.float64))) if x.size else 1.0 / (2 * osf)
+                reads_left -= 1
+                x = np.concatenate([x, (np.sqrt(power) * rng.standard_normal(blk - x.size)).astype(np.float32)])
+            else:
+                samples += blk // 2
+            sym = seq.symbols(seq.front(x))
+            if sym is None:
+                continue
+            if not args.no_agc:
+                sym = rx.agc(sym, n_frames=len(sym), output_energy=1.0)
+            sym = np.asarray(sym, np.float32).reshape(-1)
+            n_new = sym.size // 2
+            for _, _, _, bits, _, _ in vr.push(sym, None if total is None else min(max(total - pushed, 0), n_new)):
+                st["frames"] += 1
+                if snk:
+                    snk.write(np.packbits((bits != 0).astype(np.uint8), bitorder="little").tobytes())      # SinkUserBinary's bytes, frames of any K_bch
+            pushed += n_new
+    finally:
+        if args.sim_stats:
+            from .sim import print_stats
+            print_stats(list(vr.h.values()), out)
+        vr.close()
+        for f in (fh, snk):
+            if f:
+                f.close()
+    st.update(per_modcod=dict(vr.stats["frames"]), skipped=vr.stats["skipped"], losses=vr.stats["losses"], ldpc_down=vr.stats["ldpc_down"], bch_down=vr.stats["bch_down"])
+    print("# VCM: frames %d (%s) | skipped %d | losses of lock %d | LDPC flag down %d | BCH flag down %d" % (
+        st["frames"], ", ".join("%s: %d" % kv for kv in st["per_modcod"].items()) or "none", st["skipped"], st["losses"], st["ldpc_down"], st["bch_down"]), file=out)
+    return st
+
+
 def run(args, out=sys.stdout) -> dict:
+    if args.mod_cod == "VCM":
+        return run_vcm(args, out)
     from .receiver import Dvbs2Hip
     auto = None
     if args.mod_cod == "AUTO":

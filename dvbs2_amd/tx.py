@@ -3,6 +3,9 @@ PL scramble -> shaping filter -> raw IQ file, every stage on the GPU (src/mains/
 
   python -m dvbs2_amd.tx --rad-tx-file-path out_tx.bin -F 8 --src-type USER --src-path K_14232.src --mod-cod QPSK-S_8/9 --n-frames 64
 
+`--mod-cod-seq NAME:COUNT[,NAME:COUNT...]` (an extension) sends variable coding and modulation instead: COUNT frames of each MODCOD in turn, the list over and over
+(vcm.VcmTransmitter), -F frames per call through one shaping filter, and 40 zero symbols behind the last frame so that the file ends whole.
+
 `--tx-tasks` makes the PL frames by the seven TX tasks of the C ABI, one call per task (TxTasks below), instead of the fused tx_bb: the same file.
 """
 from __future__ import annotations
@@ -21,6 +24,8 @@ from .srcfile import SourceAZCW, SourceDone, SourceTS, SourceUser, SourceUserBin
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="dvbs2_tx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mod-cod", default="QPSK-S_8/9")
+    ap.add_argument("--mod-cod-seq", default=None, metavar="NAME:COUNT[,NAME:COUNT...]", help="variable coding and modulation (an extension): COUNT frames of each MODCOD in turn, the list "
+                    "over and over, in place of --mod-cod; every PLHEADER names its frame's MODCOD (the receiver's --mod-cod VCM); the payload source is RAND")
     ap.add_argument("-F", "--src-fra", type=int, default=1, dest="n_frames_batch")
     ap.add_argument("--src-type", default="RAND", choices=["RAND", "USER", "USER_BIN", "AZCW", "TS"],      # DVBS2.cpp:66
                     help="TS (an extension): --src-path is an MPEG transport stream, sent as DVB-S2 BBFRAMEs (BBHEADER, CRC-8 per packet; the receiver's --snk-type TS)")
@@ -75,8 +80,39 @@ class TxTasks:
         return pl.cpu().numpy()
 
 
+def run_vcm(args, out=sys.stdout) -> int:
+    """--mod-cod-seq: -F frames per call of vcm.VcmTransmitter, in schedule order through one shaping filter -> number of frames written"""
+    from .vcm import VcmTransmitter, parse_schedule
+    schedule = parse_schedule(args.mod_cod_seq)
+    if args.src_type != "RAND":
+        raise ValueError("--mod-cod-seq sends frames of several K_bch and fills them with tx_bb's random payloads: --src-type %s is not provided with it" % args.src_type)
+    if args.tx_tasks:
+        raise ValueError("--mod-cod-seq builds its frames with the fused tx_bb of one handle per MODCOD: --tx-tasks is not provided with it")
+    if not args.n_frames and not args.tx_time_limit:
+        raise ValueError("one of --n-frames / --tx-time-limit is needed to end the transmission")
+    F = args.n_frames_batch
+    tx = VcmTransmitter(schedule, device=args.device, seed=args.seed)
+    snd = RadioUserBinary(1, output_filename=args.rad_tx_file_path)
+    t0, frames, per = time.perf_counter(), 0, {}
+    try:
+        while (not args.n_frames or frames < args.n_frames) and (not args.tx_time_limit or (time.perf_counter() - t0) * 1e3 < args.tx_time_limit):
+            n = min(F, args.n_frames - frames) if args.n_frames else F
+            sent, x = tx.samples(n, osf=args.osf)
+            snd.send(x)
+            frames += n
+            for name, _ in sent:
+                per[name] = per.get(name, 0) + 1
+        snd.send(tx.flush(osf=args.osf))                                            # the last frame's last symbols are still in the filter: a file ends whole
+    finally:
+        tx.close(); snd.close()
+    print("(II) %d frames (%s) written in '%s'" % (frames, ", ".join("%s: %d" % kv for kv in per.items()), args.rad_tx_file_path), file=out)
+    return frames
+
+
 def run(args, out=sys.stdout) -> int:
     """-> number of frames written"""
+    if getattr(args, "mod_cod_seq", None) is not None:
+        return run_vcm(args, out)
     from .receiver import Dvbs2Hip
     mc = P.get_modcod(args.mod_cod)
     once = args.src_type in ("USER_BIN", "TS") and args.src_no_loop

@@ -631,8 +631,8 @@ int dvbs2hip_pls_describe(int32_t value, char *name, int32_t name_len, int32_t *
  *   A caller accepts the result or not (dvbs2_amd.params.find_modcod: COUNT >= 2 and SCORE >= q_min SLOTS; results/pls_search/README.md has q_min's measurement).
  * frame_symbols: no handle; pl_frame of the MODCOD of the library's table whose PLS value (pilots on: the only frames the library builds) is `value`, 0 when there is
  *   none -- an even value, a value outside 0..255, a row the table does not have.
- * The search is coherent over the header's 90 symbols and tolerates what the PLS decoder tolerates (a residual carrier of 1e-3 cycles per symbol at 0 dB); it does not
- * walk from header to header (VCM / ACM), and knows nothing of dummy frames.
+ * The search is coherent over the header's 90 symbols and tolerates what the PLS decoder tolerates (a residual carrier of 1e-3 cycles per symbol at 0 dB); it assumes
+ * frames of one length laid back to back (the PLHEADER walk below goes from header to header), and knows nothing of dummy frames.
  * The _dev forms take device addresses, are stream-ordered and make no host round trip: the scan one launch, the search three (scan, chain scores, reduction), none of
  * which waits on another workgroup.  search_dev keeps (PLS, MET, ENE) and the reduction's partial results in the handle's workspace, 12 bytes per offset: it may be
  * recorded in a graph after one call of the same n_sym (and LEN = NULL, if that is used) outside the capture, which allocates.                                       */
@@ -642,6 +642,42 @@ int dvbs2hip_pls_scan_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t 
 int dvbs2hip_pls_search(dvbs2hip_t *h, const float *X, int32_t n_sym, const int32_t *LEN, int32_t *RES, float *SCORE);
 int dvbs2hip_pls_search_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, const int32_t *LEN, int32_t *RES, float *SCORE);
 int dvbs2hip_pls_frame_symbols(int32_t value);
+
+/* ------------------------------------------------------------------ PLHEADER walk (extension: the reference has no such task; built on the PLS decoder above)
+ * A stream whose MODCOD changes from one PL frame to the next (VCM / ACM): from a header at symbol `start`, along the chain of frames whose lengths their own headers
+ * give, where every frame starts and what it is, and the frames grouped by PLS value as pointer tables that go into the located decoders of one handle per MODCOD.
+ * X: as in the search -- float[2 * n_sym], 8-byte aligned, 90 <= n_sym <= DVBS2HIP_PLS_SCAN_MAX_SYM.  0 <= start <= n_sym and 1 <= max_out; anything else is
+ *   DVBS2HIP_EINVAL, and the handle stays usable.  The call depends neither on the handle's MODCOD nor on max_frames.
+ * LEN: int32_t[256] as in the search (a host pointer in the host form, a device pointer in the _dev form, NULL: the library's own table).  LEN'[V] = LEN[V], and 0
+ *   where LEN[V] is below 90 or no multiple of 18.  Every DVB-S2 PL frame length, 90 (S + 1) + 36 P, is a multiple of 18, so every header of a chain sits at start + 18 i.
+ * For an offset c with c + 90 <= n_sym, (PLS, MET, ENE)(c) are what dvbs2hip_pls_decode_dev returns for a frame that starts at X + 2 c, bit for bit, and
+ *   q(c) = (MET * MET) / (90 * ENE) in fp32, each operation rounded once, 0 when ENE = 0: the search's q.
+ * The walk: c = start, j = 0, then in this order
+ *   1. c + 90 > n_sym: stop, END.
+ *   2. V = PLS(c), L = LEN'[V].
+ *   3. L = 0, or not q(c) >= q_min: stop, LOST.
+ *   4. c + L > n_sym: stop, END (the header was seen, the frame is not all there).
+ *   5. j = max_out: stop, FULL.
+ *   6. OFF[j] = c, VAL[j] = V, Q[j] = q(c); c += L, j += 1; again from 1.
+ *   In every stop NEXT = c: the symbol from which the caller carries the tail into its next buffer, or from which it acquires again.
+ * RES: int32_t[4] = {N, NEXT, STATUS, 0}, N = j, STATUS DVBS2HIP_PLS_WALK_END = 0, _LOST = 1, _FULL = 2.  OFF, VAL: int32_t[max_out], Q: float[max_out].
+ * CNT: int32_t[256], the frames per value.  IDX: int32_t[max_out] and SRC: max_out device pointers (_dev form only; may be NULL): the frames grouped by value ascending,
+ *   in stream order within a value -- IDX[g] = j and SRC[g] = X + 2 OFF[j].  Value v's group begins at the sum of CNT[u], u < v, and goes as it stands into
+ *   dvbs2hip_rx_bb_located_dev / dvbs2hip_estimate_pilots_located_dev of a handle of that MODCOD.  Entries at and past N are undefined.
+ * The _dev form takes device addresses, is stream-ordered and makes no host round trip; no workgroup waits on another and nothing spins.  The PLS decoder runs on the
+ *   candidates start + 18 i alone; the chain is then resolved by one lane where it can only be short, and otherwise by pointer doubling over the candidates, about
+ *   2 log2(frames) small launches of integer arithmetic whose result does not depend on any order (dvbs2_amd/csrc/k_pls_walk.hip, results/pls_walk/README.md).  The
+ *   candidates' (PLS, MET, ENE) and the jump table live in the handle's workspace: the call may be recorded in a graph after one call of the same n_sym and max_out
+ *   (and LEN = NULL, if that is used) outside the capture, which allocates for any start.  The host form stages X and returns everything but SRC.
+ * Acquisition -- which `start` -- is the caller's: dvbs2_amd.params.find_vcm_start picks it from one dvbs2hip_pls_scan of a stream's head.  Pilot-less frames and
+ *   carrier recovery across MODCODs are not provided.                                                    */
+#define DVBS2HIP_PLS_WALK_END 0
+#define DVBS2HIP_PLS_WALK_LOST 1
+#define DVBS2HIP_PLS_WALK_FULL 2
+int dvbs2hip_pls_walk(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t start, const int32_t *LEN, float q_min, int32_t max_out, int32_t *OFF, int32_t *VAL, float *Q,
+                      int32_t *IDX, int32_t *CNT, int32_t *RES);
+int dvbs2hip_pls_walk_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t start, const int32_t *LEN, float q_min, int32_t max_out, int32_t *OFF, int32_t *VAL,
+                          float *Q, const float **SRC, int32_t *IDX, int32_t *CNT, int32_t *RES);
 
 /* ------------------------------------------------------------------ pilot-aided noise estimator (extension: the reference has no such task; its only estimator is
  * Estimator_DVBS2, dvbs2hip_estimate above, whose Se = sqrt(|2 m2^2 - m4|) takes every constellation point to have the same modulus: on 16APSK it never reads above
