@@ -563,6 +563,17 @@ int dvbs2hip_bb_descramble(dvbs2hip_t *h, const int32_t *a, int32_t *b, int32_t 
 }
 
 // ------------------------------------------------------------------ fused RX baseband chain
+// the chain's front end (PL descramble -> remove_plh -> estimate -> demodulate -> deinterleave in one launch): frame f read at pl + f 2 pl_frame, or where src[f] points;
+// LLRs in natural order into llr, (sigma, Eb/N0, Es/N0) per frame into est
+static int front_rx_dev(dvbs2hip_t *h, const float *pl, const float *const *src, const float *sigma, float *llr, float *est, int F)
+{
+    Timer tm(h, DVBS2HIP_K_FRONT);
+    FrontKParams fp = front_params(h, pl, sigma, llr, est, F);
+    fp.src = src;
+    HIPCHK(h, front_rx_launch(fp, h->stream));
+    return 0;
+}
+
 static int rx_bb_any_dev(dvbs2hip_t *h, const float *pl, const float *const *src, const float *sigma, int32_t *info, int8_t *cwd_l, int8_t *cwd_b, int32_t F)
 {
     int r = check_frames(h, F); if (r) return r;
@@ -572,12 +583,7 @@ static int rx_bb_any_dev(dvbs2hip_t *h, const float *pl, const float *const *src
     if ((r = ensure(h, B_LLR, (size_t)F * h->N_ldpc * 4, &dllr)) || (r = ensure(h, B_PACKED, (size_t)F * nwords * 4, &dpk)) ||
         (r = ensure(h, B_EST, (size_t)F * 12, &dest)))
         return r;
-    {
-        Timer tm(h, DVBS2HIP_K_FRONT);
-        FrontKParams fp = front_params(h, pl, sigma, (float *)dllr, (float *)dest, F);
-        fp.src = src;
-        HIPCHK(h, front_rx_launch(fp, h->stream));
-    }
+    if ((r = front_rx_dev(h, pl, src, sigma, (float *)dllr, (float *)dest, F))) return r;
     // the LDPC kernel writes the descrambled info bits of every frame straight into the output socket (what the BCH stage outputs for a
     // frame it does not correct: nearly all of them behind a converged LDPC decoder); the BCH stage then only checks the syndromes of the
     // packed hard decisions and flips the bits it corrects -- its 4 K_bch output bytes per frame were 90 % of its time
@@ -612,6 +618,30 @@ int dvbs2hip_rx_bb(dvbs2hip_t *h, const float *pl, const float *sigma, int32_t *
     return host_call(h, F, true, {{sigma, B_SIG, (size_t)F * 4, 0, true, true}, {pl, B_IN, (size_t)F * 2 * h->pl_frame * 4}},
                      {{info, B_INFO, (size_t)F * h->K_bch * 4}, {cwd_l, B_CWD0, (size_t)F, 0, true}, {cwd_b, B_CWD1, (size_t)F, 0, true}},
                      [&](void *const *i, void *const *o, int nf) { return dvbs2hip_rx_bb_dev(h, (const float *)i[1], (const float *)i[0], (int32_t *)o[0], (int8_t *)o[1], (int8_t *)o[2], nf); });
+}
+
+// ------------------------------------------------------------------ the fused chain's front end alone: what rx_bb hands its LDPC decoder, in the caller's sockets
+int dvbs2hip_rx_front_dev(dvbs2hip_t *h, const float *pl, const float *sigma, float *LLR, float *EST, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!pl || !LLR || !EST) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    return front_rx_dev(h, pl, nullptr, sigma, LLR, EST, F);
+}
+
+int dvbs2hip_rx_front_located_dev(dvbs2hip_t *h, const float *const *SRC, const float *sigma, float *LLR, float *EST, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    if (!SRC || !LLR || !EST) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
+    if (h->bw.S > 1) return fail(h, DVBS2HIP_EUNSUPPORTED, "the located form is one stream per handle: with dvbs2hip_set_streams(S > 1) use dvbs2hip_rx_front_dev on the synchronizer's Y_N2");
+    return front_rx_dev(h, nullptr, SRC, sigma, LLR, EST, F);
+}
+
+int dvbs2hip_rx_front(dvbs2hip_t *h, const float *pl, const float *sigma, float *LLR, float *EST, int32_t F)
+{
+    int r = check_frames(h, F); if (r) return r;
+    return host_call(h, F, false, {{sigma, B_SIG, (size_t)F * 4, 0, true, true}, {pl, B_IN, (size_t)F * 2 * h->pl_frame * 4}},
+                     {{LLR, B_LLR, (size_t)F * h->N_ldpc * 4}, {EST, B_EST, (size_t)F * 12}},
+                     [&](void *const *i, void *const *o, int nf) { return dvbs2hip_rx_front_dev(h, (const float *)i[1], (const float *)i[0], (float *)o[0], (float *)o[1], nf); });
 }
 
 // ------------------------------------------------------------------ N1: TX mirror + AWGN

@@ -180,6 +180,9 @@ ABI = {
     "dvbs2hip_rx_bb": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_rx_bb_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_rx_bb_located_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_rx_front": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_rx_front_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "dvbs2hip_rx_front_located_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i]),
     "dvbs2hip_bb_scramble": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_bb_scramble_dev": (C.c_int, [_vp, _vp, _vp, _i]),
     "dvbs2hip_bch_encode": (C.c_int, [_vp, _vp, _vp, _i]),

@@ -433,6 +433,25 @@ class Dvbs2Hip:
         self._chk(self.L.dvbs2hip_rx_bb_dev(self.h, _ptr(pl_frames), _ptr(sigma), _ptr(info), _ptr(cwd_ldpc),
                                             _ptr(cwd_bch), n_frames))
 
+    def rx_front(self, pl_frames, sigma=None):
+        """the fused chain's front end alone -> (LLR f32[F, N_ldpc] in natural order: what rx_bb hands its LDPC decoder, EST f32[F, 3] = sigma, Eb/N0, Es/N0 per frame;
+        with sigma given EST is (sigma[f], 0, 0))"""
+        X, F = self._frames(pl_frames, 2 * self.pl_frame, np.float32)
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float32).ravel(), (F,)))
+        LLR, EST = np.empty((F, self.N_ldpc), dtype=np.float32), np.empty((F, 3), dtype=np.float32)
+        self._chk(self.L.dvbs2hip_rx_front(self.h, _ptr(X), _ptr(sg), _ptr(LLR), _ptr(EST), F))
+        return LLR, EST
+
+    def rx_front_dev(self, pl_frames, sigma, LLR, EST, n_frames):
+        """device addresses (sigma may be None), stream-ordered; the kernels write straight into LLR and EST"""
+        self._chk(self.L.dvbs2hip_rx_front_dev(self.h, _ptr(pl_frames), _ptr(sigma), _ptr(LLR), _ptr(EST), n_frames))
+
+    def rx_front_located_dev(self, SRC, sigma, LLR, EST, n_frames):
+        """as rx_front_dev, frame f read where SRC[f] points (device table of device pointers)"""
+        self._chk(self.L.dvbs2hip_rx_front_located_dev(self.h, _ptr(SRC), _ptr(sigma), _ptr(LLR), _ptr(EST), n_frames))
+
     # ------------------------------------------------------------------ N1: TX mirror + AWGN
     def tx_bb(self, n_frames, info=None, seed=0, sigma=None):
         """-> (info_sent[F,K_bch] int32, pl_frames[F, 2*pl_frame] f32)"""

@@ -334,6 +334,19 @@ int dvbs2hip_rx_bb_dev(dvbs2hip_t *h, const float *pl_frames, const float *sigma
 /* the fused chain reading frame f where SRC[f] points (the table dvbs2hip_sync_frame_locate_dev fills): same outputs as dvbs2hip_rx_bb_dev on the delayed copy */
 int dvbs2hip_rx_bb_located_dev(dvbs2hip_t *h, const float *const *SRC, const float *sigma, int32_t *info_bits, int8_t *cwd_ldpc, int8_t *cwd_bch, int32_t n_frames);
 
+/* ------------------------------------------------------------------ the fused chain's front end alone (a7 -> a6 -> a3 -> a4)
+ * The first launch of dvbs2hip_rx_bb* with its two outputs in the caller's sockets instead of the handle's private buffers: what the chain's LDPC decoder is handed.
+ *   pl_frames: float[n_frames * 2*pl_frame]      SRC: as dvbs2hip_rx_bb_located_dev (DVBS2HIP_EUNSUPPORTED while dvbs2hip_set_streams(S > 1), likewise)
+ *   sigma_in : float[n_frames] or NULL (NULL: the M2M4 estimate of the frame's own payload symbols)
+ *   LLR      : float[n_frames * N_ldpc], natural (code) order: the input of dvbs2hip_ldpc_decode_siho
+ *   EST      : float[n_frames * 3] = (sigma, Eb/N0 dB, Es/N0 dB) per frame; with sigma_in given (sigma_in[f], 0, 0)
+ * Same code path as the chain (one helper launches both), and the kernels write straight into LLR / EST.  Which kernel form runs depends on the sockets as it does inside
+ * the chain: the QPSK pair form needs pl_frames and LLR 16-byte aligned (the located form: LLR only) and takes the one-symbol form otherwise; the handle's own LLR buffer
+ * is 256-byte aligned, so a 16-byte aligned LLR socket selects what dvbs2hip_rx_bb* selects for the same input.  The host form stages through device buffers of the handle. */
+int dvbs2hip_rx_front(dvbs2hip_t *h, const float *pl_frames, const float *sigma_in, float *LLR, float *EST, int32_t n_frames);
+int dvbs2hip_rx_front_dev(dvbs2hip_t *h, const float *pl_frames, const float *sigma_in, float *LLR, float *EST, int32_t n_frames);
+int dvbs2hip_rx_front_located_dev(dvbs2hip_t *h, const float *const *SRC, const float *sigma, float *LLR, float *EST, int32_t n_frames);
+
 /* ------------------------------------------------------------------ N1: TX mirror + AWGN channel (test-signal side)
  * One call = the TX half + channel of TX_RX_BB/main.cpp:75-82 on the device:
  *   Source::generate -> Scrambler_BB::scramble -> Encoder_BCH_DVBS2::encode
