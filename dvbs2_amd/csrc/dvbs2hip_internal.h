@@ -295,6 +295,12 @@ struct SyncTail {
     float *seg;                      // 2 x ceil(max_frames / SYNC_SUB) x n floats of device scratch: per sub-segment of the call's frames {alpha^len, its own average from 0} (k_sync.hip)
 };
 constexpr int SYNC_MAX_SEG = 8, SYNC_SUB = 64;
+// how a one-stream call of F frames of n positions is cut for the average over frames (k_sync.hip): nseg segments of seg_F frames side by side, the last one perhaps shorter;
+// nseg = 1 (seg_F = F) is the single walk.  cap: the most segments allowed (DVBS2HIP_SYNC_SEGMENTS, else SYNC_MAX_SEG); have_scratch: SyncTail::seg is there.
+// With nseg > 1 seg_F is a multiple of the chunk's 96 frames and of SYNC_SUB, and (nseg - 1) (seg_F / SYNC_SUB) sub-segments take a {A, B} each in the scratch.
+// (Frames too long for the thirteen-wave form -- more than 256 workgroups of 64 positions -- are never cut.)
+struct SyncSegPlan { int nseg, seg_F; };
+SyncSegPlan sync_segment_plan(int n, int F, int cap, bool have_scratch);
 // S >= 1 streams per call (dvbs2hip_set_streams): Fs = F / S frames per stream, n_per = n Fs samples; xh / sofh (64 complex), cv (n), yprev (2 n), buff2 (nbuff2), st
 // (SYNC_ST_STRIDE ints) and last_metric (1) hold the streams side by side, SyncTail's per-frame arrays and keys are stream-major like the sockets
 constexpr int SYNC_ST_STRIDE = 4;

@@ -352,7 +352,8 @@ constexpr int SYM_NC = 1;  // chain waves per workgroup (1, 2 or 4: 64 / NC posi
 // c_end = A c_start + B with A = al^len and B = the segment's own result from c_start = 0.  So: a first kernel (sync_seg_partial_kernel) forms {A, B} of every segment but the
 // last, all segments side by side; then every segment runs THIS kernel on its own workgroups (grid y), its start value folded from the carried average and the {A, B} of the
 // segments before it.  Same recurrence, same operations inside a segment; across a seam the start value is rounded differently from the one-wave walk (al^len c + B instead of
-// len steps): ~1e-7 relative, far inside the metric's 2e-4 bar.  DVBS2HIP_SYNC_SEGMENTS=1 keeps the single walk.
+// len steps): at most 1 ulp of the metric at alpha 0.9 and 0.99, 10 ulp (6.3e-7 relative) at 0.999, and no further from float64 than the single walk is
+// (tests/test_sync_seg_gpu.py holds it to 4 x the walk's own error; results/sync_segments/README.md).  DVBS2HIP_SYNC_SEGMENTS=1 keeps the single walk.
 // {A, B} per SUB-SEGMENT of SYNC_SUB frames (a segment = seg_F / SYNC_SUB of them): one lane per position walks 64 frames with all of their loads in flight -- thousands of
 // short walks side by side instead of a few long ones (the first form, one walk of 1024 frames per segment with 8 loads in flight, cost 49 us more than it saved)
 __global__ void __launch_bounds__(64)
@@ -1158,6 +1159,17 @@ hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, c
     return hipGetLastError();
 }
 
+// segments of the call's frames side by side while they fit the chip (one workgroup per CU) and stay long enough to be worth a seam (>= 768 frames each)
+SyncSegPlan sync_segment_plan(int n, int F, int cap, bool have_scratch)
+{
+    const int nwg = (n + 63) / 64;
+    int nseg = cap <= 1 || !have_scratch ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);
+    int seg_F = F;
+    if (nseg > 1) { seg_F = ((F + nseg - 1) / nseg + 191) / 192 * 192; nseg = (F + seg_F - 1) / seg_F; }      // (a multiple of the chunk's 96 frames and of SYNC_SUB)
+    if (nseg <= 1) { nseg = 1; seg_F = F; }
+    return {nseg, seg_F};
+}
+
 // the average over frames with the arg max of every frame, then the per-frame sockets / delay-line table
 static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
 {
@@ -1172,13 +1184,10 @@ static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, fl
     // sample there: QPSK-N 1024 frames 42-45 us in the four-wave form, 65 us in this one)
     static const bool four = getenv("DVBS2HIP_SYNC_ARGMAX4") != nullptr;      // development: round 3's kernel for every frame length
     if (!four && nwg <= SYNC_UF96_MAX_WG) {
-        // segments of the call's frames side by side while they fit the chip (one workgroup per CU) and stay long enough to be worth a seam (>= 768 frames each)
         static const int cap = getenv("DVBS2HIP_SYNC_SEGMENTS") ? atoi(getenv("DVBS2HIP_SYNC_SEGMENTS")) : SYNC_MAX_SEG;      // (development: 1 = the single walk)
-        int nseg = cap <= 1 || !t.seg ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);
-        int seg_F = F;
-        if (nseg > 1) { seg_F = ((F + nseg - 1) / nseg + 191) / 192 * 192; nseg = (F + seg_F - 1) / seg_F; }      // (a multiple of the chunk's 96 frames and of SYNC_SUB)
+        const SyncSegPlan sp = sync_segment_plan(n, F, cap, t.seg != nullptr);
+        const int nseg = sp.nseg, seg_F = sp.seg_F;
         if (nseg > 1) hipLaunchKernelGGL(sync_seg_partial_kernel, dim3(nwg, (nseg - 1) * (seg_F / SYNC_SUB)), dim3(64), 0, s, (const float *)corr, t.seg, n, F, alpha, end_vec);
-        else { nseg = 1; seg_F = F; }
         hipLaunchKernelGGL(sync_metric_argmax_kernel<96>, dim3(nwg, nseg), dim3(64 * (SYM_NC + 12)), 0, s, cv, corr, t.keys, n, F, alpha, end_vec, (const float *)t.seg, seg_F);
     }
     else hipLaunchKernelGGL(sync_metric_argmax4_kernel, dim3(nwg), dim3(256), 0, s, cv, corr, t.keys, n, F, alpha, end_vec);

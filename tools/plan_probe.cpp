@@ -113,8 +113,22 @@ static int insts_main()
     return 0;
 }
 
+// `plan_probe syncseg N F CAP [N F CAP ..]`: a line `nseg seg_F` per triple -- how sync_segment_plan (k_sync.hip: the function the frame synchronizer's dispatch calls, the
+// handle's scratch present) cuts a one-stream call of F frames of N positions for the average over frames when at most CAP segments are allowed.
+// tests/test_sync_seg_plan.py and tests/test_sync_seg_gpu.py read it.
+static int syncseg_main(int argc, char **argv)
+{
+    if (argc < 5 || (argc - 2) % 3) { std::fprintf(stderr, "usage: plan_probe syncseg N F CAP [N F CAP ..]\n"); return 2; }
+    for (int i = 2; i + 2 < argc; i += 3) {
+        const SyncSegPlan p = sync_segment_plan(atoi(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), true);
+        std::printf("%d %d\n", p.nseg, p.seg_F);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "syncseg")) return syncseg_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "digest")) return digest_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "choice")) return choice_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "insts")) return insts_main();
