@@ -38,6 +38,12 @@ int dvbs2::bw_hist(dvbs2hip_t *h, PingPong<float> **hist)
 extern "C" {
 
 // ------------------------------------------------------------------ a5
+// the kernel of a matched-filter call of S streams of n_per samples (fir_choose, rx_dispatch.h); dvbs2hip_set_filter_kernel(h, DVBS2HIP_FIR_VALU) keeps the vector kernel
+static FirChoice fir_choice(dvbs2hip_t *h, const float *X, const float *Y, long long n_per, int S)
+{
+    return fir_choose(h->fir_T, n_per, S, ptr_align(X), ptr_align(Y), h->fir_kernel != DVBS2HIP_FIR_VALU && h->d_fir_afrag);
+}
+
 // bw.S streams per call: every stream its own sample stream of n_cplx F/S samples, with its own memory
 int dvbs2hip_filter_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx, int32_t F)
 {
@@ -48,8 +54,8 @@ int dvbs2hip_filter_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n_cplx,
     PingPong<float> *hist;
     if ((r = bw_hist(h, &hist))) return r;
     Timer tm(h, DVBS2HIP_K_FIR);
-    HIPCHK(h, fir_launch(X, Y, hist->in(), hist->out(), h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
-                         (long long)n_cplx * (F / h->bw.S), h->bw.S, h->stream));
+    const long long n_per = (long long)n_cplx * (F / h->bw.S);
+    HIPCHK(h, fir_launch(X, Y, hist->in(), hist->out(), h->d_taps_rev, h->d_fir_afrag, h->fir_T, n_per, h->bw.S, fir_choice(h, X, Y, n_per, h->bw.S), h->stream));
     hist->flip();
     return 0;
 }
@@ -103,8 +109,8 @@ int dvbs2hip_filter2_dev(dvbs2hip_t *h, const float *X, const float *Yh, float *
     if ((r = ensure(h, B_FLT2, row * F, &tmp))) return r;
     {   // the upper part of a frame reads nothing before the frame (split >= n_taps - 1): the state is neither used nor advanced
         Timer tm(h, DVBS2HIP_K_FIR);
-        HIPCHK(h, fir_launch(X, (float *)tmp, h->d_hist_zero, h->d_hist_junk, h->d_taps_rev, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_fir_afrag, h->fir_T,
-                             (long long)n_cplx * F, 1, h->stream));
+        HIPCHK(h, fir_launch(X, (float *)tmp, h->d_hist_zero, h->d_hist_junk, h->d_taps_rev, h->d_fir_afrag, h->fir_T, (long long)n_cplx * F, 1,
+                             fir_choice(h, X, (const float *)tmp, (long long)n_cplx * F, 1), h->stream));
     }
     const size_t lo = sizeof(float) * 2 * (size_t)split;
     if (Y != Yh) HIPCHK(h, hipMemcpy2DAsync(Y, row, Yh, row, lo, (size_t)F, hipMemcpyDeviceToDevice, h->stream));       // std::copy(Y_N2h, ..) :224
@@ -157,8 +163,8 @@ int dvbs2hip_shape_filter_dev(dvbs2hip_t *h, const float *X, float *Y, int32_t n
     if (h->fir_T <= 0) return fail(h, DVBS2HIP_EUNSUPPORTED, "handle was created without filter taps");
     if (n_cplx < 1) return fail(h, DVBS2HIP_EINVAL, "'n_cplx' has to be greater than 0");
     Timer tm(h, DVBS2HIP_K_FIR);
-    HIPCHK(h, upfir_launch(X, Y, h->d_uphist.in(), h->d_uphist.out(), h->d_taps, h->fir_kernel == DVBS2HIP_FIR_VALU ? nullptr : h->d_upfir_afrag, h->fir_T, h->fir_osf,
-                           (long long)n_cplx * F, h->stream));
+    const FirChoice ch = upfir_choose(h->fir_T, h->fir_osf, (long long)n_cplx * F, ptr_align(X), ptr_align(Y), h->fir_kernel != DVBS2HIP_FIR_VALU && h->d_upfir_afrag);
+    HIPCHK(h, upfir_launch(X, Y, h->d_uphist.in(), h->d_uphist.out(), h->d_taps, h->d_upfir_afrag, h->fir_T, h->fir_osf, (long long)n_cplx * F, ch, h->stream));
     h->d_uphist.flip();
     return 0;
 }

@@ -5,9 +5,6 @@
 
 using namespace dvbs2;
 
-// levels up to which one lane follows the chain instead: results/pls_walk/README.md has the measurement
-constexpr int PLSW_LANE_LEVELS = 5;
-
 // the candidates start + 18 i that have a whole header in front of n_sym
 static int plsw_candidates(int32_t n_sym, int32_t start) { return start + 90 <= n_sym ? (n_sym - 90 - start) / 18 + 1 : 0; }
 
@@ -21,15 +18,6 @@ static int plsw_min_hop(bool callers_table)
         return m ? m / 18 : 90 / 18;
     }();
     return lib;
-}
-
-// DVBS2HIP_PLS_WALK_FORM = lane | levels: a measurement aid (tools/bench_pls_walk.py times the two forms on one buffer); unset, the number of levels decides
-static bool plsw_lane(int K)
-{
-    const char *f = getenv("DVBS2HIP_PLS_WALK_FORM");
-    if (f && !strcmp(f, "lane")) return true;
-    if (f && !strcmp(f, "levels")) return false;
-    return K <= PLSW_LANE_LEVELS;
 }
 
 static int plsw_check(dvbs2hip_t *h, int32_t n_sym, int32_t start, int32_t max_out)
@@ -55,7 +43,7 @@ static int plsw_dev(dvbs2hip_t *h, const float *X, int32_t n_sym, int32_t start,
     if ((r = plss_ensure(h, B_PLSW_WORK, pls_walk_work_bytes(M0, pls_walk_levels(M0, min_hop, max_out)), &work))) return r;
     Timer tm(h, DVBS2HIP_K_MISC);
     if (M > 0) HIPCHK(h, pls_decode_launch(X + 2 * (size_t)start, nullptr, 18, (int32_t *)work, (float *)work + M, (float *)work + 2 * (size_t)M, M, h->stream));
-    HIPCHK(h, pls_walk_launch(X, n_sym, start, M, K, plsw_lane(K), LEN, q_min, max_out, work, OFF, VAL, Q, SRC, IDX, CNT, RES, h->stream));
+    HIPCHK(h, pls_walk_launch(X, n_sym, start, M, K, pls_walk_choose(K), LEN, q_min, max_out, work, OFF, VAL, Q, SRC, IDX, CNT, RES, h->stream));
     return 0;
 }
 

@@ -16,7 +16,7 @@ static int lr_check_recover(dvbs2hip_t *h, int slot)
     auto it = h->bufs.find(B_LR_TMP0 + slot);
     if (!ls.x || !ls.y || it == h->bufs.end() || !it->second.p || it->second.bytes < sizeof(float) * 4 * (size_t)ls.F)
         return fail(h, DVBS2HIP_EHIP, "L&R: a rotating workgroup timed out waiting for the recurrence and the call cannot be repeated (buffers unknown); re-run it with DVBS2HIP_LR=unfused");
-    HIPCHK(h, sff_lr_recover(ls.x, ls.y, (float *)it->second.p, ls.n, ls.F, h->stream));
+    HIPCHK(h, sff_lr_recover(ls.x, ls.y, (float *)it->second.p, ls.n, ls.F, rotate_choose(ls.n, ptr_align(ls.x), ptr_align(ls.y)), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -39,11 +39,10 @@ int dvbs2::lr_check_all(dvbs2hip_t *h)
 extern "C" {
 
 // ------------------------------------------------------------------ N4: frame synchronizer (Synchronizer_frame_DVBS2_fast)
-// DVBS2HIP_SYNC=valu (read at every call): the correlators as fp32 vector sums in the reference's order instead of the matrix cores
-static const uint16_t *sfm_frag(dvbs2hip_t *h)
+// the kernels of a call of Fs frames per stream (sync_choose, rx_dispatch.h, which reads DVBS2HIP_SYNC* at every call)
+static SyncChoice sfm_choice(dvbs2hip_t *h, const float *X_N1, int Fs, bool one_task, bool located)
 {
-    const char *e = getenv("DVBS2HIP_SYNC");
-    return e && !strcmp(e, "valu") ? nullptr : h->sfm.frag;
+    return sync_choose({h->pl_frame, Fs, h->bw.S, h->sfm.nbuff2, ptr_align(X_N1), h->sfm.frag != nullptr, h->sfm.keys != nullptr, one_task, located});
 }
 
 // every stream the state holds (S.n_alloc of them, side by side: dvbs2hip_set_streams)
@@ -146,7 +145,8 @@ int dvbs2hip_sync_frame_synchronize1_dev(dvbs2hip_t *h, const float *X_N1, float
     auto &S = h->sfm;
     Timer tm(h, DVBS2HIP_K_MISC);
     // every stream from its own 64-sample memory
-    HIPCHK(h, sync_corr_launch(X_N1, S.xh.in(), S.xh.out(), sfm_frag(h), cor_SOF, cor_PLSC, (long long)h->pl_frame * (F / h->bw.S), h->bw.S, h->stream));
+    const int Fs = F / h->bw.S;
+    HIPCHK(h, sync_corr_launch(X_N1, S.xh.in(), S.xh.out(), S.frag, cor_SOF, cor_PLSC, (long long)h->pl_frame * Fs, h->bw.S, sfm_choice(h, X_N1, Fs, false, false), h->stream));
     S.xh.flip();
     return 0;
 }
@@ -163,6 +163,14 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
     if ((r = sfm_ready(h))) return r;
     auto &S = h->sfm;
     const int n = h->pl_frame;
+    const SyncChoice ch = sfm_choice(h, X_N1, Fs, fused, SRC != nullptr);
+    if (fused && !ch.fused) {      // the two tasks through device scratch (same numbers)
+        const size_t nb = sizeof(float) * 2 * (size_t)n * F;
+        void *cs, *cp;
+        if ((r = ensure(h, B_SFM_SOF, nb, &cs)) || (r = ensure(h, B_SFM_PLSC, nb, &cp))) return r;
+        if ((r = dvbs2hip_sync_frame_synchronize1_dev(h, X_N1, (float *)cs, (float *)cp, F))) return r;
+        return dvbs2hip_sync_frame_synchronize2_dev(h, X_N1, (const float *)cs, (const float *)cp, DEL, FLG, TRI, Y_N2, F);
+    }
     void *corr, *met;
     void *dtab;
     if ((r = ensure(h, B_SFM_CORR, sizeof(float) * (size_t)n * F, &corr)) || (r = ensure(h, B_SFM_MET, sizeof(float) * (size_t)F, &met)) ||
@@ -172,10 +180,10 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
     const SyncTail tail{S.keys, delay, (float *)met, FLG, S.trigger, (int32_t *)dtab, S.metric, reinterpret_cast<float *>(S.keys + (size_t)h->max_frames * (size_t)((n + 63) / 64))};
     // every stream on its own state; frame 0 of a stream continues from that stream's previous call
     if (fused) {
-        HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh.in(), S.xh.out(), sfm_frag(h), S.sofh.in(), S.sofh.out(), S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
+        HIPCHK(h, sync_corr_metric_launch(X_N1, S.xh.in(), S.xh.out(), S.frag, S.sofh.in(), S.sofh.out(), S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, ch, h->stream));
         S.xh.flip();
     } else
-        HIPCHK(h, sync_metric_launch(cor_SOF, S.sofh.in(), S.sofh.out(), cor_PLSC, S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, h->stream));
+        HIPCHK(h, sync_metric_launch(cor_SOF, S.sofh.in(), S.sofh.out(), cor_PLSC, S.cv, (float *)corr, tail, n, Fs, NS, S.alpha, S.vec_width, ch, h->stream));
     S.sofh.flip();
     // the delay line is a recurrence from frame to frame made of copies only: resolved per output sample, one launch (k_sync.hip)
     void *need = nullptr;
@@ -184,8 +192,8 @@ static int sfm_sync2(dvbs2hip_t *h, const float *X_N1, const float *cor_SOF, con
         if ((r = ensure(h, B_SFM_SCR, sizeof(float) * 2 * (size_t)n * F, &scr)) || (r = ensure(h, B_SFM_NEED, sizeof(int32_t) * ((size_t)F + 2), &need))) return r;
         Y_N2 = (float *)scr;
     }
-    HIPCHK(h, sync_vdelay_launch(X_N1, S.yprev.in(), S.yprev.out(), Y_N2, S.buff2.in(), S.buff2.out(), S.st.in(), S.st.out(), (const int32_t *)dtab, n, S.nbuff2, Fs, NS, h->stream,
-                                 (int32_t *)need, SRC));
+    HIPCHK(h, sync_vdelay_launch(X_N1, S.yprev.in(), S.yprev.out(), Y_N2, S.buff2.in(), S.buff2.out(), S.st.in(), S.st.out(), (const int32_t *)dtab, n, S.nbuff2, Fs, NS, ch,
+                                 h->stream, (int32_t *)need, SRC));
     S.buff2.flip(), S.st.flip();
     S.yprev.flip();
     return 0;
@@ -200,15 +208,8 @@ int dvbs2hip_sync_frame_synchronize2_dev(dvbs2hip_t *h, const float *X_N1, const
 
 int dvbs2hip_sync_frame_synchronize_dev(dvbs2hip_t *h, const float *X_N1, int32_t *DEL, int32_t *FLG, float *TRI, float *Y_N2, int32_t F)
 {
-    // the one-task form: the two correlations are no sockets here and stay on chip (sync_corr_m_kernel); DVBS2HIP_SYNC_UNFUSED keeps
-    // the two-task path through device scratch (same numbers)
-    if (!getenv("DVBS2HIP_SYNC_UNFUSED")) return sfm_sync2(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, Y_N2, F);
-    int r = check_frames(h, F); if (r) return r;
-    const size_t nb = sizeof(float) * 2 * (size_t)h->pl_frame * F;
-    void *cs, *cp;
-    if ((r = ensure(h, B_SFM_SOF, nb, &cs)) || (r = ensure(h, B_SFM_PLSC, nb, &cp))) return r;
-    if ((r = dvbs2hip_sync_frame_synchronize1_dev(h, X_N1, (float *)cs, (float *)cp, F))) return r;
-    return dvbs2hip_sync_frame_synchronize2_dev(h, X_N1, (const float *)cs, (const float *)cp, DEL, FLG, TRI, Y_N2, F);
+    // the one-task form: the two correlations are no sockets here and stay on chip (sync_corr_m_kernel), unless sync_choose says otherwise
+    return sfm_sync2(h, X_N1, nullptr, nullptr, DEL, FLG, TRI, Y_N2, F);
 }
 
 // (round 5) the frame synchronizer for a consumer of this library: instead of the delayed copy Y_N2 it returns, per frame, WHERE the aligned frame starts -- inside X_N1 for a
@@ -287,8 +288,8 @@ static int sff_call(dvbs2hip_t *h, bool lr, bool host, const float *X_N1, float 
     if ((r = ensure(h, lr ? B_LR_TMP0 + slot : B_SFF_TMP, sizeof(float) * 4 * (size_t)F, &tmp))) return r;
     auto launch = [&](const float *x, float *frq, float *phs, float *y) {
         Timer tm(h, DVBS2HIP_K_MISC);
-        if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, NS, h->lr_alpha, h->lr_err_dev + slot, h->stream));
-        else HIPCHK(h, sff_fp_launch(x, y, (float *)tmp, frq, phs, n, F, h->stream));
+        if (lr) HIPCHK(h, sff_lr_launch(x, y, h->d_lr_R, (float *)tmp, frq, phs, n, F, NS, h->lr_alpha, h->lr_err_dev + slot, lr_choose(NS, n, ptr_align(x), ptr_align(y)), h->stream));
+        else HIPCHK(h, sff_fp_launch(x, y, (float *)tmp, frq, phs, n, F, rotate_choose(n, ptr_align(x), ptr_align(y)), h->stream));
         if (lr) { auto &ls = h->lr_slot[slot]; ls.x = x; ls.y = y; ls.n = n; ls.F = F; ls.pending = !host && NS == 1; }      // (NS > 1 is three kernels: no waiting workgroup, nothing to look at later)
         return 0;
     };

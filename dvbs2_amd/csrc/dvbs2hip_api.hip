@@ -412,7 +412,7 @@ static int bch_dev(dvbs2hip_t *h, const int32_t *Y, const uint32_t *packed, int8
     p.in_bits = Y; p.in_packed = packed; p.out_bits = V; p.cwd = CWD; p.n_frames = F; p.patch_only = patch_only ? 1 : 0; p.flag = flag;
     p.prbs = descramble ? h->bch.d_prbs : nullptr;
     Timer tm(h, DVBS2HIP_K_BCH);
-    HIPCHK(h, bch_launch(h->bch, p, h->stream));
+    HIPCHK(h, bch_launch(h->bch, p, bch_grid(), h->stream));
     return 0;
 }
 
@@ -442,12 +442,19 @@ static FrontKParams front_params(dvbs2hip_t *h, const float *in, const float *si
     return p;
 }
 
+// the call's facts for front_choose (rx_dispatch.h): plain values, the sockets as their alignment
+static FrontChoice front_choice(const FrontKParams &p, bool from_pl, bool deinterleave)
+{
+    return front_choose({p.bps, p.sep != 0, p.itl_cols, p.n_sym, p.pl_frame, p.n_frames, ptr_align(p.in), ptr_align(p.llr), p.src != nullptr, from_pl, deinterleave});
+}
+
 static int demod_any_dev(dvbs2hip_t *h, const float *CP, const float *Y1, float *Y2, bool deitl, int F)
 {
     int r = check_frames(h, F); if (r) return r;
     if (!CP || !Y1 || !Y2) return fail(h, DVBS2HIP_EINVAL, "null socket pointer");
     Timer tm(h, DVBS2HIP_K_DEMAP);
-    HIPCHK(h, demod_launch(front_params(h, Y1, CP, Y2, nullptr, F), deitl, h->stream));
+    const FrontKParams fp = front_params(h, Y1, CP, Y2, nullptr, F);
+    HIPCHK(h, front_launch(fp, front_choice(fp, false, deitl), h->stream));
     return 0;
 }
 
@@ -570,7 +577,7 @@ static int front_rx_dev(dvbs2hip_t *h, const float *pl, const float *const *src,
     Timer tm(h, DVBS2HIP_K_FRONT);
     FrontKParams fp = front_params(h, pl, sigma, llr, est, F);
     fp.src = src;
-    HIPCHK(h, front_rx_launch(fp, h->stream));
+    HIPCHK(h, front_launch(fp, front_choice(fp, true, true), h->stream));
     return 0;
 }
 

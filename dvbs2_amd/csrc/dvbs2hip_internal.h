@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/dvbs2hip.h"
 #include "ldpc_layer_table.h"
+#include "rx_dispatch.h"
 
 namespace dvbs2 {
 
@@ -207,7 +208,7 @@ struct BchKParams {
     int32_t N, K, m, n, t, n_frames;
 };
 std::string bch_build_plan(BchPlan &pl, int m, const int32_t *prim, int t, int N, int K);
-hipError_t bch_launch(const BchPlan &pl, BchKParams p, hipStream_t s);
+hipError_t bch_launch(const BchPlan &pl, BchKParams p, int grid_cap, hipStream_t s);      // grid_cap: bch_grid() (rx_dispatch.h)
 
 // ---------------------------------------------------------------- front end (a3, a4, a6, a7)
 struct FrontKParams {
@@ -226,8 +227,8 @@ struct FrontKParams {
     float sep_g[2], sep_h[2];
 };
 hipError_t frame_order_launch(const float *llr, float *metric, uint32_t *order, int F, int N, hipStream_t s);      // k_ldpc_generic.hip: the work queue's order for launches with the stopping rule (noisiest frames first)
-hipError_t front_rx_launch(FrontKParams p, hipStream_t s);                     // a7+a6+a3+a4 fused, in = pl frames
-hipError_t demod_launch(FrontKParams p, bool deinterleave, hipStream_t s);     // a3 (+a4), in = xfec frames, sigma_in required
+// a7+a6+a3+a4 fused (in = pl frames) or a3 (+a4) (in = xfec frames, sigma_in required), in the form front_choose chose (rx_dispatch.h)
+hipError_t front_launch(FrontKParams p, const FrontChoice &ch, hipStream_t s);
 hipError_t deinterleave_launch(const float *itl, float *nat, int N, int cols, int order, int F, hipStream_t s);
 hipError_t estimate_launch(const float *x, float *sig, float *ebn0, float *esn0, int n_sym, float code_rate,
                            int bps, int F, hipStream_t s);
@@ -271,18 +272,16 @@ hipError_t tx_pl_scramble_launch(const float *X, float *Y, const uint8_t *seq, i
 std::vector<uint8_t> bch_generator(const BchPlan &pl);
 
 // ---------------------------------------------------------------- FIR (a5)
-// S >= 1 streams of n_per samples per call (dvbs2hip_set_streams), stream s at x + 2 s n_per; the memories of T - 1 samples side by side in hist_in / hist_out
-hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
+// S >= 1 streams of n_per samples per call (dvbs2hip_set_streams), stream s at x + 2 s n_per; the memories of T - 1 samples side by side in hist_in / hist_out.
+// ch: fir_choose / upfir_choose (rx_dispatch.h)
+hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag, int T, long long n_per, int S, const FirChoice &ch,
+                      hipStream_t s);
+hipError_t upfir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps, const uint16_t *afrag2, int T, int osf, long long n_in, const FirChoice &ch,
+                        hipStream_t s);
 // matrix-core form (k_fir_mfma.hip): bf16 x 3 split operands, fp32 accumulation
 std::vector<uint16_t> fir_mfma_afrag(const float *taps_rev, int T);
-bool fir_mfma_usable(const float *x, const float *y, int T, long long n_per, int S);
-hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s);
-
-hipError_t upfir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps, const uint16_t *afrag2, int T, int osf,
-                        long long n_in, hipStream_t s);
 std::vector<uint16_t> upfir_mfma_afrag(const float *taps, int T);
-bool upfir_mfma_usable(const float *x, const float *y, int T, int osf, long long n_in);
-hipError_t upfir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag2, int T, long long n_in, hipStream_t s);
+hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n, const FirChoice &ch, hipStream_t s);
 hipError_t decimate_launch(const float *x, float *y, long long n_out, int osf, long long offset, long long n_in, hipStream_t s);
 hipError_t awgn_launch(const float *x, float *y, const float *sigma, unsigned long long seed, long long n_pairs, int F, hipStream_t s);
 
@@ -294,34 +293,29 @@ struct SyncTail {
     int32_t *Dtab; float *last_metric;
     float *seg;                      // 2 x ceil(max_frames / SYNC_SUB) x n floats of device scratch: per sub-segment of the call's frames {alpha^len, its own average from 0} (k_sync.hip)
 };
-constexpr int SYNC_MAX_SEG = 8, SYNC_SUB = 64;
-// how a one-stream call of F frames of n positions is cut for the average over frames (k_sync.hip): nseg segments of seg_F frames side by side, the last one perhaps shorter;
-// nseg = 1 (seg_F = F) is the single walk.  cap: the most segments allowed (DVBS2HIP_SYNC_SEGMENTS, else SYNC_MAX_SEG); have_scratch: SyncTail::seg is there.
-// With nseg > 1 seg_F is a multiple of the chunk's 96 frames and of SYNC_SUB, and (nseg - 1) (seg_F / SYNC_SUB) sub-segments take a {A, B} each in the scratch.
-// (Frames too long for the thirteen-wave form -- more than 256 workgroups of 64 positions -- are never cut.)
-struct SyncSegPlan { int nseg, seg_F; };
-SyncSegPlan sync_segment_plan(int n, int F, int cap, bool have_scratch);
+// (SYNC_MAX_SEG, SYNC_SUB, SyncSegPlan and sync_segment_plan: rx_dispatch.h)
 // S >= 1 streams per call (dvbs2hip_set_streams): Fs = F / S frames per stream, n_per = n Fs samples; xh / sofh (64 complex), cv (n), yprev (2 n), buff2 (nbuff2), st
 // (SYNC_ST_STRIDE ints) and last_metric (1) hold the streams side by side, SyncTail's per-frame arrays and keys are stream-major like the sockets
 constexpr int SYNC_ST_STRIDE = 4;
-hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
+// ch: what sync_choose / lr_choose / rotate_choose (rx_dispatch.h) chose for the call
+hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, const SyncChoice &ch,
+                            hipStream_t s);
 std::vector<uint16_t> sync_mfma_frag(const float *sof25, const float *plsc64);       // k_sync_mfma.hip: band fragments of the two correlators
-bool sync_mfma_usable(const float *x, const void *frag, long long n_per, int S);
 // corr != null: the one-task form (sofh_in / sofh_out its memories), else both correlations go to their sockets
 hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                 float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s);
+                                 float *cor_sof, float *cor_plsc, long long n_per, int S, unsigned grid, hipStream_t s);
 std::vector<uint16_t> sync_frag_default();                                            // k_sync.hip: the fragments of conj_SOF / conj_PLSC
 hipError_t sync_corr_metric_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
+                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, const SyncChoice &ch, hipStream_t s);
 hipError_t sync_metric_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s);
+                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, const SyncChoice &ch, hipStream_t s);
 // list / src: the located form (S == 1 only)
 hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s, int32_t *list = nullptr, const float **src = nullptr);
-// S == 1: recurrence and rotation in one launch, err_dev its error word; S > 1: three kernels, err_dev unused
-hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, hipStream_t s);
-hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hipStream_t s);
-hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, hipStream_t s);
+                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, const SyncChoice &ch, hipStream_t s, int32_t *list = nullptr, const float **src = nullptr);
+// one launch (recurrence and rotation, err_dev its error word) or three (err_dev unused)
+hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, const LrChoice &ch, hipStream_t s);
+hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, bool pair, hipStream_t s);
+hipError_t sff_fp_launch(const float *X, float *Y, float *tmp, float *FRQ, float *PHS, int n, int F, bool pair, hipStream_t s);
 // k_pls.hip: the PLHEADER of frame f, at X + 2 f stride_cplx floats or at SRC[f] (8-byte aligned), decoded to V = b0 128 + .. + b6 2 + p; MET, ENE may be null
 hipError_t pls_decode_launch(const float *X, const float *const *SRC, size_t stride_cplx, int32_t *PLS, float *MET, float *ENE, int F, hipStream_t s);
 // k_pls_search.hip: the same decoder at every symbol offset k of X (n_sym complex symbols, 8-byte aligned), K = n_sym - 89 outputs, bit for bit what pls_decode_launch

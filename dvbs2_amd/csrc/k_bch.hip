@@ -346,15 +346,13 @@ bch_decode_kernel(const BchKParams p)
     }
 }
 
-hipError_t bch_launch(const BchPlan &pl, BchKParams p, hipStream_t s)
+hipError_t bch_launch(const BchPlan &pl, BchKParams p, int grid_cap, hipStream_t s)
 {
     p.exp_ = pl.d_exp; p.log_ = pl.d_log; p.syn_tab = pl.d_syn_tab;
     p.N = pl.N; p.K = pl.K; p.m = pl.m; p.n = pl.n; p.t = pl.t;
     const size_t lds = (size_t)((pl.N + 31) / 32) * 4 + (256 + (size_t)768 * pl.t) * 2;
-    // persistent grid (about the number of workgroups the chip holds at once): the tables are staged into LDS once per
-    // workgroup, not once per frame
-    static const int cap = [] { const char *e = getenv("DVBS2HIP_BCH_GRID"); return e ? atoi(e) : 2048; }();
-    const int grid = p.n_frames < cap ? p.n_frames : cap;
+    // persistent grid (bch_grid, rx_dispatch.h): the tables are staged into LDS once per workgroup, not once per frame
+    const int grid = p.n_frames < grid_cap ? p.n_frames : grid_cap;
     hipLaunchKernelGGL(bch_decode_kernel, dim3(grid), dim3(BCH_THREADS), lds, s, p);
     return hipGetLastError();
 }

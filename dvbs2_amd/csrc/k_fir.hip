@@ -17,15 +17,10 @@
 // the structural zeros; the matrix-core form that does pay -- bf16 x 3 split operands -- is k_fir_mfma.hip, the default
 // for T <= 81, and this kernel serves longer filters, unaligned sockets and DVBS2HIP_FIR=valu.
 #include "dvbs2hip_internal.h"
-#include <cstdlib>
 
 namespace dvbs2 {
 
-constexpr int FIR_THREADS = 256;
-constexpr int FIR_R = 8;                          // outputs per lane
-constexpr int FIR_TILE = FIR_THREADS * FIR_R;     // outputs per workgroup
-constexpr int FIR_TMAX = 257;
-
+// (FIR_THREADS lanes of FIR_R outputs each = FIR_TILE outputs per workgroup, at most FIR_TMAX taps: rx_dispatch.h)
 __host__ __device__ __forceinline__ int fir_pad(int s) { return s + (s >> 3); }
 
 // MS (dvbs2hip_set_streams, S > 1 streams per call): workgroup (b, s) is workgroup b of a one-stream call on stream s alone -- n_total samples at x + s n_total, its own
@@ -109,27 +104,23 @@ __global__ void fir_hist_streams_kernel(const float2 *x, const float2 *hist_in, 
 
 // S >= 1 streams of n_per samples each (dvbs2hip_set_streams), stream s at x + 2 s n_per, the memories of T - 1 samples side by side in hist_in / hist_out.  S == 1 is the
 // one-stream kernels on a one-dimensional grid, S > 1 their stream instantiations with one grid row per stream.
-// afrag != nullptr: the matrix-core form (k_fir_mfma.hip) when it applies (fir_mfma_usable), chosen once for the call;
-// dvbs2hip_set_filter_kernel(h, DVBS2HIP_FIR_VALU) (afrag == nullptr here) or DVBS2HIP_FIR=valu keep the vector kernel
+// ch: what fir_choose (rx_dispatch.h) chose for the call -- the matrix-core form (k_fir_mfma.hip; afrag its band fragments) or the vector kernel
 hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps_rev, const uint16_t *afrag,
-                      int T, long long n_per, int S, hipStream_t s)
+                      int T, long long n_per, int S, const FirChoice &ch, hipStream_t s)
 {
-    if (T < 1 || T > FIR_TMAX || S < 1 || S > 65535 || n_per < 1) return hipErrorInvalidValue;
+    if (ch.error) return hipErrorInvalidValue;
+    if (ch.family == FIR_MFMA) return fir_mfma_launch(x, y, hist_in, hist_out, afrag, T, n_per, ch, s);
     const int H = T - 1;
-    static const bool force_valu = [] { const char *e = getenv("DVBS2HIP_FIR"); return e && e[0] == 'v'; }();
-    if (afrag && !force_valu && fir_mfma_usable(x, y, T, n_per, S))
-        return fir_mfma_launch(x, y, hist_in, hist_out, afrag, T, n_per, S, s);
     const size_t lds = sizeof(float2) * (size_t)(fir_pad(FIR_TILE + H) + 1);
-    const unsigned grid = (unsigned)((n_per + FIR_TILE - 1) / FIR_TILE);
     const float2 *x2 = reinterpret_cast<const float2 *>(x);
     float2 *y2 = reinterpret_cast<float2 *>(y);
     const float2 *h2 = reinterpret_cast<const float2 *>(hist_in);
-    const auto fir = T == 81 ? (S > 1 ? fir_ccr_kernel<81, true> : fir_ccr_kernel<81>) : (S > 1 ? fir_ccr_kernel<0, true> : fir_ccr_kernel<0>);
-    hipLaunchKernelGGL(fir, dim3(grid, S), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
+    const auto fir = ch.taps == 81 ? (ch.streams ? fir_ccr_kernel<81, true> : fir_ccr_kernel<81>) : (ch.streams ? fir_ccr_kernel<0, true> : fir_ccr_kernel<0>);
+    hipLaunchKernelGGL(fir, dim3(ch.grid_x, ch.grid_y), dim3(FIR_THREADS), lds, s, x2, y2, h2, taps_rev, T, n_per);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (H > 0)
-        hipLaunchKernelGGL(S > 1 ? fir_hist_streams_kernel : fir_hist_kernel, dim3((H + 63) / 64, S), dim3(64), 0, s, x2, h2, reinterpret_cast<float2 *>(hist_out), H, n_per);
+        hipLaunchKernelGGL(ch.streams ? fir_hist_streams_kernel : fir_hist_kernel, dim3((H + 63) / 64, S), dim3(64), 0, s, x2, h2, reinterpret_cast<float2 *>(hist_out), H, n_per);
     return hipGetLastError();
 }
 
@@ -139,7 +130,6 @@ hipError_t fir_launch(const float *x, float *y, const float *hist_in, float *his
 // `osf` FIRs, branch f holds taps H[f], H[f+osf], ..; output sample i*osf + f = branch f at input i:
 //     y[i*osf + f] = sum_m H[f + m*osf] * x[i - m]
 // One lane per output sample, inputs staged in LDS; x[<0] = tail of the previous call.
-constexpr int UP_THREADS = 256;
 __global__ void __launch_bounds__(UP_THREADS)
 upfir_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const float2 *__restrict__ hist_in, const float *__restrict__ taps,
              int T, int osf, int Hin, long long n_in)
@@ -167,17 +157,16 @@ upfir_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const float2 
     y[i * osf + f] = acc;
 }
 
-// afrag2 != nullptr: the matrix-core form (k_fir_mfma.hip) when it applies (osf = 2, branches of at most 81 taps, aligned sockets)
+// ch: what upfir_choose chose -- the matrix-core form (afrag2 its two branches' fragments) or the vector kernel
 hipError_t upfir_launch(const float *x, float *y, const float *hist_in, float *hist_out, const float *taps, const uint16_t *afrag2, int T, int osf,
-                        long long n_in, hipStream_t s)
+                        long long n_in, const FirChoice &ch, hipStream_t s)
 {
-    if (T < 1 || T > FIR_TMAX || osf < 1 || osf > 16) return hipErrorInvalidValue;
-    if (afrag2 && upfir_mfma_usable(x, y, T, osf, n_in)) return upfir_mfma_launch(x, y, hist_in, hist_out, afrag2, T, n_in, s);
+    if (ch.error) return hipErrorInvalidValue;
+    if (ch.family == FIR_MFMA) return fir_mfma_launch(x, y, hist_in, hist_out, afrag2, (T - 1) / 2 + 1, n_in, ch, s);
     const int Hin = (T - 1) / osf;                 // input samples of memory
     const int per_blk = UP_THREADS / osf;
     const size_t lds = sizeof(float2) * (size_t)(per_blk + Hin) + sizeof(float) * (size_t)T;
-    const unsigned grid = (unsigned)((n_in + per_blk - 1) / per_blk);
-    hipLaunchKernelGGL(upfir_kernel, dim3(grid), dim3(UP_THREADS), lds, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
+    hipLaunchKernelGGL(upfir_kernel, dim3(ch.grid_x), dim3(UP_THREADS), lds, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
                        reinterpret_cast<const float2 *>(hist_in), taps, T, osf, Hin, n_in);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -29,13 +29,11 @@
 #include "dvbs2hip_internal.h"
 #include <vector>
 #include <cstring>
-#include <cstdlib>
 
 namespace dvbs2 {
 
 constexpr int FM_THREADS = 256;
-constexpr int FM_TILE = 2048;                     // outputs per workgroup = 8 MFMA tiles of 256
-constexpr int FM_H = 80;                          // history the Toeplitz band is laid out for (T = 81)
+// (FM_TILE outputs per workgroup = 8 MFMA tiles of 256, FM_H samples of history the Toeplitz band is laid out for: rx_dispatch.h)
 constexpr int FM_NS = FM_TILE + FM_H;             // staged samples per workgroup
 // No padding: the 16-lane groups of a ds_read_b128 ({0-3, 12-15, 20-27}, ... MI355X_MICROARCH.md, LDS) read the 16-B slots
 // 2 c + g + const of a plane, which are 16 different slots of the 256-B bank row for every group as the lanes stand
@@ -137,7 +135,7 @@ fir_mfma_kernel(const float2 *__restrict__ x, float2 *__restrict__ y, const floa
         fm_stage(lds, 2 * tid, s0.x, s0.y, s1.x, s1.y);
     }
     // the Toeplitz fragments of the three tap parts (host-made, 9 KB, L2-resident).  A polyphase branch of the shaping filter has at most
-    // 49 taps (upfir_mfma_usable), right-aligned in the 81-entry band: nothing of it falls into the first 32-wide K step, which NPH = 2
+    // 49 taps (upfir_choose, rx_dispatch.h), right-aligned in the 81-entry band: nothing of it falls into the first 32-wide K step, which NPH = 2
     // therefore leaves out -- a third of its products multiplied zeros, and the 24 registers of those fragments were what it spilled for
     constexpr int S0 = NPH == 2 ? 1 : 0, NS = 3 - S0;
     fm_bf16x8 A[NPH][3][NS];
@@ -244,27 +242,14 @@ std::vector<uint16_t> fir_mfma_afrag(const float *taps_rev, int T)
     return out;
 }
 
-// the kernel loads 16 bytes at a time: the sockets have to be so aligned, and with S > 1 streams every stream has to start on such a boundary (n_per even)
-bool fir_mfma_usable(const float *x, const float *y, int T, long long n_per, int S)
-{
-    return T >= 1 && T <= FM_H + 1 && n_per >= 2 && (S == 1 || n_per % 2 == 0) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-}
-
-// S streams of n_per samples (fir_launch); the tiles of a stream are dealt to its workgroups as in a one-stream call of n_per samples.  Also leaves the next call's filter
+// The matched filter (ch.up false: ch.grid_y streams of n samples, T taps; the tiles of a stream are dealt to its workgroups as in a one-stream call) or the shaping filter's
+// two branches (ch.up: T = the taps of a branch, n input samples), as fir_choose / upfir_choose (rx_dispatch.h) shaped the launch.  Also leaves the next call's filter
 // memory in hist_out (T - 1 samples per stream)
-hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n_per, int S, hipStream_t s)
+hipError_t fir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag, int T, long long n, const FirChoice &ch, hipStream_t s)
 {
-    const long long n_tiles = (n_per + FM_TILE - 1) / FM_TILE;
-    // Chunks of 4 tiles, handed to the CUs by the hardware dispatcher as workgroups retire: resident workgroups do not run at
-    // the same speed (the arbiter favours the older waves), and one persistent workgroup per slot with an equal share of the
-    // stream waited for the slowest -- same-box sweep at 68 M samples: 1024 workgroups (33 tiles each) 0.222 ms, 8192 (5 tiles)
-    // 0.207 ms, 16384 0.211 ms.  Short streams still get one workgroup per tile.  DVBS2HIP_FIR_WGS caps the grid (per stream) instead.
-    static const int max_wg = [] { const char *e = getenv("DVBS2HIP_FIR_WGS"); return e ? atoi(e) : 0; }();
-    const int tiles_per_wg = max_wg > 0 ? (int)((n_tiles + max_wg - 1) / max_wg) : (n_tiles >= 4096 ? 4 : (int)((n_tiles + 1023) / 1024));
-    const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
-    hipLaunchKernelGGL(S > 1 ? fir_mfma_kernel<1 + FM_STREAMS> : fir_mfma_kernel<1>, dim3(grid, S), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x),
-                       reinterpret_cast<float2 *>(y), reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T,
-                       n_per, tiles_per_wg);
+    const auto k = ch.up ? fir_mfma_kernel<2> : ch.streams ? fir_mfma_kernel<1 + FM_STREAMS> : fir_mfma_kernel<1>;
+    hipLaunchKernelGGL(k, dim3(ch.grid_x, ch.grid_y), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
+                       reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag), T, n, ch.tiles_per_wg);
     return hipGetLastError();
 }
 
@@ -283,24 +268,6 @@ std::vector<uint16_t> upfir_mfma_afrag(const float *taps, int T)
         out.insert(out.end(), a.begin(), a.end());
     }
     return out;
-}
-
-bool upfir_mfma_usable(const float *x, const float *y, int T, int osf, long long n_in)
-{
-    // a branch of at most 49 taps: the kernel skips the band's first K step
-    return osf == 2 && T >= 1 && (T - 1) / 2 + 1 <= FM_H + 1 - 32 && n_in >= 2 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-}
-
-// hist = the last (T - 1) / 2 input samples
-hipError_t upfir_mfma_launch(const float *x, float *y, const float *hist_in, float *hist_out, const uint16_t *afrag2, int T, long long n_in, hipStream_t s)
-{
-    const long long n_tiles = (n_in + FM_TILE - 1) / FM_TILE;
-    const int tiles_per_wg = n_tiles >= 4096 ? 4 : (int)((n_tiles + 1023) / 1024);       // as fir_mfma_launch
-    const unsigned grid = (unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg);
-    hipLaunchKernelGGL(fir_mfma_kernel<2>, dim3(grid), dim3(FM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<float2 *>(y),
-                       reinterpret_cast<const float2 *>(hist_in), reinterpret_cast<float2 *>(hist_out), reinterpret_cast<const uint4 *>(afrag2),
-                       (T - 1) / 2 + 1, n_in, tiles_per_wg);
-    return hipGetLastError();
 }
 
 }  // namespace dvbs2

@@ -21,8 +21,7 @@
 
 namespace dvbs2 {
 
-constexpr int FRONT_THREADS = 256;
-// (the PL frame's layout, pl_index and pl_derotate: rx_device.h)
+// (FRONT_THREADS, FRONT_WIDE and front_syms_per_trip: rx_dispatch.h; the PL frame's layout, pl_index and pl_derotate: rx_device.h)
 
 // position of interleaved LLR i = k*bps + b in the natural (code) order
 __device__ __forceinline__ int deitl_index(int k, int b, int bps, int cols, int order, int n_rows)
@@ -56,10 +55,6 @@ __device__ __forceinline__ int deitl_index(int k, int b, int bps, int cols, int 
 // (demap_symbols); the exponent's reference is k |y|^2, no running maximum; LLRs leave through a buffer descriptor.  A_s, B_s stay in SGPR pairs: replicated in vector
 // registers as well, 16APSK-S ran 0.102 against 0.091 ms and 32APSK-S 0.133 against 0.119 (163 VGPRs: three waves per SIMD).
 constexpr float FRONT_LOG2E = 1.44269504088896341f, FRONT_LN2 = 0.693147180559945309f;
-// Symbols a lane of front_kernel demaps per trip of its loop (= per read of the constellation table); front_dispatch cuts a frame into slices of whole trips with the same
-// number.  Two per lane for the APSK constellations: 16APSK-N 0.396 against 0.402 ms, 32APSK-S 0.179 against 0.129 (registers).
-__host__ __device__ __forceinline__ constexpr int front_syms_per_trip(int bps) { return bps <= 3 ? 4 : 1; }
-
 // per-frame table of the constellation, thread s < 2^bps:  tab[s] = c log2(e) (2 re, 2 im, -|s|^2, 0)
 __device__ __forceinline__ float4 demap_table_entry(const float *cstl, int s, float inv2s2)
 {
@@ -330,7 +325,6 @@ front_kernel(const FrontKParams p)
 // SPT symbols per lane, so the PL frame crosses the fabric once (the moments of a6 need the whole frame before the
 // first LLR of a3 can be formed; the two-sweep kernel above re-reads it from L2 / Infinity Cache), the loads of a lane
 // are all in flight together, and QPSK LLR pairs leave as one 8-byte store per lane.
-constexpr int FRONT_WIDE = 1024;
 typedef float front_f2 __attribute__((ext_vector_type(2)));      // a type the non-temporal builtins accept
 template <int BPS, int SPT, bool SEP, int WIDE = FRONT_WIDE>      // SEP: separable 2-bit constellation, linear LLRs (no general demapper compiled in); WIDE lanes per frame
 __global__ void __launch_bounds__(WIDE, 4)      // four waves per SIMD: one 1024-lane or two 512-lane workgroups per CU, 128 registers
@@ -487,62 +481,38 @@ front_reg2_kernel(const FrontKParams p)
     }
 }
 
-static bool front_reg_try(const FrontKParams &p, hipStream_t s)
-{
-    if (getenv("DVBS2HIP_FRONT_TWO_SWEEP")) return false;
-    dim3 g(p.n_frames), b(FRONT_WIDE);
-    const bool small = p.n_sym <= 8 * FRONT_WIDE, mid = p.n_sym <= 22 * FRONT_WIDE, big = p.n_sym <= 32 * FRONT_WIDE;
-    const bool pair_ok = p.bps == 2 && p.sep && p.itl_cols <= 1 && p.n_sym % 2 == 0 && p.pl_frame % 2 == 0 && !getenv("DVBS2HIP_FRONT_SINGLE") &&
-                         ((reinterpret_cast<uintptr_t>(p.src ? nullptr : p.in) | reinterpret_cast<uintptr_t>(p.llr)) & 15) == 0;      // (a located frame starts on 8 bytes: the pair kernel reads it through a buffer descriptor, which takes any dword address)
-    if (pair_ok && small) hipLaunchKernelGGL((front_reg2_kernel<4>), g, b, 0, s, p);
-    else if (pair_ok && big) hipLaunchKernelGGL((front_reg2_kernel<16>), g, b, 0, s, p);
-    // one symbol per lane and access: short frames (8 symbols per lane) and the 8PSK normal frame (21600 symbols: 22 per lane = 44 registers
-    // of frame, which leaves the demapper its own; round 2's 32-per-lane 8PSK form spilled frame symbols and is gone).  A separable QPSK normal frame that
-    // cannot take the pair kernel (unaligned sockets) still runs the 32-per-lane QPSK form below (no spills since the estimator's finish lost its powf / log10f);
-    // a non-separable mapping goes to the two-sweep kernel
-    else if (p.bps == 2 && p.sep && small) hipLaunchKernelGGL((front_reg_kernel<2, 8, true>), g, b, 0, s, p);
-    else if (p.bps == 2 && p.sep && big) hipLaunchKernelGGL((front_reg_kernel<2, 32, true>), g, b, 0, s, p);
-    else if (p.bps == 2 && small) hipLaunchKernelGGL((front_reg_kernel<2, 8, false>), g, b, 0, s, p);
-    else if (p.bps == 3 && small) hipLaunchKernelGGL((front_reg_kernel<3, 8, false>), g, b, 0, s, p);
-    else if (p.bps == 3 && mid) hipLaunchKernelGGL((front_reg_kernel<3, 22, false>), g, b, 0, s, p);
-    // (round 4: the APSK frames in registers as well -- front_reg_kernel<4, 4>, <4, 16>, <5, 4> -- measured 0.398 against 0.398 ms (16APSK-N), 0.098 against 0.093 (16APSK-S),
-    // 0.136 against 0.121 (32APSK-S): with sigma given they read the frame once either way, and the two-sweep kernel overlaps eight workgroups per CU)
-    else return false;
-    return true;
-}
-
+// launches what front_choose (rx_dispatch.h) chose for the call
 template <bool FROM_PL, bool DEITL>
-static hipError_t front_dispatch(const FrontKParams &p_in, hipStream_t s)
+static void front_two_sweep(int bps, dim3 g, dim3 b, hipStream_t s, const FrontKParams &p)
 {
-    FrontKParams p = p_in;
-    p.slice_chunk = 0;
-    dim3 g(p.n_frames), b(FRONT_THREADS);
-    if (p.n_frames < 512) {      // fewer workgroups than the chip holds: several per frame
-        const int trip = front_syms_per_trip(p.bps) * FRONT_THREADS;      // symbols a workgroup takes per trip of its loop
-        int slices = (p.n_sym + trip - 1) / trip;
-        const int cap = 1024 / p.n_frames;
-        if (slices > cap) slices = cap;
-        if (slices > 1) { p.slice_chunk = ((p.n_sym + slices - 1) / slices + trip - 1) / trip * trip; g.y = (unsigned)((p.n_sym + p.slice_chunk - 1) / p.slice_chunk); }
-    }
-    switch (p.bps) {
+    switch (bps) {
         case 1: hipLaunchKernelGGL((front_kernel<1, FROM_PL, DEITL>), g, b, 0, s, p); break;
         case 2: hipLaunchKernelGGL((front_kernel<2, FROM_PL, DEITL>), g, b, 0, s, p); break;
         case 3: hipLaunchKernelGGL((front_kernel<3, FROM_PL, DEITL>), g, b, 0, s, p); break;
         case 4: hipLaunchKernelGGL((front_kernel<4, FROM_PL, DEITL>), g, b, 0, s, p); break;
-        case 5: hipLaunchKernelGGL((front_kernel<5, FROM_PL, DEITL>), g, b, 0, s, p); break;
-        default: return hipErrorInvalidValue;
+        default: hipLaunchKernelGGL((front_kernel<5, FROM_PL, DEITL>), g, b, 0, s, p); break;
     }
-    return hipGetLastError();
 }
 
-hipError_t front_rx_launch(FrontKParams p, hipStream_t s)
+hipError_t front_launch(FrontKParams p, const FrontChoice &ch, hipStream_t s)
 {
-    if (front_reg_try(p, s)) return hipGetLastError();
-    return front_dispatch<true, true>(p, s);
-}
-hipError_t demod_launch(FrontKParams p, bool deinterleave, hipStream_t s)
-{
-    return deinterleave ? front_dispatch<false, true>(p, s) : front_dispatch<false, false>(p, s);
+    if (ch.error) return hipErrorInvalidValue;
+    p.slice_chunk = ch.slice_chunk;
+    const dim3 g(p.n_frames, ch.grid_y), b(ch.block);
+    const int *t = ch.targ;
+    if (ch.form == FRONT_REG2) {
+        if (t[0] == 4) hipLaunchKernelGGL((front_reg2_kernel<4>), g, b, 0, s, p);
+        else hipLaunchKernelGGL((front_reg2_kernel<16>), g, b, 0, s, p);
+    } else if (ch.form == FRONT_REG) {
+        if (t[0] == 2 && t[2]) { if (t[1] == 8) hipLaunchKernelGGL((front_reg_kernel<2, 8, true>), g, b, 0, s, p); else hipLaunchKernelGGL((front_reg_kernel<2, 32, true>), g, b, 0, s, p); }
+        else if (t[0] == 2) hipLaunchKernelGGL((front_reg_kernel<2, 8, false>), g, b, 0, s, p);
+        else if (t[1] == 8) hipLaunchKernelGGL((front_reg_kernel<3, 8, false>), g, b, 0, s, p);
+        else hipLaunchKernelGGL((front_reg_kernel<3, 22, false>), g, b, 0, s, p);
+    }
+    else if (t[1]) front_two_sweep<true, true>(t[0], g, b, s, p);
+    else if (t[2]) front_two_sweep<false, true>(t[0], g, b, s, p);
+    else front_two_sweep<false, false>(t[0], g, b, s, p);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- a4 stand-alone

@@ -21,9 +21,7 @@ constexpr float K_CONJ_SOF[25] = {1, -1, -1, 1, -1, 1, 1, -1, 1, 1, -1, -1, 1, -
 constexpr float K_CONJ_PLSC[64] = {1, 0, 1, 0, -1, 0, -1, 0, 1, 0, -1, 0, 1, 0, -1, 0, 1, 0, -1, 0, -1, 0, 1, 0, -1, 0, -1, 0, 1, 0, 1, 0,
                                    1, 0, 1, 0, -1, 0, -1, 0, -1, 0, -1, 0, -1, 0, 1, 0, 1, 0, -1, 0, 1, 0, 1, 0, 1, 0, -1, 0, -1, 0, 1, 0};
 
-constexpr int SY_THREADS = 256;
-constexpr int SY_R = 4;                       // outputs per lane
-constexpr int SY_T = SY_THREADS * SY_R;       // outputs per workgroup
+// (SY_THREADS lanes of SY_R outputs each = SY_T outputs per workgroup: rx_dispatch.h)
 constexpr int SY_H = 64;                      // samples of x a block needs before its first output (63 of d, one more of x)
 __device__ __forceinline__ int sy_pad(int i) { return i + (i >> 2); }     // one element of padding per 4: the lanes' stride-4 reads hit 32 different banks
 
@@ -243,7 +241,6 @@ __device__ __forceinline__ void sy_wave_umax4(uint32_t &a, uint32_t &b, uint32_t
 // Every workgroup leaves its key of every frame in keys[frame][workgroup] (plain stores: agent-scope atomics on one word per frame from 521
 // workgroups were what this kernel waited for); sync_finalize_kernel takes their maximum.  A frame without a value above 0 gets key 0.
 constexpr int SYM_UF = 24;
-constexpr int SYNC_UF96_MAX_WG = 256;      // calls with at most this many workgroups (one per CU) take the thirteen-wave form below, longer frames the four-wave form of round 3
 __device__ __forceinline__ void sy_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __global__ void __launch_bounds__(256)
@@ -700,7 +697,6 @@ __device__ __forceinline__ const float *vd_source_fast(const VdU &u, const float
     return vd_source<MS>(X, yprev0, buff0, st0, Dtab, f, j, n, nbuff2);
 }
 
-constexpr int VD_SPL = 2;        // PAIRS of complex samples per lane, their loads in flight together
 typedef float vd_f4 __attribute__((ext_vector_type(4), aligned(4)));     // a pair of complex samples wherever it lies (the delays are even numbers of floats only)
 // blockIdx.y < F: output frame blockIdx.y; blockIdx.y == F: the delay line and {head2, first_time} after the last frame.
 // A lane resolves two neighbouring complex samples; almost always they are neighbours at the source too (in lock a whole output frame is ONE
@@ -957,24 +953,15 @@ __global__ void sff_rotate2_kernel(const vd_f4n *__restrict__ x, vd_f4n *__restr
     const float2 a = sff_rotate<MODE>(make_float2(v.x, v.y), e, k), b = sff_rotate<MODE>(make_float2(v.z, v.w), e, k + 1);
     __builtin_nontemporal_store(vd_f4n{a.x, a.y, b.x, b.y}, y + g);
 }
-template <int MODE>
-static void sff_rotate_launch(const float *X, float *Y, const float2 *fr, int n, long long tot, hipStream_t s)
+template <int MODE>      // pair: rotate_choose (rx_dispatch.h)
+static void sff_rotate_launch(const float *X, float *Y, const float2 *fr, int n, long long tot, bool pair, hipStream_t s)
 {
-    if (n % 2 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0)
+    if (pair)
         hipLaunchKernelGGL(sff_rotate2_kernel<MODE>, dim3((unsigned)((tot / 2 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const vd_f4n *>(X),
                            reinterpret_cast<vd_f4n *>(Y), fr, n, tot / 2);
     else
         hipLaunchKernelGGL(sff_rotate_kernel<MODE>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float2 *>(X),
                            reinterpret_cast<float2 *>(Y), fr, n, tot);
-}
-
-static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s);
-// the waiting workgroups' limit in ticks of s_memrealtime (100 MHz): one second; DVBS2HIP_LR_TIMEOUT_US overrides it (tests: 0 makes every waiting workgroup give up at
-// its first unsuccessful poll, which exercises the error word and the recovery)
-static unsigned long long sff_lr_timeout_ticks()
-{
-    const char *ev = getenv("DVBS2HIP_LR_TIMEOUT_US");
-    return ev ? (unsigned long long)atoll(ev) * 100ull : 100000000ull;
 }
 
 // ---- L&R, recurrence and rotation in ONE launch.  The recurrence over the frames of a call is serial (4096 frames: 50 us in its own kernel, during which the
@@ -988,7 +975,7 @@ static unsigned long long sff_lr_timeout_ticks()
 // to run the rotation again (sff_lr_recover).  The recurrence itself on two lanes (lane 0 the real, lane 1
 // the imaginary part: two dependent instructions per frame instead of six), its (1 - alpha) t products formed by all lanes before; the values and their order are
 // those of sff_lr_iir_kernel (alpha r + (1 - alpha) t, two roundings).
-constexpr int SFF_RU = 4, SFF_RCH = 256 * SFF_RU;        // 16-byte pairs per lane / per workgroup
+// (SFF_RU 16-byte pairs per lane, SFF_RCH per workgroup: rx_dispatch.h)
 constexpr unsigned long long SFF_NOT_YET = ~0ull;        // (an estimate that is not a number is stored as the canonical NaN: never this pattern)
 template <bool FULL>
 __device__ __forceinline__ void sff_lr_chain1(float *pl, float &r, float alpha, int cnt)
@@ -1100,93 +1087,67 @@ sff_lr_fused_kernel(const vd_f4n *__restrict__ x, vd_f4n *__restrict__ y, const 
 }
 
 // after a launch whose error word was set: every estimate is in `tmp` (workgroup 0 has ended), only rotated samples are missing -- rotate the whole call again
-hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, hipStream_t s)
+hipError_t sff_lr_recover(const float *X, float *Y, float *tmp, int n, int F, bool pair, hipStream_t s)
 {
     float2 *fr = reinterpret_cast<float2 *>(tmp) + F;
-    sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, s);
+    sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, pair, s);
     return hipGetLastError();
 }
 
-// S == 1: the one launch above with its error word, or the three kernels (DVBS2HIP_LR=unfused, an odd frame length, unaligned sockets).  S > 1 streams per call
-// (dvbs2hip_set_streams): always the three kernels (the one-launch form's waiting workgroups rely on workgroup 0 being placed first: one assumption per launch, not
-// multiplied by the streams), err_dev is not used
-hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, hipStream_t s)
-{
-    const char *ev = getenv("DVBS2HIP_LR");                    // read at every call
-    const bool unfused = ev && !strcmp(ev, "unfused");
-    if (S == 1 && !unfused && n % 2 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
-        float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
-        const int cpf = (n / 2 + SFF_RCH - 1) / SFF_RCH;
-        hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, fr, n);
-        hipLaunchKernelGGL(sff_lr_fused_kernel, dim3(1 + (unsigned)F * cpf), dim3(256), 0, s, reinterpret_cast<const vd_f4n *>(X), reinterpret_cast<vd_f4n *>(Y), tR, R_l, fr, FRQ, PHS,
-                           F, alpha, n, cpf, err_dev, sff_lr_timeout_ticks());
-        return hipGetLastError();
-    }
-    return sff_lr_launch_unfused(X, Y, R_l, tmp, FRQ, PHS, n, F, S, alpha, s);
-}
-
-// the pilots per frame, the recurrence as one workgroup per stream, the rotation per frame
-static hipError_t sff_lr_launch_unfused(const float *X, float *Y, float *R_l, float *tmp, float *FRQ, float *PHS, int n, int F, int S, float alpha, hipStream_t s)
+// ch: lr_choose (rx_dispatch.h).  The one launch above with its error word, its waiting limit in ticks of s_memrealtime (100 MHz); or three kernels: the pilots per
+// frame, the recurrence as one workgroup per stream, the rotation per frame (err_dev is not used)
+hipError_t sff_lr_launch(const float *X, float *Y, float *R_l, float *tmp /* 4 F floats */, float *FRQ, float *PHS, int n, int F, int S, float alpha, uint32_t *err_dev, const LrChoice &ch,
+                         hipStream_t s)
 {
     float2 *tR = reinterpret_cast<float2 *>(tmp), *fr = tR + F;
+    if (ch.one_launch) {
+        hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, fr, n);
+        hipLaunchKernelGGL(sff_lr_fused_kernel, dim3(1 + (unsigned)F * ch.cpf), dim3(256), 0, s, reinterpret_cast<const vd_f4n *>(X), reinterpret_cast<vd_f4n *>(Y), tR, R_l, fr, FRQ, PHS,
+                           F, alpha, n, ch.cpf, err_dev, ch.timeout_us * 100ull);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(sff_lr_pilot_kernel, dim3(F), dim3(256), 0, s, X, tR, (float2 *)nullptr, n);
     hipLaunchKernelGGL(S > 1 ? sff_lr_iir_kernel<true> : sff_lr_iir_kernel<false>, dim3(S), dim3(128), 0, s, tR, R_l, fr, FRQ, PHS, F / S, alpha);
-    sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, s);
+    sff_rotate_launch<0>(X, Y, fr, n, (long long)n * F, ch.pair, s);
     return hipGetLastError();
 }
 
-hipError_t sff_fp_launch(const float *X, float *Y, float *tmp /* 2 F floats */, float *FRQ, float *PHS, int n, int F, hipStream_t s)
+hipError_t sff_fp_launch(const float *X, float *Y, float *tmp /* 2 F floats */, float *FRQ, float *PHS, int n, int F, bool pair, hipStream_t s)
 {
     float2 *fr = reinterpret_cast<float2 *>(tmp);
     hipLaunchKernelGGL(sff_fp_pilot_kernel, dim3(F), dim3(64), 0, s, X, fr, FRQ, PHS, n);
-    const long long tot = (long long)n * F;
-    sff_rotate_launch<1>(X, Y, fr, n, tot, s);
+    sff_rotate_launch<1>(X, Y, fr, n, (long long)n * F, pair, s);
     return hipGetLastError();
 }
 
 std::vector<uint16_t> sync_frag_default() { return sync_mfma_frag(K_CONJ_SOF, K_CONJ_PLSC); }
 
 // ---- S >= 1 streams per call (dvbs2hip_set_streams): stream s = frames [s Fs, (s + 1) Fs) of every socket, n_per = n Fs samples; all state is laid out stream after stream.
-// S == 1 launches the one-stream kernels, S > 1 their stream forms with the stream in the grid's last dimension
-hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
+// S == 1 launches the one-stream kernels, S > 1 their stream forms with the stream in the grid's last dimension.  ch: what sync_choose (rx_dispatch.h) chose for the call.
+// The correlators: on the matrix cores (k_sync_mfma.hip, which also leaves the next call's memory in xh_out) or the fp32 vector kernel
+hipError_t sync_corr_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, float *cor_sof, float *cor_plsc, long long n_per, int S, const SyncChoice &ch,
+                            hipStream_t s)
 {
-    // frag: the correlators on the matrix cores (k_sync_mfma.hip, which also leaves the next call's memory in xh_out); null = the fp32 vector kernel
-    if (sync_mfma_usable(x, frag, n_per, S)) return sync_corr_mfma_launch(x, xh_in, xh_out, frag, nullptr, nullptr, nullptr, cor_sof, cor_plsc, n_per, S, s);
-    hipLaunchKernelGGL(S > 1 ? sync_corr_kernel<true> : sync_corr_kernel<false>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s,
+    if (ch.corr == SYNC_CORR_MFMA) return sync_corr_mfma_launch(x, xh_in, xh_out, frag, nullptr, nullptr, nullptr, cor_sof, cor_plsc, n_per, S, ch.corr_grid, s);
+    hipLaunchKernelGGL(S > 1 ? sync_corr_kernel<true> : sync_corr_kernel<false>, dim3(ch.corr_grid, S), dim3(SY_THREADS), 0, s,
                        reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
     hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                        reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
     return hipGetLastError();
 }
 
-// segments of the call's frames side by side while they fit the chip (one workgroup per CU) and stay long enough to be worth a seam (>= 768 frames each)
-SyncSegPlan sync_segment_plan(int n, int F, int cap, bool have_scratch)
-{
-    const int nwg = (n + 63) / 64;
-    int nseg = cap <= 1 || !have_scratch ? 1 : std::min(std::min(std::min(cap, SYNC_MAX_SEG), SYNC_UF96_MAX_WG / nwg), F / 768);
-    int seg_F = F;
-    if (nseg > 1) { seg_F = ((F + nseg - 1) / nseg + 191) / 192 * 192; nseg = (F + seg_F - 1) / seg_F; }      // (a multiple of the chunk's 96 frames and of SYNC_SUB)
-    if (nseg <= 1) { nseg = 1; seg_F = F; }
-    return {nseg, seg_F};
-}
-
 // the average over frames with the arg max of every frame, then the per-frame sockets / delay-line table
-static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, hipStream_t s)
+static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, float alpha, int vec_width, const SyncTail &t, const SyncChoice &ch, hipStream_t s)
 {
-    const int end_vec = (n / vec_width) * vec_width, nwg = (n + 63) / 64;
-    if (S > 1) {      // the streams supply the parallelism: the plain walk, one wave per (stream, 64 positions)
+    const int end_vec = (n / vec_width) * vec_width, nwg = ch.nwg;
+    if (ch.argmax == SYNC_ARGMAX_STREAMS) {
         hipLaunchKernelGGL(sync_average_argmax_streams_kernel, dim3(nwg, S), dim3(64), 0, s, cv, (const float *)corr, t.keys, n, Fs, alpha, end_vec);
         hipLaunchKernelGGL(sync_finalize_kernel<true>, dim3(Fs, S), dim3(64), 0, s, t.keys, nwg, t.delay, t.metric, t.flag, t.trigger, t.Dtab, t.last_metric, n, 25, 64, Fs);
         return;
     }
     const int F = Fs;
-    // few positions (short frames): the thirteen-wave form, one workgroup per CU at most; long frames: round 3's four-wave form (the stage is bound by its 4 bytes per
-    // sample there: QPSK-N 1024 frames 42-45 us in the four-wave form, 65 us in this one)
-    static const bool four = getenv("DVBS2HIP_SYNC_ARGMAX4") != nullptr;      // development: round 3's kernel for every frame length
-    if (!four && nwg <= SYNC_UF96_MAX_WG) {
-        static const int cap = getenv("DVBS2HIP_SYNC_SEGMENTS") ? atoi(getenv("DVBS2HIP_SYNC_SEGMENTS")) : SYNC_MAX_SEG;      // (development: 1 = the single walk)
-        const SyncSegPlan sp = sync_segment_plan(n, F, cap, t.seg != nullptr);
-        const int nseg = sp.nseg, seg_F = sp.seg_F;
+    if (ch.argmax == SYNC_ARGMAX96) {
+        const int nseg = ch.seg.nseg, seg_F = ch.seg.seg_F;
         if (nseg > 1) hipLaunchKernelGGL(sync_seg_partial_kernel, dim3(nwg, (nseg - 1) * (seg_F / SYNC_SUB)), dim3(64), 0, s, (const float *)corr, t.seg, n, F, alpha, end_vec);
         hipLaunchKernelGGL(sync_metric_argmax_kernel<96>, dim3(nwg, nseg), dim3(64 * (SYM_NC + 12)), 0, s, cv, corr, t.keys, n, F, alpha, end_vec, (const float *)t.seg, seg_F);
     }
@@ -1196,29 +1157,29 @@ static void sync_average_argmax(float *cv, float *corr, int n, int Fs, int S, fl
 
 // the one-task form: correlators + instantaneous metric fused (nothing but m leaves the chip), then the average / arg max as above
 hipError_t sync_corr_metric_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *cv, float *corr,
-                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
+                                   const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, const SyncChoice &ch, hipStream_t s)
 {
     const long long n_per = (long long)n * Fs;
-    if (sync_mfma_usable(x, frag, n_per, S)) (void)sync_corr_mfma_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, nullptr, nullptr, n_per, S, s);
+    if (ch.corr == SYNC_CORR_MFMA) (void)sync_corr_mfma_launch(x, xh_in, xh_out, frag, sofh_in, sofh_out, corr, nullptr, nullptr, n_per, S, ch.corr_grid, s);
     else {
-        hipLaunchKernelGGL(S > 1 ? sync_corr_m_kernel<true> : sync_corr_m_kernel<false>, dim3((unsigned)((n_per + SY_T - 1) / SY_T), S), dim3(SY_THREADS), 0, s,
+        hipLaunchKernelGGL(S > 1 ? sync_corr_m_kernel<true> : sync_corr_m_kernel<false>, dim3(ch.corr_grid, S), dim3(SY_THREADS), 0, s,
                            reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr, n_per);
         hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                            reinterpret_cast<float2 *>(xh_out), SY_H, n_per);
     }
-    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, s);
+    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, ch, s);
     return hipGetLastError();
 }
 
 hipError_t sync_metric_launch(const float *cor_sof, const float *sofh_in, float *sofh_out, const float *cor_plsc, float *cv, float *corr,
-                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, hipStream_t s)
+                              const SyncTail &t, int n, int Fs, int S, float alpha, int vec_width, const SyncChoice &ch, hipStream_t s)
 {
     const long long n_per = (long long)n * Fs;
     hipLaunchKernelGGL(S > 1 ? sync_m_streams_kernel : sync_m_kernel, dim3((unsigned)((n_per + 255) / 256), S), dim3(256), 0, s, reinterpret_cast<const float2 *>(cor_sof),
                        reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<const float2 *>(cor_plsc), corr, n_per);
     hipLaunchKernelGGL(S > 1 ? sync_hist_streams_kernel : sync_hist_kernel, dim3(1, S), dim3(64), 0, s, reinterpret_cast<const float2 *>(cor_sof), reinterpret_cast<const float2 *>(sofh_in),
                        reinterpret_cast<float2 *>(sofh_out), 64, n_per);
-    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, s);
+    sync_average_argmax(cv, corr, n, Fs, S, alpha, vec_width, t, ch, s);
     return hipGetLastError();
 }
 
@@ -1247,20 +1208,13 @@ __global__ void sync_locate_kernel(const float *X, float *scratch, const int32_t
 }
 
 // all Fs frames of each of the call's S streams; Dtab (Fs S ints) comes from sync_finalize_kernel; Yprev_new = the last output frame for the next call.  list / src != null:
-// the located form (Y = scratch for the frames that are materialized), one stream only
+// the located form (Y = scratch for the frames that are materialized), one stream only.  The grid: sync_choose
 hipError_t sync_vdelay_launch(const float *X, const float *Yprev, float *Yprev_new, float *Y, const float *buff_old, float *buff_new, const int *st_old, int *st_new,
-                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, hipStream_t s, int32_t *list, const float **src)
+                              const int32_t *Dtab, int n, int nbuff2, int Fs, int S, const SyncChoice &ch, hipStream_t s, int32_t *list, const float **src)
 {
     if (list && S > 1) return hipErrorInvalidValue;
-    const int tot = ((nbuff2 > 2 * n ? nbuff2 : 2 * n) + 3) / 4;     // pairs of complex samples
-    const int gx = (tot + 256 * VD_SPL - 1) / (256 * VD_SPL);
-    int gy = Fs + 1;
-    if (list) {
-        hipLaunchKernelGGL(sync_locate_kernel, dim3(1), dim3(1024), 0, s, X, Y, Dtab, n, nbuff2, Fs, list, src);
-        // rows of the grid share the list's entries: in lock three of them have work (first frame, last frame, state row), while the synchronizer acquires all do
-        gy = Fs + 1 < 64 ? Fs + 1 : 64;
-    }
-    hipLaunchKernelGGL(S > 1 ? sync_vdelay_batch_kernel<true> : sync_vdelay_batch_kernel<false>, dim3(gx, gy, S), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new,
+    if (list) hipLaunchKernelGGL(sync_locate_kernel, dim3(1), dim3(1024), 0, s, X, Y, Dtab, n, nbuff2, Fs, list, src);
+    hipLaunchKernelGGL(S > 1 ? sync_vdelay_batch_kernel<true> : sync_vdelay_batch_kernel<false>, dim3(ch.vd_gx, ch.vd_gy, S), dim3(256), 0, s, X, Yprev, Yprev_new, Y, buff_old, buff_new,
                        st_old, st_new, Dtab, n, nbuff2, Fs, (const int32_t *)list);
     return hipGetLastError();
 }

@@ -25,8 +25,7 @@
 
 namespace dvbs2 {
 
-constexpr int SM_THREADS = 256;
-constexpr int SM_TILE = 2048;                      // outputs per workgroup = 8 MFMA tiles of 256
+// (SM_THREADS lanes, SM_TILE outputs per workgroup = 8 MFMA tiles of 256: rx_dispatch.h)
 constexpr int SM_HALO = 144;                       // 80 (band layout of fir_mfma_afrag) + 64 (SOF_PLSC_delay)
 constexpr int SM_NS = SM_TILE + SM_HALO;           // staged differential samples; plane index j <-> d[blk0 - 144 + j]
 constexpr int SM_PLANE = SM_NS;
@@ -225,16 +224,13 @@ std::vector<uint16_t> sync_mfma_frag(const float *sof25, const float *plsc64)
     return out;
 }
 
-// the kernel loads 16 bytes at a time: the socket has to be so aligned, and with S > 1 streams every stream has to start on such a boundary (n_per even)
-bool sync_mfma_usable(const float *x, const void *frag, long long n_per, int S) { return frag && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (S == 1 || n_per % 2 == 0); }
-
 // S streams of n_per samples.  corr != null is the one-task form (the instantaneous metric only; sofh_in / sofh_out its memories, cor_sof / cor_plsc null), else both
-// correlations go to their sockets (sofh_in / sofh_out null)
+// correlations go to their sockets (sofh_in / sofh_out null).  grid: workgroups per stream (sync_choose, rx_dispatch.h, which also holds what the kernel asks of the socket)
 hipError_t sync_corr_mfma_launch(const float *x, const float *xh_in, float *xh_out, const uint16_t *frag, const float *sofh_in, float *sofh_out, float *corr,
-                                 float *cor_sof, float *cor_plsc, long long n_per, int S, hipStream_t s)
+                                 float *cor_sof, float *cor_plsc, long long n_per, int S, unsigned grid, hipStream_t s)
 {
     const auto k = corr ? (S > 1 ? sync_corr_mfma_streams_kernel<true> : sync_corr_mfma_kernel<true>) : (S > 1 ? sync_corr_mfma_streams_kernel<false> : sync_corr_mfma_kernel<false>);
-    hipLaunchKernelGGL(k, dim3((unsigned)((n_per + SM_TILE - 1) / SM_TILE), S), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
+    hipLaunchKernelGGL(k, dim3(grid, S), dim3(SM_THREADS), 0, s, reinterpret_cast<const float2 *>(x), reinterpret_cast<const float2 *>(xh_in),
                        reinterpret_cast<float2 *>(xh_out), reinterpret_cast<const uint4 *>(frag), reinterpret_cast<const float2 *>(sofh_in), reinterpret_cast<float2 *>(sofh_out), corr,
                        reinterpret_cast<float2 *>(cor_sof), reinterpret_cast<float2 *>(cor_plsc), n_per);
     return hipGetLastError();

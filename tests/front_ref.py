@@ -1,4 +1,4 @@
-"""float64 twin of the receive chain's fused front end (k_front.hip: front_rx_launch = PL descrambling, header / pilot removal, the M2M4 noise
+"""float64 twin of the receive chain's fused front end (k_front.hip: front_launch = PL descrambling, header / pilot removal, the M2M4 noise
 estimate, the soft demapper and the de-interleaver in one launch), the bars its outputs are held to, and an fp32 model of the demapper's
 arithmetic.  tests/test_front_ref.py (CPU) and tests/test_front_fp64_gpu.py (the kernels, through dvbs2hip_rx_front*) share all of it.
 

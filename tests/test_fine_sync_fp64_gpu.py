@@ -53,11 +53,26 @@ def _hold(tag, mc, rows):
     assert not bad, (tag, mc, bad)
 
 
-def _lr_form(monkeypatch, form):
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    from test_plan_digest import build_probe
+    exe = str(tmp_path_factory.mktemp("fine_fp64") / "plan_probe")
+    build_probe(exe)
+    return exe
+
+
+def _lr_form(monkeypatch, form, probe=None, n=0):
+    """sets the knob of the asked form; with the probe, -> the kernel lr_choose (dvbs2_amd/csrc/rx_dispatch.h) names for a one-stream call on aligned sockets under
+    it, which has to be the one launch / the pair rotation of the three"""
     if form == "unfused":
         monkeypatch.setenv("DVBS2HIP_LR", "unfused")
     else:
         monkeypatch.delenv("DVBS2HIP_LR", raising=False)
+    if probe:
+        from test_rx_dispatch import lr_form
+        name = lr_form(probe, 1, n)
+        assert name == ("sff_lr_fused_kernel" if form == "fused" else "sff_rotate2_kernel<0>"), (form, name)
+        return name
 
 
 @pytest.mark.parametrize("modcod", R.modcods())
@@ -76,7 +91,7 @@ def test_freq_phase_host_form_against_float64(O, Rx, Yd, modcod):
 
 
 @pytest.mark.parametrize("modcod", R.modcods())
-def test_lr_both_forms_against_float64(O, Rx, Yd, monkeypatch, modcod):
+def test_lr_both_forms_against_float64(O, Rx, Yd, monkeypatch, probe, modcod):
     """alpha 0: every frame's estimate is its own -- estimates against lr_estimates64, rotation against rotate64.  alpha 0.7 over the six
     frames, the six again, the six reversed: the recurrence against the float64 recurrence (which carries its own R), held to 4 x the error
     of the oracle object on the same sequence.  sff_lr_fused_kernel (default) and the three-kernel path give the same bits throughout."""
@@ -91,7 +106,7 @@ def test_lr_both_forms_against_float64(O, Rx, Yd, monkeypatch, modcod):
     print("fine_fp64 bars: E_orc %.3e, FRQ alpha 0 %.3e, FRQ alpha 0.7 %.3e" % (refs["E"], refs["frq_bar"], seq_bar))
     out = {}
     for form in ("fused", "unfused"):
-        _lr_form(monkeypatch, form)
+        print("fine_fp64 L&R %s: %s" % (form, _lr_form(monkeypatch, form, probe, n)))
         rx = Rx(modcod, max_frames=F)
         rx.sync_lr_set_alpha(0.0)
         FRQ, PHS, Y = rx.sync_lr_synchronize(X)

@@ -198,9 +198,15 @@ def test_shaping_filter_against_float64(O, Rx, kernel, case):
     _float64_bars(kernel, "shape_filter " + case, *[np.concatenate(o) for o in out], T)
 
 
-def test_long_stream_four_tiles_per_workgroup_against_float64(O, Rx):
+def test_long_stream_four_tiles_per_workgroup_against_float64(O, Rx, tmp_path):
     """3073 tiles in one call: the matrix-core kernel's workgroups take four tiles each (three carries of the overlap inside LDS), the last one
-    a single ragged tile"""
+    a single ragged tile -- as `plan_probe fir` (fir_choose, dvbs2_amd/csrc/rx_dispatch.h) says of this call"""
+    from test_plan_digest import build_probe
+    from test_rx_dispatch import ask
+    build_probe(str(tmp_path / "plan_probe"))
+    line = ask(str(tmp_path / "plan_probe"), "fir", [(81, R.LONG_N, 1, 16, 16, 1)], inherit=True)[0]
+    print("fir_fp64 long stream: " + line)
+    assert line == "fir_mfma_kernel<1> | grid %d x 1 tiles_per_wg 4" % -(-(-(-R.LONG_N // 2048)) // 4) and -(-R.LONG_N // 2048) % 4 == 1
     taps = R.srrc(81)
     x = np.random.default_rng(44).standard_normal(2 * R.LONG_N).astype(np.float32)
     rx = _rx(Rx, taps, "mfma")

@@ -209,3 +209,29 @@ def test_filter1_filter2_split_matches_the_reference_tasks(O, Rx, P, kernel):
     with pytest.raises(Exception):
         rx.filter1(np.zeros(2 * 100, np.float32), 1)          # half a frame shorter than the filter's memory
     rx.close(); ref.close()
+
+
+def test_a_knob_flipped_mid_process_takes_effect(Rx, P, monkeypatch):
+    """DVBS2HIP_FIR is read at each call (fir_choose, dvbs2_amd/csrc/rx_dispatch.h), not once per process: one handle, one frame of 1024 samples through the 81-tap
+    filter from the reset state with the knob unset, set to valu, unset again.  The first and third outputs are the matrix-core kernel's, equal bit for bit; the second
+    is bit for bit what set_filter_kernel(FIR_VALU) gives, and differs from them (another order of the same sum)."""
+    from dvbs2_amd import lib_binding as B
+    taps = P.rrc_taps(0.2, 2, 20)
+    assert taps.size == 81
+    x = np.random.default_rng(11).standard_normal(2 * 1024).astype(np.float32)
+    monkeypatch.delenv("DVBS2HIP_FIR", raising=False)
+    rx = Rx("32APSK-S_3/4", max_frames=1)
+    out = []
+    for knob in (None, "valu", None):
+        if knob:
+            monkeypatch.setenv("DVBS2HIP_FIR", knob)
+        else:
+            monkeypatch.delenv("DVBS2HIP_FIR", raising=False)
+        rx.filter_reset()
+        out.append(rx.filter(x, 1).view(np.uint32))
+    rx.set_filter_kernel(B.FIR_VALU)
+    rx.filter_reset()
+    valu = rx.filter(x, 1).view(np.uint32)
+    rx.close()
+    assert np.array_equal(out[0], out[2])
+    assert np.array_equal(out[1], valu) and not np.array_equal(out[1], out[0])

@@ -1,7 +1,8 @@
-"""The fused front end (k_front.hip: front_rx_launch, entered by every rx_bb* call) against its float64 twin, through the tap dvbs2hip_rx_front*.
+"""The fused front end (k_front.hip: front_launch, entered by every rx_bb* call) against its float64 twin, through the tap dvbs2hip_rx_front*.
 
-Every kernel form is reached by its condition and named in the case's docstring; which form a call takes is decided on the host by front_reg_try /
-front_dispatch from the MODCOD, the frame count, two environment variables and the alignment of the PL and LLR sockets.  The bars are those of
+Every kernel form is reached by its condition and named in the case's docstring; which form a call takes is decided on the host by front_choose
+(dvbs2_amd/csrc/rx_dispatch.h) from the MODCOD, the frame count, two environment variables and the alignment of the PL and LLR sockets.  Each case asks
+`plan_probe front` with its own facts and this process's knobs, requires the documented form and prints that name.  The bars are those of
 tests/front_ref.py::judge, against the twin evaluated at the sigma the device itself reports in EST[:, 0], so the LLRs' scale and the estimate are
 judged apart: no NaN of the sockets' fill left, EST = (sigma_in, 0, 0) bit for bit where sigma is given, |L - L64| <= 1e-4 max(1, |L64|) for every
 LLR, the frame's rms normalized error within TIGHT_MARGIN of the oracle demapper's own on the same frame and sigma, and with the estimator sigma
@@ -21,6 +22,22 @@ GUARD = 64                       # floats of NaN in front of and behind each out
 def Rx():
     from dvbs2_amd.receiver import Dvbs2Hip
     return Dvbs2Hip
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    from test_plan_digest import build_probe
+    exe = str(tmp_path_factory.mktemp("front_fp64") / "plan_probe")
+    build_probe(exe)
+    return exe
+
+
+def _form(probe, modcod, F, want, **kw):
+    """the form front_choose names for such a call, which has to be the documented one"""
+    from test_rx_dispatch import front_form
+    got = front_form(probe, modcod, F, **kw)
+    assert got == want, (modcod, F, kw, got)
+    return got
 
 
 def _same(a, b):
@@ -76,26 +93,26 @@ def _both(O, case, modcod, form, rx, pl, sig, **kw):
 
 
 # ---------------------------------------------------------------------------------------------------------------- A
-DEFAULT_FORM = {"QPSK-S_8/9": "front_reg2_kernel<4>", "QPSK-S_3/5": "front_reg2_kernel<4>", "QPSK-N_8/9": "front_reg2_kernel<16>",
+DOCUMENTED = {"QPSK-S_8/9": "front_reg2_kernel<4>", "QPSK-S_3/5": "front_reg2_kernel<4>", "QPSK-N_8/9": "front_reg2_kernel<16>",
                 "8PSK-S_3/5": "front_reg_kernel<3, 8, false>", "8PSK-S_8/9": "front_reg_kernel<3, 8, false>", "8PSK-N_8/9": "front_reg_kernel<3, 22, false>",
                 "16APSK-S_8/9": "front_kernel<4, true, true> sliced", "16APSK-N_8/9": "front_kernel<4, true, true> sliced", "32APSK-S_3/4": "front_kernel<5, true, true> sliced"}
 
 
 @pytest.mark.parametrize("modcod", R.modcods())
-def test_a_default_form_of_every_modcod(O, Rx, modcod):
+def test_a_default_form_of_every_modcod(O, Rx, probe, modcod):
     """Three frames, 256-byte aligned sockets, no environment: QPSK takes front_reg2_kernel<4> (short) / <16> (normal: 16-byte aligned sockets, separable
     mapping, no interleaver), 8PSK front_reg_kernel<3, 8, false> (short: at most 8 symbols per lane) / <3, 22, false> (normal), 16APSK and 32APSK fall
-    through front_reg_try to the two-sweep front_kernel<4|5, true, true>, sliced over gridDim.y since 3 < 512 frames."""
+    past the register-resident forms to the two-sweep front_kernel<4|5, true, true>, sliced over gridDim.y since 3 < 512 frames."""
     _, pl, _, sigma = R.frames(O, modcod)
     rx = Rx(modcod, max_frames=3)
-    _both(O, "A", modcod, DEFAULT_FORM[modcod], rx, pl, R.sigmas(sigma, 3))
+    _both(O, "A", modcod, _form(probe, modcod, 3, DOCUMENTED[modcod]), rx, pl, R.sigmas(sigma, 3))
     rx.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- B
 @pytest.mark.parametrize("how", ["env_single", "pl_two_floats_in", "llr_two_floats_in"])
 @pytest.mark.parametrize("modcod", ["QPSK-S_8/9", "QPSK-N_8/9"])
-def test_b_qpsk_one_symbol_form_equals_the_pair_form(O, Rx, monkeypatch, modcod, how):
+def test_b_qpsk_one_symbol_form_equals_the_pair_form(O, Rx, probe, monkeypatch, modcod, how):
     """front_reg_kernel<2, 8, true> (short) / <2, 32, true> (normal): the pair form is refused by DVBS2HIP_FRONT_SINGLE=1 (read at each call), by a PL socket
     two floats into its allocation, or by an LLR socket two floats in (either is then 8-byte aligned only).  With sigma given its LLRs equal the pair
     form's (front_reg2_kernel, the default) bit for bit; with the estimator the moments are summed in another order and only the bars apply."""
@@ -106,37 +123,40 @@ def test_b_qpsk_one_symbol_form_equals_the_pair_form(O, Rx, monkeypatch, modcod,
     if how == "env_single":
         monkeypatch.setenv("DVBS2HIP_FRONT_SINGLE", "1")
     kw = dict(pl_off=2) if how == "pl_two_floats_in" else dict(llr_off=2) if how == "llr_two_floats_in" else {}
-    (given, _), _ = _both(O, "B", modcod, "front_reg_kernel<2, %d, true> (%s)" % (8 if "-S" in modcod else 32, how), rx, pl, sig, **kw)
+    form = _form(probe, modcod, 3, "front_reg_kernel<2, %d, true>" % (8 if "-S" in modcod else 32), align_pl=8 if how == "pl_two_floats_in" else 16,
+                 align_llr=8 if how == "llr_two_floats_in" else 16)
+    (given, _), _ = _both(O, "B", modcod, "%s (%s)" % (form, how), rx, pl, sig, **kw)
     assert _same(given, pair)
     rx.close()
 
 
 @pytest.mark.parametrize("modcod,form", [("QPSK-S_8/9", "front_reg_kernel<2, 8, false>"), ("QPSK-N_8/9", "front_kernel<2, true, true> sliced, general demapper")])
-def test_b_qpsk_general_demapper(O, Rx, monkeypatch, modcod, form):
+def test_b_qpsk_general_demapper(O, Rx, probe, monkeypatch, modcod, form):
     """DVBS2HIP_DEMAP_GENERAL=1 (read at create) leaves the mapping unmarked as separable: the short frame takes front_reg_kernel<2, 8, false> (log-sum-exp
     from the LDS table), the normal frame has no register-resident general form and falls to the two-sweep front_kernel<2, true, true>, sliced."""
     monkeypatch.setenv("DVBS2HIP_DEMAP_GENERAL", "1")
     _, pl, _, sigma = R.frames(O, modcod)
     rx = Rx(modcod, max_frames=3)
-    _both(O, "B", modcod, form, rx, pl, R.sigmas(sigma, 3))
+    _both(O, "B", modcod, _form(probe, modcod, 3, form.replace(", general demapper", ""), sep=0) + ", general demapper", rx, pl, R.sigmas(sigma, 3))
     rx.close()
 
 
 @pytest.mark.parametrize("modcod", ["QPSK-S_8/9", "QPSK-N_8/9", "8PSK-S_3/5", "8PSK-S_8/9", "8PSK-N_8/9"])
-def test_b_two_sweep_form_of_qpsk_and_8psk(O, Rx, monkeypatch, modcod):
-    """DVBS2HIP_FRONT_TWO_SWEEP=1 (read at each call) sends QPSK and 8PSK past front_reg_try: front_kernel<2|3, true, true>, sliced (3 < 512 frames; 8PSK
+def test_b_two_sweep_form_of_qpsk_and_8psk(O, Rx, probe, monkeypatch, modcod):
+    """DVBS2HIP_FRONT_TWO_SWEEP=1 (read at each call) sends QPSK and 8PSK past the register-resident forms: front_kernel<2|3, true, true>, sliced (3 < 512 frames; 8PSK
     takes 1024 symbols per trip and slice, QPSK's linear form as well)."""
     monkeypatch.setenv("DVBS2HIP_FRONT_TWO_SWEEP", "1")
     _, pl, _, sigma = R.frames(O, modcod)
     rx = Rx(modcod, max_frames=3)
-    _both(O, "B", modcod, "front_kernel<%d, true, true> sliced (DVBS2HIP_FRONT_TWO_SWEEP)" % chain(O, modcod).mc.bps, rx, pl, R.sigmas(sigma, 3))
+    form = _form(probe, modcod, 3, "front_kernel<%d, true, true> sliced" % chain(O, modcod).mc.bps)
+    _both(O, "B", modcod, form + " (DVBS2HIP_FRONT_TWO_SWEEP)", rx, pl, R.sigmas(sigma, 3))
     rx.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- C
 @pytest.mark.parametrize("F", [1, 3, 300, 513])
 @pytest.mark.parametrize("modcod", ["32APSK-S_3/4", "16APSK-S_8/9"])
-def test_c_slicing_of_the_two_sweep_kernel(O, Rx, modcod, F):
+def test_c_slicing_of_the_two_sweep_kernel(O, Rx, probe, modcod, F):
     """front_kernel<5|4, true, true>.  32APSK-S has 3240 symbols = 13 trips of 256 (the last with 168), 16APSK-S 4050 = 16 trips (the last with 210).
     F = 1: one frame, a slice per trip; F = 3: the same with three frames; F = 300: the cap of 1024 / 300 = 3 slices per frame (1280 / 1536 symbols
     each, the last shorter); F = 513: from 512 frames on unsliced, one workgroup walks the frame.  The frames are three distinct ones tiled with
@@ -144,7 +164,7 @@ def test_c_slicing_of_the_two_sweep_kernel(O, Rx, modcod, F):
     _, pl3, _, sigma = R.frames(O, modcod)
     pl, sig = pl3[np.arange(F) % 3], R.sigmas(sigma, F)
     rx = Rx(modcod, max_frames=513)
-    form = "front_kernel<%d, true, true> %s" % (chain(O, modcod).mc.bps, "unsliced" if F >= 512 else "sliced, F = %d" % F)
+    form = _form(probe, modcod, F, "front_kernel<%d, true, true>%s" % (chain(O, modcod).mc.bps, "" if F >= 512 else " sliced")) + (" unsliced" if F >= 512 else ", F = %d" % F)
     for s in (sig, None):
         LLR, EST = _tap(rx, pl, s)
         for f in range(3, F):
@@ -154,7 +174,7 @@ def test_c_slicing_of_the_two_sweep_kernel(O, Rx, modcod, F):
 
 
 # ---------------------------------------------------------------------------------------------------------------- D
-def test_d_located_form_equals_the_contiguous_call(O, Rx):
+def test_d_located_form_equals_the_contiguous_call(O, Rx, probe):
     """The located variant of front_reg2_kernel<4> (QPSK-S), front_reg_kernel<3, 8, false> (8PSK-S) and the sliced front_kernel<5, true, true> (32APSK-S):
     frame f read at SRC[f].  The nine frames lie in one device stream in shuffled order with gaps of 1e30, every start at an odd complex-sample
     index, so 8-byte aligned only (the pair kernel reads a located frame through a buffer descriptor and keeps its form).  LLRs and EST equal the
@@ -176,6 +196,7 @@ def test_d_located_form_equals_the_contiguous_call(O, Rx):
     stream = torch.from_numpy(host).cuda()
     assert stream.data_ptr() % 16 == 0
     for m in modcods:
+        print("\nFRONT64 D | %s | %s, frames at 8-byte aligned starts" % (m, _form(probe, m, 3, DOCUMENTED[m], align_pl=8, located=True)))
         _, pl, _, sigma = inputs[m]
         sig = R.sigmas(sigma, 3)
         src = torch.tensor([stream.data_ptr() + 8 * start[m, f] for f in range(3)], dtype=torch.int64, device="cuda")
@@ -192,7 +213,7 @@ def test_d_located_form_equals_the_contiguous_call(O, Rx):
 
 # ---------------------------------------------------------------------------------------------------------------- E
 @pytest.mark.parametrize("modcod", R.HIGH_SNR["modcods"])
-def test_e_high_llr_through_the_fused_entry(O, Rx, modcod):
+def test_e_high_llr_through_the_fused_entry(O, Rx, probe, modcod):
     """30 dB frames demapped with sigma 0.05, 0.1, 0.2: |LLR| up to several hundred.  front_reg_kernel<3, 8|22, false> (8PSK-S, 8PSK-N) and the sliced
     front_kernel<4|5, true, true> (16APSK-S, 32APSK-S), each through demap_symbols_s and, for the symbols whose weaker subset sums below 2^-100,
     demap_symbol_far.  The twin counts the symbols on either side of that threshold: both kinds are in the call.  Signs equal the sent code word."""
@@ -205,7 +226,7 @@ def test_e_high_llr_through_the_fused_entry(O, Rx, modcod):
     assert 0 < sum(far) < 3 * mc.N_xfec
     rx = Rx(modcod, max_frames=3)
     LLR, EST = _tap(rx, pl, sig)
-    _judge(O, "E", modcod, DEFAULT_FORM[modcod] + ", far path", pl, LLR, EST, sig)
+    _judge(O, "E", modcod, _form(probe, modcod, 3, DOCUMENTED[modcod]) + ", far path", pl, LLR, EST, sig)
     assert np.array_equal((LLR < 0).astype(np.int32), cw)
     rx.close()
 

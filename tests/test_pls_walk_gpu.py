@@ -3,7 +3,7 @@
 The buffer is the library's own transmitter's: 37 symbols of noise, then QPSK-S_8/9, 32APSK-S_3/4 twice, 16APSK-S_8/9, a dummy frame (the header of value 0 from the twin's
 generator), 8PSK-S_3/5, one QPSK-N_8/9 (a hop of 33282 symbols), QPSK-S_3/5, and the first 2000 symbols of a ninth frame.  The walk is integers behind the PLS decoder, so
 on the device's own decoder outputs at the candidates it has to equal the twin exactly, Q by bit pattern; end to end it is held to the float64 decoder at the search
-test's bar for q, 1e-4.  The library resolves a chain of few levels with one lane and a longer one by pointer doubling (api_pls_walk.hip, PLSW_LANE_LEVELS = 5 levels, so
+test's bar for q, 1e-4.  The library resolves a chain of few levels with one lane and a longer one by pointer doubling (pls_walk_choose of rx_dispatch.h, PLSW_LANE_LEVELS = 5 levels, so
 max_out 31 against 32 with a caller's table): MAX_OUT below takes every case through both."""
 import ctypes as C
 

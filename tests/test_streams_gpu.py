@@ -124,7 +124,7 @@ def test_frame_synchronizer_streams_against_the_oracle_and_single_stream_handles
     """S = 4 streams of 12 frames in calls of F/S = 1, 2, 3, 2, 3, 1 (32APSK-S_3/4: n = 3402 is no multiple of vec_width 8, so the unaveraged tail positions are in
     play), the one-task form, DVBS2HIP_SYNC_UNFUSED and DVBS2HIP_SYNC=valu.  Per stream against its own O.SyncFrame: DEL exact, Y_N2 bit-exact, TRI within
     2e-4 max(1, metric), FLG and get_metric[s] equal.  Against four single-stream handles: DEL, FLG, Y_N2 identical and TRI bit for bit -- at these frame counts the
-    single-stream handle takes the single walk of the average over frames (a call is cut into segments only from F >= 1536 frames on: k_sync.hip, sync_average_argmax),
+    single-stream handle takes the single walk of the average over frames (a call is cut into segments only from F >= 1536 frames on: rx_dispatch.h, sync_choose),
     which is the recurrence the S-stream kernel runs."""
     monkeypatch.delenv("DVBS2HIP_SYNC", raising=False)
     monkeypatch.delenv("DVBS2HIP_SYNC_UNFUSED", raising=False)

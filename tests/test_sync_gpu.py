@@ -183,17 +183,28 @@ def test_frame_synchronizer_at_size_locks_and_realigns_the_stream(O, Rx):
     rx.close(); rx2.close()
 
 
-def test_average_and_arg_max_over_many_short_frames(O, Rx):
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    """tools/plan_probe.cpp, which says what sync_choose (dvbs2_amd/csrc/rx_dispatch.h) picks under this process's knobs"""
+    from test_plan_digest import build_probe
+    exe = str(tmp_path_factory.mktemp("sync_gpu") / "plan_probe")
+    build_probe(exe)
+    return exe
+
+
+def test_average_and_arg_max_over_many_short_frames(O, Rx, monkeypatch, probe):
     """The thirteen-wave form of the average over frames / arg max (k_sync.hip, sync_metric_argmax_kernel<96>: short frames, 96 frames between two barriers) on a call of
     2 whole chunks + a partial one, then calls of 96, 1 and 132 frames (a whole chunk exactly, less than one, one + a partial one): delays and aligned frames equal to the
-    oracle's frame by frame, the metric within the correlators' tolerance, and every socket bit for bit what round 3's four-wave kernel gives (a child process with
-    DVBS2HIP_SYNC_ARGMAX4 set: the knob is read once per process)."""
-    import subprocess, sys, tempfile
+    oracle's frame by frame, the metric within the correlators' tolerance, and every socket bit for bit what round 3's four-wave kernel gives (a fresh handle with
+    DVBS2HIP_SYNC_ARGMAX4 set: the knob is read at each call).  `plan_probe sync` names the form either handle runs."""
+    from test_rx_dispatch import sync_forms
     modcod, F, off = "32APSK-S_3/4", 229, 1501
     _, pl, _, _ = make_pl_frames(O, modcod, 7, 9.0, seed=31)
     n = pl.shape[1] // 2
     stream = np.concatenate([np.zeros(2 * off, np.float32), np.tile(pl.reshape(-1), F // 7 + 2)])[:F * 2 * n].reshape(F, 2 * n)
     sf = O.SyncFrame(n, alpha=0.9, trigger=30.0, vec_width=8)
+    monkeypatch.delenv("DVBS2HIP_SYNC_ARGMAX4", raising=False)                  # (whatever the environment of the test run says)
+    assert all(sync_forms(probe, n, Fc)[1] == "sync_metric_argmax_kernel<96>" for Fc in (F, 96, 1, F - 97))
     rx = Rx(modcod, max_frames=F)
     d, flg, tri, Y = rx.sync_frame_synchronize(stream, with_flags=True)
     for f in range(F):
@@ -206,15 +217,14 @@ def test_average_and_arg_max_over_many_short_frames(O, Rx):
     assert np.array_equal(np.concatenate([q[0] for q in parts]), d) and np.array_equal(np.concatenate([q[3] for q in parts]), Y)
     assert np.array_equal(np.concatenate([q[2] for q in parts]).view(np.uint32), tri.view(np.uint32))
     rx.close(); rx2.close()
-    with tempfile.TemporaryDirectory() as td:
-        np.save(os.path.join(td, "x.npy"), stream)
-        code = ("import sys, numpy as np; sys.path.insert(0, %r); from dvbs2_amd.receiver import Dvbs2Hip; x = np.load(%r); rx = Dvbs2Hip(%r, max_frames=%d); "
-                "d, flg, tri, Y = rx.sync_frame_synchronize(x, with_flags=True); np.savez(%r, d=d, flg=flg, tri=tri, Y=Y)"
-                % (ROOT, os.path.join(td, "x.npy"), modcod, F, os.path.join(td, "o.npz")))
-        subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, DVBS2HIP_SYNC_ARGMAX4="1"))
-        o = np.load(os.path.join(td, "o.npz"))
-        assert np.array_equal(o["d"], d) and np.array_equal(o["flg"], flg) and np.array_equal(o["Y"], Y)
-        assert np.array_equal(o["tri"].view(np.uint32), tri.view(np.uint32))
+    monkeypatch.setenv("DVBS2HIP_SYNC_ARGMAX4", "1")
+    assert sync_forms(probe, n, F)[1] == "sync_metric_argmax4_kernel"
+    rx4 = Rx(modcod, max_frames=F)
+    d4, flg4, tri4, Y4 = rx4.sync_frame_synchronize(stream, with_flags=True)
+    rx4.close()
+    monkeypatch.delenv("DVBS2HIP_SYNC_ARGMAX4")
+    assert np.array_equal(d4, d) and np.array_equal(flg4, flg) and np.array_equal(Y4, Y)
+    assert np.array_equal(tri4.view(np.uint32), tri.view(np.uint32))
 
 
 def test_two_task_form_and_correlations(O, Rx):

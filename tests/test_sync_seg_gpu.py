@@ -5,24 +5,18 @@ short-frame call of 1536 frames or more runs) held to float64, to the oracle and
     positions, on the edge positions in the frames behind every seam), two calls on one handle: DEL / FLG / Y equal to the oracle's, the delay the one of the float64 first
     maximum, TRI within 4 x the float32 single walk's own largest error of the float64 maximum (the margin tests/test_fine_sync_fp64_gpu.py gives a reordered fp32 sum over
     the reference's own error), TRI the bump itself where the bump sits on a position that is not averaged;
-(b) the same calls in a child process with DVBS2HIP_SYNC_SEGMENTS=1 (the single walk; the switch is read once per process): DEL / FLG / Y equal, TRI bit for bit equal
+(b) the same calls on a fresh handle with DVBS2HIP_SYNC_SEGMENTS=1 (the single walk; the switch is read at each call): DEL / FLG / Y equal, TRI bit for bit equal
     over the first segment of the first call, within 2 x the bar of (a) anywhere else (each side is entitled to that bar against float64);
 (c) the one-task form on a real stream, one call of 1632 frames against calls of 1536 + 96, the oracle and the single walk;
 (d) the located form against the delayed copy on that stream.
-Every case asks `plan_probe syncseg` (the library's sync_segment_plan) what its call is cut into and requires two segments at least.  tests/test_sync_seg_ref.py shows
+Every case asks `plan_probe sync` (the library's sync_choose, dvbs2_amd/csrc/rx_dispatch.h, under this process's knobs) which arg-max form its call takes and what it is
+cut into, and requires the thirteen-wave form in two segments at least; the single walk's calls have to come back as one segment.  tests/test_sync_seg_ref.py shows
 on the CPU that these bars reject each mistake the segmented form invites.  Measured figures: results/sync_segments/README.md."""
 import hashlib
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if __name__ == "__main__":
-    sys.path.insert(0, ROOT)
 
 import sync_seg_ref as R
 
@@ -84,30 +78,20 @@ def device_stream(modcod, x, cuts):
     return [np.concatenate([p[k] for p in parts]) for k in range(4)]
 
 
-if __name__ == "__main__":      # the child of (b) and (c): `synthetic CASE SEG_F OUT.npz` | `stream X.npy OUT.npz`, run with DVBS2HIP_SYNC_SEGMENTS=1
-    if sys.argv[1] == "synthetic":
-        got = device_synthetic(CASES[int(sys.argv[2])], int(sys.argv[3]))
-        np.savez(sys.argv[4], **{"%s%d" % (k, c): got[c][k] for c in range(CALLS) for k in ("DEL", "FLG", "TRI", "Yd", "metric")})
-    else:
-        DEL, FLG, TRI, Y = device_stream(STREAM[0], np.load(sys.argv[2]), [(0, STREAM[1])])
-        np.savez(sys.argv[3], DEL=DEL, FLG=FLG, TRI=TRI, Yd=digest(Y))
-    sys.exit(0)
-
-
-def child(args):
-    """a fresh process with the single walk (never an exec: the parent has the GPU open)"""
-    subprocess.check_call([sys.executable, os.path.abspath(__file__)] + [str(a) for a in args], env=dict(os.environ, DVBS2HIP_SYNC_SEGMENTS="1"))
-
-
 @pytest.fixture(scope="module")
 def plan_of(tmp_path_factory):
-    """(n, F) -> (nseg, seg_F) of the library's sync_segment_plan with the default cap"""
+    """(n, F) -> (nseg, seg_F) of a one-stream call as the library's sync_choose cuts it under the knobs this process has at that moment; the form is the thirteen-wave one"""
     from test_plan_digest import build_probe
-    from test_sync_seg_plan import segment_plans, MAX_SEG
-    assert "DVBS2HIP_SYNC_SEGMENTS" not in os.environ, "this process has to run the default form"
+    from test_rx_dispatch import SYNC, ask
+    assert "DVBS2HIP_SYNC_SEGMENTS" not in os.environ and "DVBS2HIP_SYNC_ARGMAX4" not in os.environ, "this process has to run the default form"
     exe = str(tmp_path_factory.mktemp("sync_seg_gpu") / "plan_probe")
     build_probe(exe)
-    return lambda n, F: segment_plans(exe, [(n, F, MAX_SEG)])[0]
+
+    def plan(n, F):
+        m = SYNC.match(ask(exe, "sync", [(n, F, 1, 16, 1, 1, 1, 0)], inherit=True)[0])
+        assert m[5] == "sync_metric_argmax_kernel<96>", m[0]
+        return int(m[7]), int(m[8])
+    return plan
 
 
 @pytest.fixture(scope="module", params=range(len(CASES)), ids=["%s-F%d-a%g-v%d" % c for c in CASES])
@@ -157,15 +141,16 @@ def test_synthetic_metric_in_segments_against_fp64_and_the_oracle(O, case):
         assert g["metric"].view(np.uint32) == g["TRI"][-1].view(np.uint32) and g["flag"] == bool(g["FLG"][-1])
 
 
-def test_synthetic_metric_in_segments_against_the_single_walk(case):
-    k, seg_F, got, ref, E = (case[q] for q in ("k", "seg_F", "got", "ref", "E"))
-    with tempfile.TemporaryDirectory() as td:
-        child(["synthetic", k, seg_F, os.path.join(td, "o.npz")])
-        o = dict(np.load(os.path.join(td, "o.npz")))
+def test_synthetic_metric_in_segments_against_the_single_walk(case, plan_of, monkeypatch):
+    k, n, seg_F, got, ref, E = (case[q] for q in ("k", "n", "seg_F", "got", "ref", "E"))
+    monkeypatch.setenv("DVBS2HIP_SYNC_SEGMENTS", "1")
+    assert plan_of(n, CASES[k][1]) == (1, CASES[k][1])
+    walk = device_synthetic(CASES[k], seg_F)                        # a fresh handle, the same inputs
+    monkeypatch.delenv("DVBS2HIP_SYNC_SEGMENTS")
     for call in range(CALLS):
-        g, mx64 = got[call], ref[call][0]
-        assert np.array_equal(o["DEL%d" % call], g["DEL"]) and np.array_equal(o["FLG%d" % call], g["FLG"]) and str(o["Yd%d" % call]) == g["Yd"], call
-        a, b = g["TRI"], o["TRI%d" % call]
+        g, o, mx64 = got[call], walk[call], ref[call][0]
+        assert np.array_equal(o["DEL"], g["DEL"]) and np.array_equal(o["FLG"], g["FLG"]) and o["Yd"] == g["Yd"] and np.array_equal(o["Y"], g["Y"]), call
+        a, b = g["TRI"], o["TRI"]
         if call == 0:
             assert np.array_equal(a[:seg_F].view(np.uint32), b[:seg_F].view(np.uint32))
         d = float(np.max(np.abs(a.astype(np.float64) - b) / mx64))
@@ -209,7 +194,7 @@ def stream_twin(O, x, n):
     return d, flg, met, Ys, mx64, R.rel_err(mx32, mx64)
 
 
-def test_one_task_form_on_a_real_stream_in_segments(O, stream):
+def test_one_task_form_on_a_real_stream_in_segments(O, stream, plan_of, monkeypatch):
     modcod, F, off = STREAM
     x, n, seg_F = stream["x"], stream["n"], stream["seg_F"]
     DEL, FLG, TRI, Y = stream["one"]
@@ -225,12 +210,12 @@ def test_one_task_form_on_a_real_stream_in_segments(O, stream):
     same = min(cut, seg_F)                                          # both cuts walk from the reset average up to their first seam
     assert np.array_equal(TRI2[:same].view(np.uint32), TRI[:same].view(np.uint32))
     d2 = float(np.max(np.abs(TRI2.astype(np.float64) - TRI) / mx64))
-    # the single walk in a child process
-    with tempfile.TemporaryDirectory() as td:
-        np.save(os.path.join(td, "x.npy"), x)
-        child(["stream", os.path.join(td, "x.npy"), os.path.join(td, "o.npz")])
-        o = dict(np.load(os.path.join(td, "o.npz")))
-    assert np.array_equal(o["DEL"], DEL) and np.array_equal(o["FLG"], FLG) and str(o["Yd"]) == digest(Y)
+    # the single walk on a fresh handle
+    monkeypatch.setenv("DVBS2HIP_SYNC_SEGMENTS", "1")
+    assert plan_of(n, F) == (1, F)
+    o = dict(zip(("DEL", "FLG", "TRI", "Y"), device_stream(modcod, x, [(0, F)])))
+    monkeypatch.delenv("DVBS2HIP_SYNC_SEGMENTS")
+    assert np.array_equal(o["DEL"], DEL) and np.array_equal(o["FLG"], FLG) and np.array_equal(o["Y"], Y)
     assert np.array_equal(o["TRI"][:seg_F].view(np.uint32), TRI[:seg_F].view(np.uint32))
     d1 = float(np.max(np.abs(o["TRI"].astype(np.float64) - TRI) / mx64))
     print("sync_seg (c) %s F %d: walk error %.3g; one call against 1536 + 96: %.3g = %.2f x; against the single walk %.3g = %.2f x; device against the oracle's metric %.3g"

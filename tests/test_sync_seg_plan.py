@@ -1,5 +1,5 @@
 """How the frame synchronizer cuts a call's frames into segments for the average over frames (CPU; `plan_probe syncseg` links the library's host code and prints what
-sync_segment_plan -- the function sync_average_argmax of k_sync.hip calls -- answers): the nine MODCODs' PL frame lengths, call lengths on both sides of every threshold,
+sync_segment_plan -- the function sync_choose of dvbs2_amd/csrc/rx_dispatch.h calls, with the cap DVBS2HIP_SYNC_SEGMENTS gives at that call -- answers): the nine MODCODs' PL frame lengths, call lengths on both sides of every threshold,
 every cap.  tests/test_sync_seg_gpu.py asks the same probe whether its cases are cut at all."""
 import subprocess
 

@@ -113,7 +113,7 @@ static int insts_main()
     return 0;
 }
 
-// `plan_probe syncseg N F CAP [N F CAP ..]`: a line `nseg seg_F` per triple -- how sync_segment_plan (k_sync.hip: the function the frame synchronizer's dispatch calls, the
+// `plan_probe syncseg N F CAP [N F CAP ..]`: a line `nseg seg_F` per triple -- how sync_segment_plan (rx_dispatch.h: the function sync_choose calls, the
 // handle's scratch present) cuts a one-stream call of F frames of N positions for the average over frames when at most CAP segments are allowed.
 // tests/test_sync_seg_plan.py and tests/test_sync_seg_gpu.py read it.
 static int syncseg_main(int argc, char **argv)
@@ -126,8 +126,45 @@ static int syncseg_main(int argc, char **argv)
     return 0;
 }
 
+// The receive path's choosers (rx_dispatch.h): a line per case -- the kernel's name as the code object and the results files spell it, then the launch geometry.  The facts
+// of a case are integers on the command line (alignments in bytes, flags 0 / 1), several cases one after the other; the DVBS2HIP_* knobs come from the environment.
+//   front  BPS SEP ITL_COLS N_SYM PL_FRAME F ALIGN_PL ALIGN_LLR LOCATED FROM_PL DEINTERLEAVE
+//   fir    T N_PER S ALIGN_X ALIGN_Y HAVE_FRAG          upfir  T OSF N_IN ALIGN_X ALIGN_Y HAVE_FRAG
+//   sync   N FS S ALIGN_X HAVE_FRAG HAVE_SEG ONE_TASK LOCATED   (the delay line of 4 (N + 1) floats every handle has)
+//   lr     S N ALIGN_X ALIGN_Y                          walk   K
+// tests/test_rx_dispatch.py walks them; the fp64 GPU tests ask which form their cases reach.
+static int rx_main(const char *mode, int argc, char **argv)
+{
+    const int per = !strcmp(mode, "front") ? 11 : !strcmp(mode, "sync") ? 8 : !strcmp(mode, "lr") ? 4 : !strcmp(mode, "walk") ? 1 : 6;
+    if (argc < 2 + per || (argc - 2) % per) { std::fprintf(stderr, "usage: plan_probe %s followed by %d integers per case\n", mode, per); return 2; }
+    for (int i = 2; i + per <= argc; i += per) {
+        long long a[11];
+        for (int k = 0; k < per; k++) a[k] = atoll(argv[i + k]);
+        if (!strcmp(mode, "front")) {
+            const FrontChoice ch = front_choose({(int)a[0], a[1] != 0, (int)a[2], (int)a[3], (int)a[4], (int)a[5], (unsigned)a[6], (unsigned)a[7], a[8] != 0, a[9] != 0, a[10] != 0});
+            std::printf("front: %s | block %d grid %d x %d slice_chunk %d\n", front_choice_name(ch).c_str(), ch.block, (int)a[5], ch.grid_y, ch.slice_chunk);
+        } else if (!strcmp(mode, "fir") || !strcmp(mode, "upfir")) {
+            const FirChoice ch = mode[0] == 'f' ? fir_choose((int)a[0], a[1], (int)a[2], (unsigned)a[3], (unsigned)a[4], a[5] != 0) : upfir_choose((int)a[0], (int)a[1], a[2], (unsigned)a[3], (unsigned)a[4], a[5] != 0);
+            std::printf("%s: %s | grid %u x %u tiles_per_wg %d\n", mode, fir_choice_name(ch).c_str(), ch.grid_x, ch.grid_y, ch.family == FIR_MFMA ? ch.tiles_per_wg : 0);
+        } else if (!strcmp(mode, "sync")) {
+            const SyncFacts c = {(int)a[0], (int)a[1], (int)a[2], 4 * ((int)a[0] + 1), (unsigned)a[3], a[4] != 0, a[5] != 0, a[6] != 0, a[7] != 0};
+            const SyncChoice ch = sync_choose(c);
+            std::printf("sync: %s grid %u x %d fused %d | %s nwg %d nseg %d seg_F %d | delay line grid %d x %d x %d\n", sync_corr_name(c, ch).c_str(), ch.corr_grid, c.S, ch.fused,
+                        sync_argmax_name(ch).c_str(), ch.nwg, ch.seg.nseg, ch.seg.seg_F, ch.vd_gx, ch.vd_gy, c.S);
+        } else if (!strcmp(mode, "lr")) {
+            const LrChoice ch = lr_choose((int)a[0], (int)a[1], (unsigned)a[2], (unsigned)a[3]);
+            std::printf("lr: %s | launches %d timeout_us %llu workgroups per frame %d rotation %s\n", lr_choice_name(ch).c_str(), ch.one_launch ? 1 : 3, ch.timeout_us, ch.cpf,
+                        ch.pair ? "sff_rotate2_kernel<0>" : "sff_rotate_kernel<0>");
+        } else
+            std::printf("walk: %s\n", pls_walk_choose((int)a[0]) ? "pls_walk_lane_kernel" : "pls_walk_double_kernel");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    for (const char *m : {"front", "fir", "upfir", "sync", "lr", "walk"})
+        if (argc > 1 && !strcmp(argv[1], m)) return rx_main(m, argc, argv);
     if (argc > 1 && !strcmp(argv[1], "syncseg")) return syncseg_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "digest")) return digest_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "choice")) return choice_main(argc, argv);
